@@ -11,13 +11,18 @@ ranks / wall time between barriers.
   python bench.py --gpus N --steps K --warmup W         (no launcher: starts its own N rank processes, see self_launch)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --full ...                            (also the secondary measurements, see below)
+  python bench.py --dump-outputs DIR ...                (also writes what the last timed step computed, DIR/<name>.npy)
 
 Multi-GPU: the batch shards trivially, no data-path collective; after each rollout the ranks all-gather the
 terminal states [B_local][nX] over RCCL/xGMI (what a discopt line-search consumes).  The ranks never import
 torch: the launcher only provides RANK / LOCAL_RANK / WORLD_SIZE, the communicator is RCCL behind the C ABI
-(include/trep_amd.h tg_comm_*, trep_amd/rccl.py).  The headline value is WEAK scaling (8192 trajectories per GPU);
-the same run also measures BASELINE config 3 as written -- 8192 trajectories in total, B/N per GPU -- and reports
-it as the "strong_scaling" object, and config 4 (discopt on 256 puppet seeds, N = 1000) as the "discopt" object.
+(include/trep_amd.h tg_comm_*, trep_amd/rccl.py).  The headline value is WEAK scaling (8192 trajectories per GPU).
+
+A plain run measures the headline line only.  With --full the same run also measures BASELINE config 3 as written
+(8192 trajectories in total, B/N per GPU) as the "strong_scaling" object when there is more than one rank, config 4
+(discopt on 256 puppet seeds, N = 1000) as the "discopt" object, and the CPU oracle on a sample of the same
+rollouts as the "cpu_baseline" object.
 """
 import argparse
 import json
@@ -183,13 +188,13 @@ def expected_line_keys(args, world):
     object and the CPU baseline are rank 0's own figures and do not depend on how many ranks run)."""
     keys = ["metric", "value", "unit", "n_gpus", "rccl_ranks", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
             "dtype", "data", "config", "roofline"]
-    if world > 1:
+    if world > 1 and args.full:
         keys.append("%s_scaling" % ("strong" if args.scaling == "weak" else "weak"))
     if args.system == "puppet":
         keys.append("fp64")
-        if not args.no_discopt:
+        if args.full and not args.no_discopt:
             keys.append("discopt")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         keys.append("cpu_baseline")
     return keys
 
@@ -266,8 +271,54 @@ def dry_run_rank(args, world, rank):
                       "shards": shards, "run_key": os.environ.get("TREPAMD_RUN_KEY"), "line_keys": expected_line_keys(args, world)}))
 
 
-def measure_rollouts(args, system, Q0, U, K, dt, B, N, device, comm, gather_rows):
-    """W warm-up + K timed passes of B trajectories x N steps on this rank; returns timing and status figures."""
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs writes at most this much in all
+DUMP_ROWS_MAX = 8192          # per-trajectory outputs of a larger batch: a fixed, seeded sample of this many trajectories
+DUMP_X_TRAJECTORIES = 64      # whole state trajectories X[b] (N + 1 rows each): a fixed, seeded sample of this many
+DUMP_X_BYTES_MAX = 32 << 20   # ... fewer when N is so long that 64 of them would exceed this
+
+
+def sample_rows(n, most, seed):
+    """range(n) when n <= most, otherwise a fixed seeded sample of `most` of its indices in increasing order."""
+    if n <= most:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, most, replace=False))
+
+
+def dump_outputs(dirname, mvi, X_dev, N, iters, status, gathered):
+    """--dump-outputs: what the last timed pass handed its caller, as float64 DIR/<name>.npy.  Per trajectory (rows.npy says
+    which): the final state q_final / p_final / lambda_final and the pass's Newton iterations and status; X_sample [S][N+1][nX],
+    the whole written trajectories of S sampled ones (X_sample_rows.npy); with a communicator, the all-gathered terminal
+    states [rows][nX] (terminal_gathered.npy, every rank's shard padded to the largest)."""
+    from trep_amd import _lib
+    L = _lib.lib()
+    B, nX = mvi.batch, mvi.nX
+    rows = sample_rows(B, DUMP_ROWS_MAX, 1)
+    out = {"rows": rows, "q_final": mvi.q2[rows], "p_final": mvi.p2[rows], "lambda_final": mvi.lambda1[rows],
+           "newton_iterations": iters[rows], "status": status[rows]}
+    if X_dev is not None:
+        traj_bytes = 8 * (N + 1) * nX
+        xrows = sample_rows(B, max(1, min(DUMP_X_TRAJECTORIES, DUMP_X_BYTES_MAX // traj_bytes)), 2)
+        X = np.zeros((len(xrows), N + 1, nX))
+        for i, b in enumerate(xrows):    # X[b] is contiguous on the device: one copy per sampled trajectory
+            _lib.check(L.tg_memcpy_d2h(mvi._device, X[i].ctypes.data, X_dev + int(b) * traj_bytes, traj_bytes))
+        out["X_sample_rows"], out["X_sample"] = xrows, X
+    if gathered is not None:
+        dev, n_rows = gathered
+        G = mvi.download(dev, (n_rows, nX))
+        grows = sample_rows(n_rows, DUMP_ROWS_MAX, 3)
+        out["terminal_gathered_rows"], out["terminal_gathered"] = grows, G[grows]
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_BYTES_MAX:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB, more than %d MB" % (total / 2.0 ** 20, DUMP_BYTES_MAX >> 20))
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
+def measure_rollouts(args, system, Q0, U, K, dt, B, N, device, comm, gather_rows, dump_dir=None):
+    """W warm-up + K timed passes of B trajectories x N steps on this rank; returns timing and status figures.  With
+    `dump_dir`, the outputs of the last timed pass are written there after the timing (dump_outputs)."""
     import trep_amd
     from trep_amd import _lib
     L = _lib.lib()
@@ -326,6 +377,9 @@ def measure_rollouts(args, system, Q0, U, K, dt, B, N, device, comm, gather_rows
     res = {"elapsed": elapsed, "launches": n_launch, "kernel_ms": kernel_ms, "newton_iterations": int(iters.sum()),
            "failed": int((status != 0).sum()), "info": mvi.info(), "specialised": bool(specialised), "nX": mvi.nX, "nU": mvi.nU, "nc": mvi.nc,
            "spec_library": os.path.relpath(kinfo["spec_library"], ROOT) if kinfo["spec_library"] else None}
+    if dump_dir is not None:   # with --no-x the collective gathers terminal states nobody wrote: nothing to dump there
+        gathered = (gather, comm.world * gather_rows) if comm is not None and X_dev is not None else None
+        dump_outputs(dump_dir, mvi, X_dev, N, iters, status, gathered)
     mvi.close()
     return res
 
@@ -339,9 +393,14 @@ def main():
     ap.add_argument("--rollout-steps", type=int, default=200, help="DEL steps per trajectory per pass")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="headline line: weak = --batch per GPU (default), strong = --batch in total (BASELINE config 3 as written); "
-                         "with more than one rank the other mode is measured too and reported next to it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-discopt", action="store_true", help="skip the discopt iterations/s measurement (BASELINE config 4)")
+                         "with more than one rank and --full the other mode is measured too and reported next to it")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline, discopt iterations/s (BASELINE "
+                         "config 4) and, with more than one rank, the other scaling mode")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as float64 DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-discopt", action="store_true", help="with --full: skip the discopt iterations/s measurement (BASELINE config 4)")
     ap.add_argument("--discopt-seeds", type=int, default=256)
     ap.add_argument("--discopt-horizon", type=int, default=1000)
     ap.add_argument("--no-x", action="store_true", help="do not write the state trajectory X to HBM")
@@ -357,6 +416,8 @@ def main():
     ap.add_argument("--dry-run-ranks", action="store_true",
                     help="ranks only do the communicator-id rendezvous and the shard arithmetic (no GPU call): CPU test of the launcher")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)          # never returns; this process makes no GPU call
@@ -368,7 +429,7 @@ def main():
     if args.dry_run_ranks:
         dry_run_rank(args, world, rank)
         return
-    want_cpu = not args.no_cpu_baseline and rank == 0 and args.system == "puppet"      # rank 0's host cores, whatever the world size
+    want_cpu = args.full and not args.no_cpu_baseline and rank == 0 and args.system == "puppet"   # rank 0's host cores, whatever the world size
     if want_cpu:      # compile the checker (a `make` child process) BEFORE this process touches the GPU
         from oracle import oracle as _oracle
         _oracle.build()
@@ -400,17 +461,18 @@ def main():
         return (Q0[lo:hi], None if U is None else U[lo:hi], None if K is None else K[lo:hi], hi - lo,
                 padded_rows(B, world))
 
-    modes = [args.scaling] + ([("strong" if args.scaling == "weak" else "weak")] if world > 1 else [])
+    modes = [args.scaling] + ([("strong" if args.scaling == "weak" else "weak")] if world > 1 and args.full else [])
     results = {}
     for mode in modes:
+        dump_dir = args.dump_outputs if mode == args.scaling and rank == 0 else None    # the headline's outputs, rank 0's view
         if mode == "weak":
-            results[mode] = (measure_rollouts(args, system, Q0, U, K, dt, B, N, local_rank, comm, B), world * B, B)
+            results[mode] = (measure_rollouts(args, system, Q0, U, K, dt, B, N, local_rank, comm, B, dump_dir), world * B, B)
         else:
             q, u, k, b_local, b_max = shard_of_global()
-            results[mode] = (measure_rollouts(args, system, q, u, k, dt, b_local, N, local_rank, comm, b_max), B, b_local)
+            results[mode] = (measure_rollouts(args, system, q, u, k, dt, b_local, N, local_rank, comm, b_max, dump_dir), B, b_local)
 
     discopt = None
-    if not args.no_discopt and args.system == "puppet":
+    if args.full and not args.no_discopt and args.system == "puppet":
         import bench_discopt
         d = bench_discopt.measure(args.discopt_seeds, args.discopt_horizon, quasi=1, newton=1, comm=comm, device=local_rank)
         discopt = {k: d[k] for k in ("iters_per_s", "seeds", "horizon", "n_gpus", "seed_iterations_counted", "elapsed_s",
@@ -491,7 +553,7 @@ def main():
         if want_cpu:
             out["cpu_baseline"] = cpu_baseline(system, Q0, K, dt)
             out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
         missing = [k for k in expected_line_keys(args, world) if k not in out]
         if missing:       # the measured line is printed whatever the self-check says; the ranks still meet at the barrier below

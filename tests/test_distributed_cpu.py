@@ -235,7 +235,7 @@ def test_bench_self_launcher_dry_run(tmp_path):
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TREPAMD_RUN_KEY")}
     env["TREPAMD_RENDEZVOUS_DIR"] = str(tmp_path)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-ranks", "--batch", "8193"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-ranks", "--batch", "8193", "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=100)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -248,6 +248,51 @@ def test_bench_self_launcher_dry_run(tmp_path):
     for key in ("roofline", "fp64", "cpu_baseline", "discopt", "strong_scaling", "n_gpus", "rccl_ranks"):
         assert key in out["line_keys"], (key, out["line_keys"])
     assert not os.listdir(str(tmp_path))          # the rendezvous files are gone
+
+
+@pytest.mark.timeout(120)
+def test_bench_plain_line_leaves_secondary_measurements_to_full(tmp_path):
+    """Without --full the line is the headline measurement only: no CPU baseline, discopt or second scaling mode."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "TREPAMD_RUN_KEY")}
+    env["TREPAMD_RENDEZVOUS_DIR"] = str(tmp_path)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run-ranks"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=100)
+    assert r.returncode == 0, r.stderr[-2000:]
+    keys = json.loads(r.stdout.strip().splitlines()[-1])["line_keys"]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in keys, (key, keys)
+    for key in ("cpu_baseline", "discopt", "strong_scaling"):
+        assert key not in keys, (key, keys)
+
+
+def test_bench_dump_outputs_writes_float64_arrays(tmp_path):
+    """bench.dump_outputs on a stand-in batch without a trajectory buffer: one float64 .npy per output, the seeded sample of
+    the per-trajectory rows the same from call to call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.pop(0)
+
+    class Batch(object):
+        batch, nX = bench.DUMP_ROWS_MAX + 5, 4
+        q2 = np.arange(batch * 3, dtype=float).reshape(batch, 3)
+        p2 = -q2[:, :1]
+        lambda1 = np.zeros((batch, 0))
+
+    iters, status = np.full(Batch.batch, 3, dtype=np.int32), np.zeros(Batch.batch, dtype=np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), Batch(), None, 10, iters, status, None)
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["lambda_final.npy", "newton_iterations.npy", "p_final.npy", "q_final.npy", "rows.npy", "status.npy"]
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype == np.float64 and a.shape[0] == bench.DUMP_ROWS_MAX and (a == b).all(), n
+    rows = np.load(str(tmp_path / "a" / "rows.npy")).astype(np.int64)
+    assert (np.diff(rows) > 0).all() and (np.load(str(tmp_path / "a" / "q_final.npy")) == Batch.q2[rows]).all()
 
 
 def test_bench_refuses_a_rank_count_that_contradicts_the_launcher():
