@@ -315,6 +315,30 @@ void *tg_batch_stream(tg_batch *b);
  * number of launches and the sum of their durations in milliseconds. */
 int tg_batch_timing(tg_batch *b, int32_t reset, int32_t *n_launches, double *total_ms);
 
+/* Per-trajectory parameters: one batch, many parameter sets, without rebuilding the schedule or the specialised kernels.
+ * The reference changes them one system at a time with Frame.set_mass (trep/frame.py), the Gravity.gravity setter
+ * (trep/potentials/gravity.py) and Damping.set_damping_coefficient (trep/forces/damping.py); a row of the table acts as a
+ * system rebuilt with its values.  Blocks of a row:
+ *   inertia [n_bodies][4]  (mass, Ixx, Iyy, Izz) of every massive frame, in System.masses order
+ *   gravity [3]            the gravity vector (sum over the system's Gravity potentials)      -- systems with a Gravity only
+ *   damping [nd]           total damping coefficient of every dynamic config                  -- systems with a Damping only
+ * tg_system_parameters: sizes_out = n_bodies, nd, has_gravity, has_damping, and the system's own values (null outputs skipped).
+ * tg_batch_set_parameters: `rows` rows per block (null block: the system's values in every row); trajectory t -- its batch
+ * index after any subset remapping -- uses row t / group; rows * group == batch, or rows == 1 for the whole batch.  Values must
+ * be finite (a zero mass is allowed); a massless frame stays massless.  TG_ERR_INVALID, with the table unchanged, for bad
+ * shapes, non-finite values or a block the system does not have.  The upload is ordered on the batch's stream: launches already
+ * enqueued keep their table.  While a table is set every mode runs a parameter kernel (the loaded specialised library's if it
+ * has one for the mode -- rollout, deriv1, deriv2z -- else the generic one); the forward-mode entry points (*_forward) return
+ * TG_ERR_UNSUPPORTED.  tg_batch_clear_parameters returns to the default kernels.
+ * tg_batch_par_info: out[0] bit m = mode m has a specialised parameter kernel loaded; out[1] / out[2] bit m = a mode-m launch went
+ * through a specialised / generic parameter kernel; out[3] / out[4] the number of such launches (tg_batch_info counts only the
+ * default kernels); out[5] rows of the current table (0: none); out[6] its group; out[7] 0. */
+int tg_system_parameters(const tg_system *sys, int32_t sizes_out[4], double *inertia, double *gravity, double *damping);
+int tg_batch_set_parameters(tg_batch *b, int32_t rows, int32_t group, const double *inertia_host, const double *gravity_host,
+                            const double *damping_host);
+int tg_batch_clear_parameters(tg_batch *b);
+int tg_batch_par_info(const tg_batch *b, int32_t out[8]);
+
 /* ------------------------------------------------------------------------------------------------------
  * Device-side discopt primitives: the direct caller of the MidpointVI path.
  * Everything below takes DEVICE pointers (tg_device_alloc) and is asynchronous; tg_device_synchronize or any

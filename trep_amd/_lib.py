@@ -22,6 +22,7 @@ _c_ip = ctypes.POINTER(ctypes.c_int32)
 F_Q1, F_Q2, F_P1, F_P2, F_U1, F_LAMBDA1 = 0, 1, 2, 3, 4, 5
 F_D1_BASE = 10  # TG_F_Q2_DQ1; order q2_d{q1,p1,u1,k2}, p2_d*, l1_d*
 OK, NOT_CONVERGED, SINGULAR = 0, 1, 2
+ERR_INVALID = -1  # TG_ERR_INVALID
 
 
 
@@ -103,6 +104,10 @@ _SIGNATURES = {
     "tg_system_spec_key": (ctypes.c_uint64, [ctypes.c_void_p]),
     "tg_batch_load_specialized": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p]),
     "tg_batch_info": (ctypes.c_int, [ctypes.c_void_p, _c_ip]),
+    "tg_system_parameters": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_set_parameters": (ctypes.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
+    "tg_batch_clear_parameters": (ctypes.c_int, [_vp]),
+    "tg_batch_par_info": (ctypes.c_int, [_vp, _c_ip]),
     "tg_batch_stream": (ctypes.c_void_p, [ctypes.c_void_p]),
     # device-side discopt primitives
     "tg_batch_set_from_trajectories": (ctypes.c_int, [_vp, _i32, _i32, _f64, _f64, _vp, _vp, _i32]),

@@ -255,6 +255,13 @@ struct RunArgs {
     // derivative of the quantity along seed1 (and seed2) instead of the quantity.
     const int *seed1, *seed2;
 };
+// Per-trajectory parameter table of the PAR kernels (tg_batch_set_parameters), passed beside RunArgs (whose layout the host emulation
+// mirrors): row r = [mass, Ixx, Iyy, Izz of every body | gravity [3] | damping [nd]], `stride` doubles apart; trajectory t (after
+// tg_remap_trajectory) uses row t / group.  Every block is complete: the host fills an omitted one with the system's own values.
+struct ParTable {
+    const double *rows;
+    int group, stride;
+};
 // which trajectory of the batch a launch's i-th trajectory is (RunArgs::remap_*); A.batch for an index past the subset (an idle team)
 template <class ARGS> TG_HD int tg_remap_trajectory(const ARGS &A, int i) {
     if (A.remap_len <= 0) return i;
@@ -397,7 +404,7 @@ template <int V> struct IntTag { static constexpr int value = V; };
 
 // Real: the scalar the trajectory's LDS slice holds -- double everywhere except the forward-mode kernels of the continuous dynamics (dual.hpp),
 // which run dynamics / dyn_deriv1 / lagrangian and what those call on Dual numbers; every other member is only ever instantiated for double.
-template <int TEAM, bool SPRINGS = false, class PROG = CProg, class Real = double>
+template <int TEAM, bool SPRINGS = false, class PROG = CProg, class Real = double, bool PAR = false>
 struct Core {
     TG_HD bool has_cs() const { return SPRINGS && P.has_cs; }
     // Potentials on a single config: d1 = V_dq, d2 = V_dqdq, d3 = V_dqdqdq of config i at the value q.  ConfigSpring
@@ -454,6 +461,11 @@ struct Core {
     int swc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, swr = 0, swcol = 0;
     bool swact = false;
     double tdamp = 0.0;
+    // PAR kernels: the trajectory's parameter row from its gravity entry on (ParTable: body inertias before, damping after).  The
+    // default kernels read the schedule's values instead -- constants of the specialised kernels -- and never touch this pointer.
+    const double *par = nullptr;
+    template <class PP> TG_HD double grav_of(PP &Pl, int k) const { if constexpr (PAR) return par[k]; else return Pl.grav[k]; }
+    template <class PP> TG_HD double damp_of(PP &Pl, int i) const { if constexpr (PAR) return par[3 + i]; else return Pl.damp[i]; }
     // world-frame evaluation (eval_world): the lane's row of P.wev_lane and its config-pair records, constants of the lane for the whole
     // kernel; w_k = [V_k^-, s_k] of the lane's config between the evaluation and the Newton matrix
     int wvl[4] = {0, 0, 0, 0}, wpair[4] = {0, 0, 0, 0};
@@ -517,7 +529,8 @@ struct Core {
     // Keeps global-memory look-ups (and their latency) out of the sweep.
     TG_HD void init_sweep_schedule(bool rollout = false) {
         PROG &P = tg_fresh(this->P);
-        TG_FOR(i, 4 * P.n_bodies) S[P.o_I + i] = P.b_inertia[i];   // body inertias: LDS copy for the whole kernel
+        if constexpr (PAR) { TG_FOR(i, 4 * P.n_bodies) S[P.o_I + i] = par[i - 4 * P.n_bodies]; }   // (the row's inertia block)
+        else TG_FOR(i, 4 * P.n_bodies) S[P.o_I + i] = P.b_inertia[i];   // body inertias: LDS copy for the whole kernel
         TG_FOR(c, P.nc) S[P.o_ctol + c] = P.c_tol[c];
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_BBD)
         if constexpr (TEAM == 64 && tg_static_bbd<typename std::remove_cv<PROG>::type>::value) {
@@ -564,7 +577,7 @@ struct Core {
             }
             const int b = lane < 6 * P.n_bodies ? lane / 6 : 0;
             bio[0] = P.b_item_off[b]; bio[1] = P.b_item_off[b + 1];
-            tdamp = P.damp[lane < P.nd ? lane : 0];
+            tdamp = damp_of(P, lane < P.nd ? lane : 0);
             if constexpr (tg_static_wev<typename std::remove_cv<PROG>::type>::value) {
                 typedef typename std::remove_cv<PROG>::type SP;
                 static_assert((SP::n_cmpairs + TEAM - 1) / TEAM <= 4, "eval_world: at most four trips of config pairs");
@@ -1216,7 +1229,7 @@ struct Core {
             if (lane < 3 * P.n_bodies) {
                 const int b = lane / 3, r = lane % 3;
                 const double *gb = S + P.o_gB + 12 * b;
-                S[P.o_gam + lane] = gb[r] * P.grav[0] + gb[4 + r] * P.grav[1] + gb[8 + r] * P.grav[2];
+                S[P.o_gam + lane] = gb[r] * grav_of(P, 0) + gb[4 + r] * grav_of(P, 1) + gb[8 + r] * grav_of(P, 2);
             }
         }
         TG_SYNC();
@@ -1568,7 +1581,7 @@ struct Core {
             const double *w = wev_w;
             const double lddq = sk[0] * h0 + sk[1] * h1 + sk[2] * h2 + sk[3] * h3 + sk[4] * h4 + sk[5] * h5;
             const double Gx = M * sk[0] + (sk[4] * Cz - sk[5] * Cy), Gy = M * sk[1] + (sk[5] * Cx - sk[3] * Cz), Gz = M * sk[2] + (sk[3] * Cy - sk[4] * Cx);
-            const double gx = P.grav[0], gy = P.grav[1], gz = P.grav[2];
+            const double gx = grav_of(P, 0), gy = grav_of(P, 1), gz = grav_of(P, 2);
             const double ldq = (w[0] * h0 + w[1] * h1 + w[2] * h2 + w[3] * h3 + w[4] * h4 + w[5] * h5) + (gx * Gx + gy * Gy + gz * Gz);
             const int i = lane;
             S[P.o_Ldq + i] = ldq; S[P.o_Lddq + i] = lddq;
@@ -1690,7 +1703,7 @@ struct Core {
         if (on) TG_FOR(idx, 3 * P.n_bodies) {
             const int b = idx / 3, r = idx % 3;
             const Real *gb = S + P.o_gB + 12 * b;
-            S[P.o_gam + idx] = gb[r] * P.grav[0] + gb[4 + r] * P.grav[1] + gb[8 + r] * P.grav[2];
+            S[P.o_gam + idx] = gb[r] * grav_of(P, 0) + gb[4 + r] * grav_of(P, 1) + gb[8 + r] * grav_of(P, 2);
         }
         TG_SYNC();
     }
@@ -1756,7 +1769,7 @@ struct Core {
             if (has_cs()) ldq -= cs_d1(i, qval(0, i));   // config springs (configspring.c:22-31, nonlinear_config_spring.c:24-34)
             if (n_springs()) ldq -= S[P.o_sV + i];
             S[P.o_Ldq + i] = ldq; S[P.o_Lddq + i] = lddq;
-            double force = -P.damp[i] * S[P.o_dq + i];
+            double force = -damp_of(P, i) * S[P.o_dq + i];
             for (int k = 0; k < P.n_cf; k++) if (P.cf_cfg[k] == i) force += S[P.o_u + P.cf_in[k]];
             if (n_wrenches()) force += S[P.o_wF + i];
             if (has_damper()) force += S[P.o_sF + i];
@@ -1971,7 +1984,7 @@ struct Core {
             Z[5] = Iw[5] + (b0 * h1 - b1 * h0) + (b3 * h4 - b4 * h3);
             // G = M v + w x C;  GG = G x g
             const double Gx = M * b0 + (b4 * Cz - b5 * Cy), Gy = M * b1 + (b5 * Cx - b3 * Cz), Gz = M * b2 + (b3 * Cy - b4 * Cx);
-            const double gx = P.grav[0], gy = P.grav[1], gz = P.grav[2];
+            const double gx = grav_of(P, 0), gy = grav_of(P, 1), gz = grav_of(P, 2);
             double *o = CZ + 15 * lane;
 #pragma unroll
             for (int r = 0; r < 6; r++) { o[r] = Is[r]; o[6 + r] = Z[r]; }
@@ -2059,7 +2072,7 @@ struct Core {
             Z[4] = Iw[4] + (b2 * h0 - b0 * h2) + (b5 * h3 - b3 * h5);
             Z[5] = Iw[5] + (b0 * h1 - b1 * h0) + (b3 * h4 - b4 * h3);
             const double Gx = M * b0 + (b4 * Cz - b5 * Cy), Gy = M * b1 + (b5 * Cx - b3 * Cz), Gz = M * b2 + (b3 * Cy - b4 * Cx);
-            const double gx = P.grav[0], gy = P.grav[1], gz = P.grav[2];
+            const double gx = grav_of(P, 0), gy = grav_of(P, 1), gz = grav_of(P, 2);
             double *o = CZ + 15 * lane;
 #pragma unroll
             for (int r = 0; r < 6; r++) { o[r] = Is[r]; o[6 + r] = Z[r]; }
@@ -2145,7 +2158,7 @@ struct Core {
         if (on) {
             TG_FOR(r, nf) {
                 A[r * ld + nf] = S[P.o_f + r];
-                if (r < nd) A[r * ld + r] = -P.damp[r] - (has_cs() ? 0.25 * dt * cs_d2(r, qval(0, r)) : 0.0);   // + dt/4 (-V_dqdq)
+                if (r < nd) A[r * ld + r] = -damp_of(P, r) - (has_cs() ? 0.25 * dt * cs_d2(r, qval(0, r)) : 0.0);   // + dt/4 (-V_dqdq)
             }
             TG_FOR(n, P.n_dh) {
                 const int c = P.dh_pack[8 * (size_t)n], k = P.dh_pack[8 * (size_t)n + 1];
@@ -3028,8 +3041,8 @@ struct Core {
         // constant blocks: forces (damping.c:21-27, configforce.c:27-33), -Dh1T, Dh2, unit p1 columns, k2 constraint rows
         if (on && w0) {
             TG_FOR(o, nd) {
-                AUG[o * ld + o] -= P.damp[o];              // D2D1L2_D2fm2: + dF_o/d(dq_o)
-                AUG[o * ld + c_q1 + o] -= P.damp[o];       // -(D1D1L2_D1fm2): -( - dF_o/d(dq_o) )
+                AUG[o * ld + o] -= damp_of(P, o);              // D2D1L2_D2fm2: + dF_o/d(dq_o)
+                AUG[o * ld + c_q1 + o] -= damp_of(P, o);       // -(D1D1L2_D1fm2): -( - dF_o/d(dq_o) )
                 AUG[o * ld + c_p1 + o] = -1.0;
                 if (has_cs()) {   // a = dt/4 (-V_dqdq) on the diagonal of all four second-order tables
                     const double a_ = -0.25 * dt * cs_d2(o, qval(0, o));
@@ -4609,7 +4622,7 @@ struct Core {
                 if (cfg < nd) lds_add(&rhs[cfg], term);
             }
             TG_FOR(i, nd) {
-                Real force = -P.damp[i] * S[P.o_dq + i];
+                Real force = -damp_of(P, i) * S[P.o_dq + i];
                 for (int k = 0; k < P.n_cf; k++) if (P.cf_cfg[k] == i) force += S[P.o_u + P.cf_in[k]];
                 if (has_cs()) force -= cs_d1(i, S[P.o_q2 + i]);
                 if (n_springs()) force -= S[P.o_sV + i];
@@ -4659,7 +4672,7 @@ struct Core {
             TG_FOR(b, P.n_bodies) {
                 const Real *I = S + P.o_I + 4 * b, *v = S + P.o_vB + 6 * b, *gb = S + P.o_gB + 12 * b;
                 lds_add(&acc[0], 0.5 * inner6(I, v, v));
-                lds_add(&acc[1], -I[0] * (P.grav[0] * gb[3] + P.grav[1] * gb[7] + P.grav[2] * gb[11]));
+                lds_add(&acc[1], -I[0] * (grav_of(P, 0) * gb[3] + grav_of(P, 1) * gb[7] + grav_of(P, 2) * gb[11]));
             }
             if (has_cs()) TG_FOR(i, P.nq) {
                 const Real q = S[P.o_q2 + i];
@@ -4931,7 +4944,7 @@ struct Core {
                 if (x != y) emit(y, x, false);
             }
             TG_FOR(i, nd) {
-                lds_add(&AUG[i * ld + c_dq + i], -P.damp[i]);
+                lds_add(&AUG[i * ld + c_dq + i], -damp_of(P, i));
                 for (int k = 0; k < P.n_cf; k++) if (P.cf_cfg[k] == i) lds_add(&AUG[i * ld + c_u + P.cf_in[k]], 1.0);
                 if (has_cs()) lds_add(&AUG[i * ld + c_q + i], -cs_d2(i, S[P.o_q2 + i]));
             }
@@ -5084,8 +5097,9 @@ TG_HD void run_forward(PROG &P, ARGS &A, Real *S, int lane, int traj) {
 // derivative modes are far larger than the rollout loop).
 // PIVOT: -1 the pivot rule is read from the arguments at run time (generic kernels); 0 / 1 compile the single-precision ranking /
 // the reference's exact rule in alone (specialised kernels: the variant not asked for is not in the kernel's call graph at all)
-template <int TEAM, int MODE, bool SPRINGS = false, class PROG = CProg, class ARGS = CArgs, int PIVOT = -1>
-TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int wave = 0, int nw = 1) {
+// PAR: masses / inertias, gravity and damping come from the trajectory's row of the parameter table T (ParTable) instead of the schedule
+template <int TEAM, int MODE, bool SPRINGS = false, class PROG = CProg, class ARGS = CArgs, int PIVOT = -1, bool PAR = false>
+TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int wave = 0, int nw = 1, const ParTable T = ParTable{nullptr, 1, 0}) {
     PROG &P = tg_fresh(P0);
     ARGS &A = A0;
     const int nq = P.nq, nd = P.nd, nk = P.nk, nu = P.nu, nc = P.nc;
@@ -5093,7 +5107,9 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
     const size_t t = (size_t)(live ? traj : 0);
     double dt = MODE == MODE_ROLLOUT ? A.dt : (A.t2 - A.t1);
     if (A.dt_steps && A.dt_period > 0) dt = A.dt_steps[t % (size_t)A.dt_period];   // per-trajectory step size (k-parallel linearisation)
-    Core<TEAM, SPRINGS, PROG> core(P, S, lane, dt);
+    Core<TEAM, SPRINGS, PROG, double, PAR> core(P, S, lane, dt);
+    if constexpr (PAR) core.par = T.rows + (t / (size_t)T.group) * (size_t)T.stride + 4 * P.n_bodies;
+    else (void)T;
     core.wave = wave; core.nw = nw;
     core.d1_compact = MODE == MODE_DERIV1 && P.a_ok != 0;
     if (wave == 0) core.init_sweep_schedule(MODE == MODE_ROLLOUT);

@@ -58,6 +58,26 @@ double *lds = tg_lds_base();
     tg::run_trajectory<SPEC_TEAM, MODE, SPEC_SPRINGS, const SpecProg, std::remove_reference<decltype(A)>::type, PIVOT>(P, A, lds + (size_t)team * stride, lane, traj, wave, spec_waves<MODE>());
 }
 
+// The same kernel with per-trajectory masses / inertias, gravity and damping (tg_batch_set_parameters, tg_spec_launch_par): the
+// trajectory's row of the parameter table T takes the place of the compiled-in values (mvi_core.hpp, ParTable).  Its twin's launch
+// bounds and LDS slice.
+template <int MODE, int PIVOT = 0>
+__global__ __launch_bounds__(64 * spec_waves<MODE>(), MODE == tg::MODE_DERIV1 ? (SpecProg::a_ok ? 2 : 1) : (MODE == tg::MODE_DERIV2Z ? TG_DERIV_WAVES : TG_ROLLOUT_WAVES)) void k_spec_par(SPEC_KERNEL_ARGS, const tg::ParTable T) {
+    SPEC_ARGS_REF;
+    double *lds = tg_lds_base();
+    const SpecProg P{};
+    int wave = 0, team = threadIdx.x / SPEC_TEAM, lane = threadIdx.x % SPEC_TEAM;
+    if constexpr (spec_waves<MODE>() > 1) {
+        wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        team = 0; lane = threadIdx.x & 63;
+    }
+    const int block = MODE == tg::MODE_ROLLOUT ? tg_xcd_block((int)blockIdx.x, (int)gridDim.x) : (int)blockIdx.x;
+    const int traj = tg::tg_remap_trajectory(A, block * (64 / SPEC_TEAM) + team);
+    constexpr int stride = MODE == tg::MODE_DERIV2Z ? SpecProg::e_lds_per_team : (MODE == tg::MODE_DERIV1 ? SpecProg::a_lds_per_team : SpecProg::lds_per_team);
+    tg::run_trajectory<SPEC_TEAM, MODE, SPEC_SPRINGS, const SpecProg, std::remove_reference<decltype(A)>::type, PIVOT, true>(P, A, lds + (size_t)team * stride, lane, traj, wave,
+                                                                                                                          spec_waves<MODE>(), T);
+}
+
 // Test hook: the Newton-system solve of this library's rollout kernel (default pivot rule) on caller-supplied matrices [nf][nf + 1],
 // one workgroup per matrix, in the rollout kernel's own LDS layout: the structured solve along the compiled-in plan if the system
 // has one (bbd.hpp), the pivoting solver if a pivot guard fails.  path: 1 structured, 2 pivoting solver, -1 singular.
@@ -120,6 +140,19 @@ int launch_mode(const tg::RunArgs *A, tg::RunArgs *slot, int grid, size_t lds, h
 #endif
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
+template <int MODE, int PIVOT = 0>
+int launch_mode_par(const tg::RunArgs *A, tg::RunArgs *slot, int grid, size_t lds, hipStream_t stream, const tg::ParTable &T) {
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_spec_par<MODE, PIVOT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return 1;
+#if defined(SPEC_ARGS_IN_MEMORY)
+    if (!slot) return 3;
+    if (hipMemcpyAsync(slot, A, sizeof(tg::RunArgs), hipMemcpyHostToDevice, stream) != hipSuccess) return 1;
+    hipLaunchKernelGGL((k_spec_par<MODE, PIVOT>), dim3(grid), dim3(64 * spec_waves<MODE>()), lds, stream, (const tg::RunArgs *)slot, T);
+#else
+    hipLaunchKernelGGL((k_spec_par<MODE, PIVOT>), dim3(grid), dim3(64 * spec_waves<MODE>()), lds, stream, *A, T);
+#endif
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
 }  // namespace
 
 extern "C" {
@@ -151,6 +184,8 @@ int tg_spec_modes(void) {
 #endif
     return m;
 }
+// bit m set: kernel mode m has a per-trajectory-parameter instantiation in this library (tg_spec_launch_par)
+int tg_spec_par_modes(void) { return tg_spec_modes(); }
 // (test hook) n_mats systems [nf][nf + 1] in, solutions [nf] and the path taken out; device pointers
 int tg_spec_debug_solve(const double *A_dev, double *x_dev, int *path_dev, int n_mats, int skip_structured) {
     const size_t lds = sizeof(double) * (size_t)SpecProg::lds_per_team;
@@ -176,6 +211,20 @@ int tg_spec_launch(int mode, const tg::RunArgs *A, tg::RunArgs *device_slot, int
 #if defined(SPEC_DERIVATIVES)
     case tg::MODE_DERIV1: return launch_mode<tg::MODE_DERIV1>(A, device_slot, grid, lds, (hipStream_t)stream);
     case tg::MODE_DERIV2Z: return launch_mode<tg::MODE_DERIV2Z>(A, device_slot, grid, lds, (hipStream_t)stream);
+#endif
+    default: return 2;
+    }
+}
+// tg_spec_launch with the per-trajectory parameter table (tg_batch_set_parameters): rows [.][stride] doubles, trajectory t uses row t / group
+int tg_spec_launch_par(int mode, const tg::RunArgs *A, tg::RunArgs *device_slot, int grid, size_t lds, void *stream, const double *rows, int group, int stride) {
+    const tg::ParTable T{rows, group, stride};
+    switch (mode) {
+    case tg::MODE_ROLLOUT:
+        return A->exact_pivot ? launch_mode_par<tg::MODE_ROLLOUT, 1>(A, device_slot, grid, lds, (hipStream_t)stream, T)
+                              : launch_mode_par<tg::MODE_ROLLOUT, 0>(A, device_slot, grid, lds, (hipStream_t)stream, T);
+#if defined(SPEC_DERIVATIVES)
+    case tg::MODE_DERIV1: return launch_mode_par<tg::MODE_DERIV1>(A, device_slot, grid, lds, (hipStream_t)stream, T);
+    case tg::MODE_DERIV2Z: return launch_mode_par<tg::MODE_DERIV2Z>(A, device_slot, grid, lds, (hipStream_t)stream, T);
 #endif
     default: return 2;
     }

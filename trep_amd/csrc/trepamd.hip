@@ -17,6 +17,12 @@
 #include "spec_emit.inc"
 #include <dlfcn.h>
 
+namespace tg_detail {
+int fail(int code, const std::string &msg);
+// the generic per-trajectory-parameter kernels (trepamd_par.hip: their own object, compiled beside this one)
+int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+}
+
 namespace {
 
 thread_local std::string g_error;
@@ -61,6 +67,7 @@ __global__ __launch_bounds__(64, 1) void k_forward(const tg::DevProg *__restrict
 struct tg_system {
     tg::HostProgram H;
     int team = 64;
+    bool has_gravity = false, has_damping = false;   // the system has a Gravity potential / a Damping force (parameter blocks it accepts)
 };
 
 struct tg_batch {
@@ -71,6 +78,16 @@ struct tg_batch {
     // optional system-specialised rollout kernel (tg_batch_load_specialized): launcher exported by a generated library
     void *spec_lib = nullptr;
     int (*spec_launch)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *) = nullptr;
+    // ... and its per-trajectory-parameter kernels (tg_spec_launch_par; null for a library without them)
+    int (*spec_launch_par)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *, const double *, int, int) = nullptr;
+    int spec_par_modes = 0;
+    // per-trajectory parameter table (tg_batch_set_parameters): par_rows rows of par_stride doubles (tg::ParTable layout) on the device;
+    // par_rows == 0: none set, the default kernels run
+    double *par_dev = nullptr;
+    size_t par_cap = 0;
+    int par_rows = 0, par_group = 1, par_stride = 0;
+    unsigned int par_spec_launched_modes = 0, par_generic_launched_modes = 0;   // bit m: a mode-m launch went through a parameter kernel of that kind
+    long long par_spec_launches = 0, par_generic_launches = 0;                   // (tg_batch_par_info; tg_batch_info counts the default kernels)
     // argument blocks of the specialised kernels: ARG_SLOTS device-side blocks fed from a pinned host ring (a truly asynchronous
     // hipMemcpyAsync; a slot is reused only after the launch that read it has finished: arg_done[i])
     static constexpr int ARG_SLOTS = 4;
@@ -183,6 +200,8 @@ int launch_variant(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
     return TG_SUCCESS;
 }
 
+bool launch_springs(const tg_batch *b) { return b->P.has_cs || b->P.n_springs || b->P.has_plane || b->P.n_wrenches; }
+
 // systems with spring potentials run their own instantiation of every kernel (mvi_core.hpp, Core<TEAM, SPRINGS>)
 template <int TEAM, int MODE>
 int launch_one(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
@@ -239,22 +258,29 @@ int launch(tg_batch *b, tg::RunArgs &A) {
         if (hipEventRecord(e0, b->stream) != hipSuccess) { b->pool.push_back(e0); b->pool.push_back(e1); return fail(TG_ERR_HIP, "hipEventRecord failed"); }
     }
     int rc;
-    if (b->spec_launch && ((b->spec_modes >> A.mode) & 1)) {
+    // a parameter table selects the PAR kernels: the library's specialised one of the mode if it has it, else the generic one
+    const bool par = b->par_rows > 0;
+    if (par ? (b->spec_launch_par && ((b->spec_par_modes >> A.mode) & 1)) : (b->spec_launch && ((b->spec_modes >> A.mode) & 1))) {
         const int i = b->arg_next;
         b->arg_next = (i + 1) % tg_batch::ARG_SLOTS;
         rc = TG_SUCCESS;
         if (b->arg_used[i] && hipEventSynchronize(b->arg_done[i]) != hipSuccess) rc = fail(TG_ERR_HIP, "hipEventSynchronize failed");
         if (rc == TG_SUCCESS) {
             b->h_args[i] = A;
-            rc = b->spec_launch(A.mode, &b->h_args[i], b->d_args + i, grid, lds, (void *)b->stream) == 0 ? TG_SUCCESS : fail(TG_ERR_HIP, "specialised kernel launch failed");
+            const int lrc = par ? b->spec_launch_par(A.mode, &b->h_args[i], b->d_args + i, grid, lds, (void *)b->stream, b->par_dev, b->par_group, b->par_stride)
+                                : b->spec_launch(A.mode, &b->h_args[i], b->d_args + i, grid, lds, (void *)b->stream);
+            rc = lrc == 0 ? TG_SUCCESS : fail(TG_ERR_HIP, "specialised kernel launch failed");
             b->arg_used[i] = hipEventRecord(b->arg_done[i], b->stream) == hipSuccess;
             if (!b->arg_used[i]) hipStreamSynchronize(b->stream);
-            b->spec_launched_modes |= 1u << A.mode; b->spec_launches++;
+            if (par) { b->par_spec_launched_modes |= 1u << A.mode; b->par_spec_launches++; }
+            else { b->spec_launched_modes |= 1u << A.mode; b->spec_launches++; }
         }
     } else {
-    b->generic_launched_modes |= 1u << A.mode; b->generic_launches++;
-    rc = team == 64 ? launch_team<64>(b, A, grid, lds) : (team == 16 ? launch_team<16>(b, A, grid, lds)
-             : (team == 4 ? launch_team<4>(b, A, grid, lds) : launch_team<1>(b, A, grid, lds)));
+        if (par) { b->par_generic_launched_modes |= 1u << A.mode; b->par_generic_launches++; }
+        else { b->generic_launched_modes |= 1u << A.mode; b->generic_launches++; }
+        rc = par ? tg_detail::launch_par(team, launch_springs(b), b->d_prog, A, tg::ParTable{b->par_dev, b->par_group, b->par_stride}, grid, lds, b->stream)
+                 : (team == 64 ? launch_team<64>(b, A, grid, lds) : (team == 16 ? launch_team<16>(b, A, grid, lds)
+                    : (team == 4 ? launch_team<4>(b, A, grid, lds) : launch_team<1>(b, A, grid, lds))));
     }
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
     if (b->timing) {
@@ -294,6 +320,7 @@ int launch_forward(tg_batch *b, const tg::RunArgs &A, int order) {
 #else
     typedef tgdual::Dual<double> D1;
     typedef tgdual::Dual<D1> D2;
+    if (b->par_rows) return fail(TG_ERR_UNSUPPORTED, "forward-mode kernels take the system's own parameters: clear the parameter table first");
     b->mirror_valid = false;
     if (A.mode == tg::MODE_DYN_DERIV1 && order == 1) return launch_forward_mode<tg::MODE_DYN_DERIV1, D1>(b, A);
     if (A.mode == tg::MODE_LAGRANGIAN && order == 1) return launch_forward_mode<tg::MODE_LAGRANGIAN, D1>(b, A);
@@ -456,6 +483,7 @@ tg_system *tg_system_create(const tg_system_desc *desc) {
         tg_system *s = new tg_system();
         s->H = tg::build_program(desc);
         s->team = pick_team(s->H);
+        s->has_gravity = desc->n_gravity > 0; s->has_damping = desc->n_damping > 0;
         return s;
     } catch (const std::exception &e) {
         fail(TG_ERR_INVALID, e.what());
@@ -529,7 +557,7 @@ void tg_batch_destroy(tg_batch *b) {
     if (b->stream) hipStreamSynchronize(b->stream);
     for (auto &e : b->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &e : b->pool) hipEventDestroy(e);
-    void *ptrs[] = {b->d_args, b->dt_dev, b->d_prog, b->d_ints, b->d_dbls, b->q1, b->q2, b->p1, b->p2, b->lam, b->u1, b->stage_u, b->stage_k,
+    void *ptrs[] = {b->d_args, b->dt_dev, b->par_dev, b->d_prog, b->d_ints, b->d_dbls, b->q1, b->q2, b->p1, b->p2, b->lam, b->u1, b->stage_u, b->stage_k,
                     b->stage_qh, b->stage_lh, b->f_out, b->iters, b->status, b->fallbacks, b->snap, b->z_dev, b->hz_dev, b->zl_dev, b->dyn, b->dyn_ints, b->seeds, b->dyn_d1, b->energy, b->lag,
                     b->d1[0], b->d1[1], b->d1[2], b->d1[3], b->d1[4], b->d1[5], b->d1[6], b->d1[7], b->d1[8], b->d1[9], b->d1[10], b->d1[11]};
     for (void *p : ptrs) if (p) hipFree(p);
@@ -1242,6 +1270,10 @@ int tg_batch_load_specialized(tg_batch *b, const char *library_path) {
     b->spec_lib = h; b->spec_launch = launch_fn; b->spec_modes = modes_fn(); b->spec_path = library_path;
     auto waves_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_waves"));
     b->spec_waves = waves_fn ? waves_fn() : 1;
+    auto par_fn = reinterpret_cast<int (*)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *, const double *, int, int)>(dlsym(h, "tg_spec_launch_par"));
+    auto par_modes_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_par_modes"));
+    b->spec_launch_par = par_modes_fn ? par_fn : nullptr;
+    b->spec_par_modes = (par_fn && par_modes_fn) ? par_modes_fn() : 0;
     return TG_SUCCESS;
 }
 
@@ -1298,6 +1330,78 @@ int tg_batch_info(const tg_batch *b, int32_t out[8]) {
     out[1] = (int32_t)b->spec_launched_modes; out[2] = (int32_t)b->generic_launched_modes;
     out[3] = (int32_t)std::min<long long>(b->spec_launches, 0x7fffffff); out[4] = (int32_t)std::min<long long>(b->generic_launches, 0x7fffffff);
     out[5] = b->exact_pivot; out[6] = b->sys->team; out[7] = b->spec_launch ? b->spec_waves : 1;
+    return TG_SUCCESS;
+}
+
+/* The parameter kernels of this batch (tg_batch_set_parameters): out[0] bit m = mode m has a specialised parameter kernel loaded;
+ * out[1] / out[2] bit m = a mode-m launch has gone through a specialised / a generic parameter kernel; out[3] / out[4] the number of
+ * such launches; out[5] rows of the current table (0: none set); out[6] its group; out[7] 0. */
+int tg_batch_par_info(const tg_batch *b, int32_t out[8]) {
+    if (!b || !out) return fail(TG_ERR_INVALID, "null argument");
+    out[0] = b->spec_launch_par ? b->spec_par_modes : 0;
+    out[1] = (int32_t)b->par_spec_launched_modes; out[2] = (int32_t)b->par_generic_launched_modes;
+    out[3] = (int32_t)std::min<long long>(b->par_spec_launches, 0x7fffffff); out[4] = (int32_t)std::min<long long>(b->par_generic_launches, 0x7fffffff);
+    out[5] = b->par_rows; out[6] = b->par_rows ? b->par_group : 0; out[7] = 0;
+    return TG_SUCCESS;
+}
+
+/* Base values of the per-trajectory parameters (tg_batch_set_parameters): sizes_out = n_bodies, nd, has_gravity, has_damping;
+ * inertia [n_bodies][4] (mass, Ixx, Iyy, Izz of every massive frame in System.masses order: reference frame.py set_mass), gravity [3]
+ * (the sum over the Gravity potentials: potentials/gravity.py), damping [nd] (the summed coefficient of every dynamic config:
+ * forces/damping.py).  Null outputs are skipped. */
+int tg_system_parameters(const tg_system *sys, int32_t sizes_out[4], double *inertia, double *gravity, double *damping) {
+    if (!sys) return fail(TG_ERR_INVALID, "null system");
+    const tg::HostProgram &H = sys->H;
+    if (sizes_out) { sizes_out[0] = H.p.n_bodies; sizes_out[1] = H.p.nd; sizes_out[2] = sys->has_gravity; sizes_out[3] = sys->has_damping; }
+    if (inertia) std::memcpy(inertia, H.b_inertia.data(), H.b_inertia.size() * sizeof(double));
+    if (gravity) for (int k = 0; k < 3; k++) gravity[k] = H.p.grav[k];
+    if (damping) for (int i = 0; i < H.p.nd; i++) damping[i] = H.damp.empty() ? 0.0 : H.damp[i];
+    return TG_SUCCESS;
+}
+
+/* Per-trajectory parameters: `rows` rows of inertia [n_bodies][4], gravity [3] and damping [nd] (host arrays, row-major; null: the
+ * system's own values in every row); trajectory t uses row t / group (t after any subset remapping).  rows * group == batch, or rows
+ * == 1 for the whole batch.  Refused (TG_ERR_INVALID, nothing changed) for bad shapes, non-finite values, or a gravity / damping block
+ * of a system without a Gravity potential / Damping force.  The reference's own parameter writes are Frame.set_mass (frame.py),
+ * Gravity.gravity (potentials/gravity.py) and Damping.set_damping_coefficient (forces/damping.py): a row acts as a system rebuilt with
+ * them; the structure (which frames are massive) never changes.  Ordered on the batch's stream: launches already enqueued keep the
+ * table they were launched with, later ones see the new one. */
+int tg_batch_set_parameters(tg_batch *b, int32_t rows, int32_t group, const double *inertia_host, const double *gravity_host,
+                            const double *damping_host) {
+    if (!b) return fail(TG_ERR_INVALID, "null batch");
+    if (rows <= 0 || group <= 0) return fail(TG_ERR_INVALID, "rows and group must be positive");
+    if (rows != 1 && (int64_t)rows * group != b->batch) return fail(TG_ERR_INVALID, "rows * group must equal the batch size (or rows == 1)");
+    if (gravity_host && !b->sys->has_gravity) return fail(TG_ERR_INVALID, "the system has no Gravity potential: no gravity block");
+    if (damping_host && !b->sys->has_damping) return fail(TG_ERR_INVALID, "the system has no Damping force: no damping block");
+    const tg::HostProgram &H = b->sys->H;
+    const int nb = H.p.n_bodies, nd = H.p.nd, stride = 4 * nb + 3 + nd;
+    std::vector<double> tab((size_t)rows * stride);
+    for (int r = 0; r < rows; r++) {
+        double *row = tab.data() + (size_t)r * stride;
+        for (int i = 0; i < 4 * nb; i++) row[i] = inertia_host ? inertia_host[(size_t)r * 4 * nb + i] : H.b_inertia[i];
+        for (int k = 0; k < 3; k++) row[4 * nb + k] = gravity_host ? gravity_host[3 * (size_t)r + k] : H.p.grav[k];
+        for (int i = 0; i < nd; i++) row[4 * nb + 3 + i] = damping_host ? damping_host[(size_t)r * nd + i] : (H.damp.empty() ? 0.0 : H.damp[i]);
+    }
+    for (double v : tab) if (!std::isfinite(v)) return fail(TG_ERR_INVALID, "parameter values must be finite");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));          // a launch in flight keeps reading the old table until it has finished
+    if (tab.size() > b->par_cap) {
+        if (b->par_dev) { HIP_TRY(hipFree(b->par_dev)); b->par_dev = nullptr; b->par_cap = 0; b->par_rows = 0; }
+        HIP_TRY(hipMalloc(&b->par_dev, tab.size() * sizeof(double)));
+        b->par_cap = tab.size();
+    }
+    HIP_TRY(hipMemcpyAsync(b->par_dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->par_rows = rows; b->par_group = rows == 1 ? b->batch : group; b->par_stride = stride;
+    b->mirror_valid = false;
+    return TG_SUCCESS;
+}
+
+/* Back to the system's own parameters: the default kernels run again. */
+int tg_batch_clear_parameters(tg_batch *b) {
+    if (!b) return fail(TG_ERR_INVALID, "null batch");
+    b->par_rows = 0;
+    b->mirror_valid = false;
     return TG_SUCCESS;
 }
 

@@ -399,6 +399,14 @@ class BatchDSystem(_Packing):
         X[:, self._slice_v] = (q2 - q1)[:, self._np:] / (t2 - t1)
         return X
 
+    def set_parameters(self, inertia=None, gravity=None, damping=None, group=1):
+        """Per-trajectory masses / inertias, gravity and damping of the batch (BatchMidpointVI.set_parameters): set(), f(),
+        linearize() and second_order() then use trajectory b's row."""
+        self.varint.set_parameters(inertia=inertia, gravity=gravity, damping=damping, group=group)
+
+    def clear_parameters(self):
+        self.varint.clear_parameters()
+
     def linearize(self):
         """A [B][nX][nX], B [B][nX][nU] at the current step (one deriv1 launch for the batch)."""
         v = self.varint

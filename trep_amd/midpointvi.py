@@ -69,7 +69,8 @@ class BatchMidpointVI(object):
         integrator keeps its state across them (trep/potentials/gravity.py, trep/midpointvi.py:25-136 only
         re-allocates on *structure* changes); here every change re-builds the few-kB device schedule, and the batch
         state (times, q1, q2, p1, p2, u1, lambda1, tolerance, predictor) is carried over whenever the sizes are
-        unchanged.  Returns True if a rebuild happened."""
+        unchanged.  A per-trajectory parameter table (set_parameters) is dropped by a rebuild: its sizes and base values
+        belong to the old schedule.  Returns True if a rebuild happened."""
         if self._structure_version == self._system._structure_version:
             return False
         old_sizes = (self.nq, self.nd, self.nk, self.nu, self.nc)
@@ -89,6 +90,7 @@ class BatchMidpointVI(object):
         self._L.tg_batch_destroy(self._h)
         self._L.tg_system_destroy(self._sys_h)
         self._desc, self._sys_h, self._h = desc, sys_h, h
+        self._parameter_rows = 0
         self._structure_version = self._system._structure_version
         self._specialized = None
         if self._specialize_mode is True or (self._specialize_mode == "auto" and os.environ.get("TREPAMD_NO_SPECIALIZE") is None):
@@ -176,19 +178,68 @@ class BatchMidpointVI(object):
         return dict(zip(keys, (int(v) for v in out)))
 
     MODES = {"rollout": 0, "calc_p2": 1, "calc_f": 2, "deriv1": 3, "deriv2z": 4}
+    ALL_MODES = dict(MODES, dynamics=5, dynamics_deriv1=6, energy=7, lagrangian=8)
+
+    # -- per-trajectory parameters ------------------------------------------------------
+    def parameters(self):
+        """The system's own parameter values as the device schedule holds them (tg_system_parameters): dict with inertia
+        [n_bodies][4] (mass, Ixx, Iyy, Izz of system.masses), gravity [3] (None without a Gravity potential) and damping [nd]
+        (None without a Damping force)."""
+        sizes = np.zeros(4, dtype=np.int32)
+        _lib.check(self._L.tg_system_parameters(self._sys_h, sizes.ctypes.data, None, None, None))
+        inertia = np.zeros((int(sizes[0]), 4))
+        gravity, damping = np.zeros(3), np.zeros(int(sizes[1]))
+        _lib.check(self._L.tg_system_parameters(self._sys_h, None, inertia.ctypes.data if inertia.size else None, gravity.ctypes.data,
+                                                damping.ctypes.data if damping.size else None))
+        return {"inertia": inertia, "gravity": gravity if sizes[2] else None, "damping": damping if sizes[3] else None}
+
+    def set_parameters(self, inertia=None, gravity=None, damping=None, group=1):
+        """Per-trajectory masses / inertias, gravity and damping (trep_amd/parameters.py has the shapes): trajectory t uses row
+        t // group of each block, a block of one row applies to every trajectory, an omitted block keeps the system's values.
+        Every later launch -- rollouts, step, calc_p2 / calc_f, deriv1 / linearize, deriv2z, the continuous dynamics, energy and
+        Lagrangian -- runs with the table, through the parameter kernels (kernel_info: par_spec_launched / par_generic_launched);
+        the forward-mode entry points (*_forward) raise LibraryError while it is set.  Raises ValueError (nothing changed) for
+        bad shapes or values.  The schedule is not rebuilt and a loaded specialised library stays in use.  Set the table before
+        initialize_from_configs: the initial momenta (calc_p2) depend on the masses."""
+        self.refresh()
+        from . import parameters as _par
+        rows, group, blocks = _par.pack(self._system, self._batch, inertia=inertia, gravity=gravity, damping=damping, group=group)
+        p = lambda name: None if blocks[name] is None or blocks[name].size == 0 else blocks[name].ctypes.data
+        rc = self._L.tg_batch_set_parameters(self._h, rows, group, p("inertia"), p("gravity"), p("damping"))
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        self._parameter_rows = rows
+
+    def clear_parameters(self):
+        """Back to the system's own parameters (and the default kernels)."""
+        _lib.check(self._L.tg_batch_clear_parameters(self._h))
+        self._parameter_rows = 0
+
+    @property
+    def has_parameters(self):
+        return getattr(self, "_parameter_rows", 0) > 0
 
     def kernel_info(self):
         """Which kernels this batch has launched (tg_batch_info): `spec_modes` = set of mode names with a specialised kernel
         loaded, `spec_launched` / `generic_launched` = mode names that have actually gone through a specialised / generic
         kernel, and the launch counts; `helper_waves` = wavefronts per trajectory in the loaded library's derivative kernels;
-        `spec_library` the loaded file."""
+        `spec_library` the loaded file.  The par_* keys: the same for the per-trajectory parameter kernels (set_parameters),
+        over all kernel modes (ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
         out = np.zeros(8, dtype=np.int32)
         _lib.check(self._L.tg_batch_info(self._h, out.ctypes.data_as(_lib._c_ip)))
         names = lambda bits: sorted(n for n, m in self.MODES.items() if (int(bits) >> m) & 1)
+        par = np.zeros(8, dtype=np.int32)
+        _lib.check(self._L.tg_batch_par_info(self._h, par.ctypes.data_as(_lib._c_ip)))
+        every = lambda bits: sorted(n for n, m in self.ALL_MODES.items() if (int(bits) >> m) & 1)
         return {"spec_modes": names(out[0]), "spec_launched": names(out[1]), "generic_launched": names(out[2]),
                 "spec_launch_mask": int(out[1]), "generic_launch_mask": int(out[2]),
                 "spec_launches": int(out[3]), "generic_launches": int(out[4]), "exact_pivot": bool(out[5]), "team": int(out[6]),
-                "helper_waves": int(out[7]), "spec_library": self._specialized}
+                "helper_waves": int(out[7]), "spec_library": self._specialized,
+                # per-trajectory parameter kernels (set_parameters); the keys above count the default kernels only
+                "par_spec_modes": every(par[0]), "par_spec_launched": every(par[1]), "par_generic_launched": every(par[2]),
+                "par_spec_launches": int(par[3]), "par_generic_launches": int(par[4]), "parameter_rows": int(par[5]),
+                "parameter_group": int(par[6])}
 
     @property
     def stream(self):
