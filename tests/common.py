@@ -67,3 +67,26 @@ def relerr(a, b):
     if a.size == 0:
         return 0.0
     return float(np.abs(a - b).max() / max(1.0, np.abs(b).max()))
+
+# (seeds, horizon, k_begin, k_end) of the remapped deriv2z launches (tg_batch_deriv2_contract_device_range) that the team-size
+# tests run: batch = seeds * horizon, launch slots = seeds * (k_end - k_begin), a multiple of no team count per block (64/team > 1)
+RANGE_CASES = [(3, 7, 2, 5), (5, 6, 1, 6), (2, 13, 0, 9)]
+
+# Generic-kernel cells of the team-size tests (TREPAMD_TEAM forces the team): system -> {team: LDS slice kinds whose block,
+# (64 / team) x slice x 8 B, is over the 160 KiB a workgroup may have -- the launches the library must refuse}.  The slice kind of
+# calc_p2, calc_f, dynamics, energy and lagrangian is the rollout's.
+LDS_SLICES = ("rollout", "deriv1", "deriv2z", "dynamics_deriv1")
+_ALL = set(LDS_SLICES)
+TEAM_CELLS = {
+    "pendulum1": {1: set(), 4: set(), 16: set(), 64: set()},
+    "pend_on_cart": {1: set(), 4: set(), 16: set(), 64: set()},
+    "dual_pendulums": {1: set(), 4: set(), 16: set(), 64: set()},
+    "damper_link": {1: {"deriv2z", "dynamics_deriv1"}, 4: set(), 16: set(), 64: set()},
+    "spring_link": {1: _ALL, 4: set(), 16: set(), 64: set()},
+    "plane_link": {1: {"deriv1", "deriv2z", "dynamics_deriv1"}, 4: set(), 16: set(), 64: set()},
+    "pendulum5": {1: _ALL, 4: set(), 16: set(), 64: set()},
+    "wrench_arm": {1: _ALL, 4: set(), 16: set(), 64: set()},
+    "spring_arm": {1: {"deriv1", "deriv2z", "dynamics_deriv1"}, 4: set(), 16: set(), 64: set()},
+    "scissor4": {1: _ALL, 4: {"deriv1", "deriv2z", "dynamics_deriv1"}, 16: set(), 64: set()},
+    "puppet_basic": {16: {"deriv2z"}, 64: set()},
+}

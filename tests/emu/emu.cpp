@@ -51,6 +51,12 @@ void emu_destroy(void *h) { delete (Emu *)h; }
 
 int emu_lds_doubles(void *h) { return ((Emu *)h)->P.lds_per_team; }
 
+// The per-trajectory LDS slices (doubles) of the generic kernels: rollout-type modes, deriv1, deriv2z, dynamics_deriv1.
+void emu_lds_slices(void *h, int *out) {
+    const tg::DevProg &P = ((Emu *)h)->P;
+    out[0] = P.lds_per_team; out[1] = P.a_lds_per_team; out[2] = P.e_lds_per_team; out[3] = P.g_lds_per_team;
+}
+
 // Runs every trajectory of the batch through the kernel body, one after the other.
 void emu_run(void *h, const tg::RunArgs *args) {
     Emu *e = (Emu *)h;
@@ -75,4 +81,9 @@ void emu_run_forward(void *h, const tg::RunArgs *args, int order) {
     if (order == 2) emu_forward<tgdual::Dual<tgdual::Dual<double>>>((Emu *)h, args);
     else emu_forward<tgdual::Dual<double>>((Emu *)h, args);
 }
+
+// The launch-geometry arithmetic of the kernels (mvi_core.hpp): workgroup order of the rollout grid and the subset remapping.
+int emu_xcd_block(int b, int G) { return tg_xcd_block(b, G); }
+
+int emu_remap_trajectory(const tg::RunArgs *args, int i) { return tg::tg_remap_trajectory(*args, i); }
 }

@@ -45,8 +45,36 @@ def lib():
         L.emu_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.emu_run_forward.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         L.emu_lds_doubles.argtypes = [ctypes.c_void_p]
+        L.emu_lds_slices.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.emu_xcd_block.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.emu_remap_trajectory.argtypes = [ctypes.c_void_p, ctypes.c_int]
         _LIB = L
     return _LIB
+
+
+def lds_slices(desc):
+    """Per-trajectory LDS slices in doubles of the generic kernels: {"rollout", "deriv1", "deriv2z", "dynamics_deriv1"} (the rollout's
+    slice is also that of calc_p2, calc_f, dynamics, energy and lagrangian)."""
+    L = lib()
+    h = L.emu_create(ctypes.addressof(desc.struct))
+    assert h
+    out = np.zeros(4, dtype=np.int32)
+    L.emu_lds_slices(h, out.ctypes.data)
+    L.emu_destroy(h)
+    return dict(zip(("rollout", "deriv1", "deriv2z", "dynamics_deriv1"), (int(v) for v in out)))
+
+
+def xcd_block(b, G):
+    """tg_xcd_block: the block a workgroup of a G-workgroup rollout grid works on."""
+    return lib().emu_xcd_block(int(b), int(G))
+
+
+def remap_trajectory(batch, remap_len=0, remap_stride=0, remap_off=0, remap_count=0, slots=None):
+    """tg_remap_trajectory for launch slots 0 .. slots-1 (default: remap_count, or batch without remapping)."""
+    a = RunArgs()
+    a.batch, a.remap_len, a.remap_stride, a.remap_off, a.remap_count = batch, remap_len, remap_stride, remap_off, remap_count
+    n = slots if slots is not None else (remap_count if remap_len > 0 else batch)
+    return [lib().emu_remap_trajectory(ctypes.byref(a), i) for i in range(n)]
 
 
 def _p(a):
