@@ -463,6 +463,17 @@ typedef struct tg_lq_problem {
                                            * projection sweep, the second derivatives and the Newton-model sweep chunk by chunk in three stream lanes */
 } tg_lq_problem;
 int tg_tv_lq(int32_t device, const tg_lq_problem *problem);
+/* Which kernel tg_tv_lq would launch for this problem, decided on the host alone (no device is touched; the same environment
+ * switches are read): out[0] kernel (0 = the VALU kernel k_tv_lq, 1 = the matrix-core kernel k_tv_lq_mfma, 2 = the DSystem-structured
+ * kernel k_tv_lq_ds), out[1] size class (tile size TS of the VALU kernel: 2, 4, 5, 6; else NT = 16 x 16 tiles per dimension: 1, 2, 3,
+ * 5, 6), out[2] NR (rows of the input solve in registers: 4, 8, 20, 32; 0 for the VALU kernel), out[3] threads per workgroup,
+ * out[4] dynamic LDS bytes, out[5] 0.  Returns what tg_tv_lq would return before launching (TG_ERR_INVALID, TG_ERR_UNSUPPORTED;
+ * `out` is then meaningless); tg_tv_lq launches what this reports.  The structured kernel loads A_k, B_k sixteen bytes at a
+ * time, and it never computes the v columns of the gains: a structured problem whose A_dev or B_dev is not 16-byte aligned, or whose
+ * curvature block reaches into the v rows (hz_nx > 2 ds_nd + ds_nk), takes the dense kernel.  An affine sweep that continues
+ * from Pt_dev needs bt_dev, and Pt_dev is refused for a sweep that starts at the horizon's end (k_end = 0 or horizon), which
+ * starts from Qf and q_N. */
+int tg_tv_lq_plan(const tg_lq_problem *problem, int32_t out[6]);
 
 /* Backward adjoint of the Newton model (doptimizer.py:319-345): Z[s][k] = z_{k+1}, the vector the second
  * derivatives of step k are contracted with; z_k = q_k - K_k' r_k + (A_k - B_k K_k)' z_{k+1}, z_N = q_N. */
@@ -475,6 +486,11 @@ int tg_tangent_rollout(int32_t device, int32_t n_problems, int32_t horizon, int3
                        const int32_t *select_dev, const double *A_dev, const double *B_dev, const double *K_dev,
                        const double *C_dev, const double *q_dev, const double *r_dev, double *dX_dev, double *dU_dev,
                        double *dcost_dev);
+/* Which kernel tg_tangent_rollout would launch (host only; the pointers are looked at for their alignment, never dereferenced):
+ * out[0] kernel (0 = the LDS-staged k_tangent, 1 = k_tangent_rows with the rows in registers), out[1..3] the register class
+ * CA, CB, CK (0 for k_tangent), out[4] 1 = pairs of columns per thread with 16-byte loads (even sizes and 16-byte aligned A, B,
+ * K), out[5] threads per workgroup.  Returns TG_SUCCESS or what tg_tangent_rollout would refuse the sizes with. */
+int tg_tangent_rollout_plan(int32_t nX, int32_t nU, const void *A_dev, const void *B_dev, const void *K_dev, int32_t out[6]);
 /* DCost (trep/discopt/dcost.py:5-118): cost[t] = sum_k 1/2 (x-xd)'Q(x-xd) + 1/2 (u-ud)'R(u-ud) + terminal
  * with Qf, for n_trajectories trajectories of which `group` consecutive ones share the reference of one seed:
  * trajectory t is compared with Xd/Ud of seed select_dev[t/group] (or t/group if select_dev is NULL). */

@@ -8,57 +8,9 @@ import numpy as np
 import pytest
 
 from common import golden, relerr
+from common import device_pool as _pool, random_lq_problem as _random_problem, host_lq as _host_lq, dsystem_structure as _dsystem_structure
 
 pytestmark = pytest.mark.gpu
-
-
-def _pool():
-    from trep_amd.discopt.batch_doptimizer import _DevicePool
-    return _DevicePool(0)
-
-
-def _random_problem(rng, S, N, nX, nU, nxh):
-    A = 0.2 * rng.standard_normal((S, N, nX, nX)) / np.sqrt(nX) + 0.9 * np.eye(nX)
-    B = rng.standard_normal((S, N, nX, nU)) / np.sqrt(nX)
-    Q = rng.standard_normal((nX, nX)); Q = Q.dot(Q.T) / nX + np.eye(nX)
-    Qf = 2.0 * Q
-    R = rng.standard_normal((nU, nU)); R = R.dot(R.T) / nU + np.eye(nU)
-    q = rng.standard_normal((S, N + 1, nX))
-    r = rng.standard_normal((S, N, nU))
-    Rz = nxh + nU
-    hz = 0.05 * rng.standard_normal((S, N, Rz, Rz))
-    hz = hz + np.swapaxes(hz, 2, 3)
-    return A, B, Q, Qf, R, q, r, hz
-
-
-def _host_lq(A, B, Q, Qf, R, q, r, hz, nxh):
-    """numpy reference: dlqr.solve_tv_lq with the Newton-model weights assembled like DSystem._split_hz."""
-    from trep_amd.discopt import dlqr
-    N, nX, nU = A.shape[0], A.shape[1], B.shape[2]
-
-    def Qk(k):
-        if k == N:
-            return Qf
-        M = Q.copy()
-        if hz is not None:
-            M[:nxh, :nxh] += hz[k][:nxh, :nxh]
-        return M
-
-    def Sk(k):
-        M = np.zeros((nX, nU))
-        if hz is not None:
-            M[:nxh, :] = hz[k][:nxh, nxh:]
-        return M
-
-    def Rk(k):
-        return R + (hz[k][nxh:, nxh:] if hz is not None else 0.0)
-
-    if q is None:
-        assert hz is None
-        K, P = dlqr.solve_tv_lqr(A, B, Qk, Rk)
-        return np.array(K), None, P, None
-    K, C, P, b = dlqr.solve_tv_lq(A, B, q, r, Qk, Sk, Rk)
-    return np.array(K), np.array(C), P, b
 
 
 @pytest.mark.parametrize("nX,nU,nxh,N,S", [(4, 1, 4, 40, 3), (18, 3, 12, 25, 2), (80, 18, 62, 30, 3), (90, 10, 70, 8, 1)])
@@ -103,20 +55,6 @@ def test_tv_lq_matches_numpy(nX, nU, nxh, N, S):
                     assert relerr(C[s], Ch) < 1e-9 and relerr(b0[s], bh) < 1e-9, (mode, s)
     finally:
         pool.close()
-
-
-def _dsystem_structure(rng, A, B, nd, nk, nu, dt=0.01):
-    """Impose the block structure of DSystem.fdx / fdu (dsystem.py:284-317) on random A, B: states [Qd | Qk | p | v], inputs [u | rho]."""
-    nq, nX = nd + nk, 2 * (nd + nk)
-    Qd, Qk, p, v = slice(0, nd), slice(nd, nq), slice(nq, nq + nd), slice(nq + nd, nX)
-    A[..., Qk, :] = 0.0; A[..., v, :] = 0.0; A[..., :, v] = 0.0
-    B[..., Qk, :] = 0.0; B[..., v, :] = 0.0
-    for m in range(nk):
-        steps = dt * (1.0 + 0.3 * rng.random(A.shape[:-2]))       # any time base: the entries are read, not assumed
-        A[..., nq + nd + m, nd + m] = -1.0 / steps
-        B[..., nd + m, nu + m] = 1.0
-        B[..., nq + nd + m, nu + m] = 1.0 / steps
-    return A, B
 
 
 @pytest.mark.parametrize("nd,nk,nu,N,S", [(22, 18, 0, 30, 3), (9, 4, 2, 25, 2), (3, 5, 1, 20, 2), (30, 10, 0, 12, 1), (5, 0, 3, 20, 2)])

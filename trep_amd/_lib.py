@@ -116,6 +116,8 @@ _SIGNATURES = {
     "tg_batch_deriv2_contract_device": (ctypes.c_int, [_vp, _vp, _vp]),
     "tg_batch_deriv2_contract_device_range": (ctypes.c_int, [_vp, _vp, _vp, _i32, _i32, _i32]),
     "tg_tv_lq": (ctypes.c_int, [_i32, ctypes.POINTER(LqProblem)]),
+    "tg_tv_lq_plan": (ctypes.c_int, [ctypes.POINTER(LqProblem), _c_ip]),
+    "tg_tangent_rollout_plan": (ctypes.c_int, [_i32, _i32, _vp, _vp, _vp, _c_ip]),
     "tg_adjoint_sweep": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tg_tangent_rollout": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tg_quadratic_cost": (ctypes.c_int, [_i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -2071,24 +2071,26 @@ hipStream_t dopt_lane_stream(int device, int lane) {
     return st;
 }
 hipStream_t dopt_stream(int device) { return dopt_lane_stream(device, g_lane); }
-}  // namespace
 
-extern "C" {
-
-int tg_tv_lq(int32_t device, const tg_lq_problem *p) {
+// Which kernel a call launches, decided on the host alone (no device is touched): tg_tv_lq / tg_tangent_rollout launch what these
+// report, tg_tv_lq_plan / tg_tangent_rollout_plan export the same decision.
+struct LqPlan { int kernel = -1, cls = 0, nr = 0, threads = 0; size_t lds = 0; };    // kernel: 0 k_tv_lq (cls = TS), 1 k_tv_lq_mfma, 2 k_tv_lq_ds (cls = NT)
+int lq_plan(const tg_lq_problem *p, LqPlan &pl) {
     if (!p || p->n_problems <= 0 || p->horizon <= 0 || p->nX <= 0 || p->nU <= 0) return fail(TG_ERR_INVALID, "bad LQ problem sizes");
     if (!p->A_dev || !p->B_dev || !p->Q_dev || !p->Qf_dev || !p->R_dev || !p->K_dev) return fail(TG_ERR_INVALID, "null LQ buffer");
     if ((p->q_dev == nullptr) != (p->r_dev == nullptr)) return fail(TG_ERR_INVALID, "q and r must be given together");
-    if (p->hz_dev && (p->hz_R < p->hz_nx + p->nU || p->hz_nx > p->nX)) return fail(TG_ERR_INVALID, "bad curvature block sizes");
+    if (p->hz_dev && (p->hz_nx < 0 || p->hz_R < p->hz_nx + p->nU || p->hz_nx > p->nX)) return fail(TG_ERR_INVALID, "bad curvature block sizes");
     if (p->nU > 64) return fail(TG_ERR_UNSUPPORTED, "more than 64 inputs");
     if (p->k_begin < 0 || p->k_end < 0 || p->k_end > p->horizon || (p->k_end > 0 && p->k_begin >= p->k_end) || (p->k_end == 0 && p->k_begin != 0))
         return fail(TG_ERR_INVALID, "bad step range of the sweep");
     if (p->k_end > 0 && p->k_end < p->horizon && !p->Pt_dev) return fail(TG_ERR_INVALID, "a sweep that ends before the horizon needs the terminal (P, b) of the steps behind it");
+    // (P, b) travel as a pair: without b the kernels would start the vector recursion from different leftovers; and a sweep that starts at the
+    // horizon's end starts from Qf, q_N -- a terminal there would silently replace them
+    if (p->Pt_dev && p->q_dev && !p->bt_dev) return fail(TG_ERR_INVALID, "an affine sweep that continues from a terminal P needs the terminal b as well");
+    if (p->Pt_dev && (p->k_end == 0 || p->k_end == p->horizon)) return fail(TG_ERR_INVALID, "a sweep that starts at the horizon's end starts from Qf: no terminal (P, b)");
     if (p->ds_nd < 0 || p->ds_nk < 0 || p->ds_nu < 0 || (p->ds_nd > 0 && (2 * (p->ds_nd + p->ds_nk) != p->nX || p->ds_nu + p->ds_nk != p->nU)))
         return fail(TG_ERR_INVALID, "DSystem block structure does not match nX / nU");
-    // size class: tile size TS with nX <= 16*TS (one tile per thread), prefetch registers RI*CI >= nX*ceil(nX/32)/8
     const int nX = p->nX, nXU = p->nX * p->nU;
-    HIP_TRY(hipSetDevice(device));
     // matrix-core sweep (k_tv_lq_mfma) whenever it fits: nX <= 96, nU <= 32, LDS; TREPAMD_LQ_LEGACY=1 keeps the VALU kernel
     {
         const LqLayout L(p->nX, p->nU);
@@ -2098,78 +2100,144 @@ int tg_tv_lq(int32_t device, const tg_lq_problem *p) {
             // instantiated size classes: nX <= 16, 32, 48, 80, 96 (tiles per dimension 1, 2, 3, 5, 6) x nU <= 4, 8, 20, 32
             const int nt = nX <= 16 ? 1 : (nX <= 32 ? 2 : (nX <= 48 ? 3 : (nX <= 80 ? 5 : 6)));
             const int nr = p->nU <= 4 ? 4 : (p->nU <= 8 ? 8 : (p->nU <= 20 ? 20 : 32));
-            // DSystem block structure: its own kernel (k_tv_lq_ds) when the padding of the dense-row blocks can be taken from the sparse rows
+            // DSystem block structure: its own kernel (k_tv_lq_ds) when the padding of the dense-row blocks can be taken from the sparse rows.
+            // It fills LDS with 16-byte global_load_lds from A_k, B_k (rows start at even offsets: nX is even), so both must sit on 16-byte
+            // boundaries; anything else takes the dense kernel, whose loads are 8 bytes wide
             const char *dense_env = std::getenv("TREPAMD_LQ_DENSE");
-            if (p->ds_nd > 0 && !(dense_env && dense_env[0] == '1') && p->ds_nk >= round_up(p->ds_nd, 4) - p->ds_nd && p->ds_nk <= 31 && (nX % 2) == 0) {
+            const bool aligned = (((uintptr_t)p->A_dev | (uintptr_t)p->B_dev) & 15) == 0;
+            // ... and it never computes the v columns of Kpart and K (zero for a DSystem, whose second derivatives have no v part): a curvature
+            // block that reaches into the v rows (hz_nx > 2 nd + nk) would put S_k there, so such a problem takes the dense kernel as well
+            const bool hz_fits = !p->hz_dev || p->hz_nx <= 2 * p->ds_nd + p->ds_nk;
+            if (p->ds_nd > 0 && !(dense_env && dense_env[0] == '1') && p->ds_nk >= round_up(p->ds_nd, 4) - p->ds_nd && p->ds_nk <= 31 && (nX % 2) == 0 && aligned && hz_fits) {
                 const LqDsLayout D(16 * nt, p->nU, p->ds_nd, p->ds_nd + p->ds_nk);
                 const size_t ldsd = sizeof(double) * (size_t)D.total;
                 if (ldsd <= 160 * 1024 - 256 && nt * (D.ldc / 16) + nt * ((p->nU + 15) / 16) <= 32) {
-#define TG_LQD_LAUNCH(NT_, NR_)                                                                                                  \
-                    do {                                                                                                         \
-                        if (ldsd > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tv_lq_ds<NT_, NR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd)); \
-                        hipLaunchKernelGGL((k_tv_lq_ds<NT_, NR_>), dim3(p->n_problems), dim3(LQM_T), ldsd, dopt_stream(device), *p);                 \
-                    } while (0)
-#define TG_LQD_NR(NT_)                                                                                                           \
-                    switch (nr) {                                                                                                \
-                    case 4: TG_LQD_LAUNCH(NT_, 4); break;                                                                        \
-                    case 8: TG_LQD_LAUNCH(NT_, 8); break;                                                                        \
-                    case 20: TG_LQD_LAUNCH(NT_, 20); break;                                                                      \
-                    default: TG_LQD_LAUNCH(NT_, 32); break;                                                                      \
-                    }
-                    switch (nt) {
-                    case 1: TG_LQD_NR(1) break;
-                    case 2: TG_LQD_NR(2) break;
-                    case 3: TG_LQD_NR(3) break;
-                    case 5: TG_LQD_NR(5) break;
-                    default: TG_LQD_NR(6) break;
-                    }
-#undef TG_LQD_NR
-#undef TG_LQD_LAUNCH
-                    HIP_TRY(hipGetLastError());
+                    pl.kernel = 2; pl.cls = nt; pl.nr = nr; pl.threads = LQM_T; pl.lds = ldsd;
                     return TG_SUCCESS;
                 }
             }
             const LqLayout L2(16 * nt, p->nU);   // the kernel pads nX to 16 * nt
             const size_t ldsk = sizeof(double) * (size_t)L2.total;
             if (ldsk <= 160 * 1024 - 256) {
-#define TG_LQ_LAUNCH(NT_, NR_)                                                                                                   \
-                do {                                                                                                             \
-                    if (ldsk > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tv_lq_mfma<NT_, NR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsk)); \
-                    hipLaunchKernelGGL((k_tv_lq_mfma<NT_, NR_>), dim3(p->n_problems), dim3(LQM_T), ldsk, dopt_stream(device), *p);                   \
-                } while (0)
-#define TG_LQ_NR(NT_)                                                                                                            \
-                switch (nr) {                                                                                                    \
-                case 4: TG_LQ_LAUNCH(NT_, 4); break;                                                                             \
-                case 8: TG_LQ_LAUNCH(NT_, 8); break;                                                                             \
-                case 20: TG_LQ_LAUNCH(NT_, 20); break;                                                                           \
-                default: TG_LQ_LAUNCH(NT_, 32); break;                                                                           \
-                }
-                switch (nt) {
-                case 1: TG_LQ_NR(1) break;
-                case 2: TG_LQ_NR(2) break;
-                case 3: TG_LQ_NR(3) break;
-                case 5: TG_LQ_NR(5) break;
-                default: TG_LQ_NR(6) break;
-                }
-#undef TG_LQ_NR
-#undef TG_LQ_LAUNCH
-                HIP_TRY(hipGetLastError());
+                pl.kernel = 1; pl.cls = nt; pl.nr = nr; pl.threads = LQM_T; pl.lds = ldsk;
                 return TG_SUCCESS;
             }
         }
     }
+    // VALU kernel, size class: tile size TS with nX <= 16*TS (one tile per thread), prefetch registers RI*CI >= nX*ceil(nX/32)/8
     const int cls = (nX <= 32 && nXU <= 2 * LQ_T) ? 0 : ((nX <= 64 && nXU <= 6 * LQ_T) ? 1 : ((nX <= 80 && nXU <= 8 * LQ_T) ? 2 : ((nX <= 96 && nXU <= 12 * LQ_T) ? 3 : -1)));
     if (cls < 0) return fail(TG_ERR_UNSUPPORTED, "state dimension too large for the LDS-resident Riccati kernel");
     const int ts = cls == 0 ? 2 : (cls == 1 ? 4 : (cls == 2 ? 5 : 6));
     const size_t lds = lq_lds_bytes(p->nX, p->nU, ts);
     if (lds > 160 * 1024 - 64) return fail(TG_ERR_UNSUPPORTED, "state dimension too large for the LDS-resident Riccati kernel");
-    const void *fn = cls == 0 ? (const void *)k_tv_lq<2, 4, 1, 2> : (cls == 1 ? (const void *)k_tv_lq<4, 8, 2, 6>
-                     : (cls == 2 ? (const void *)k_tv_lq<5, 10, 3, 8> : (const void *)k_tv_lq<6, 12, 3, 12>));
+    pl.kernel = 0; pl.cls = ts; pl.nr = 0; pl.threads = LQ_T; pl.lds = lds;
+    return TG_SUCCESS;
+}
+
+struct TangentPlan { int kernel = -1, ca = 0, cb = 0, ck = 0, threads = 0; bool pair = false; size_t lds = 0; };   // kernel: 0 k_tangent, 1 k_tangent_rows<ca, cb, ck, pair>
+int tangent_plan(int nX, int nU, const void *A_dev, const void *B_dev, const void *K_dev, TangentPlan &pl) {
+    if (nX <= 4 * TR_MAX_CA && nU <= 4 * TR_MAX_CB && nX <= 8 * TR_MAX_CK && nX >= 1 && nU >= 1 && !std::getenv("TREPAMD_TANGENT_LDS")) {     // rows in registers (k_tangent_rows)
+        int nt = 4 * nX > 8 * nU ? 4 * nX : 8 * nU;
+        nt = (nt + 63) & ~63;
+        if (nt <= 384) {
+            // even sizes: pairs of columns per thread, 16-byte loads (rows of A, B, K then start on 16-byte boundaries)
+            const bool pair = nX % 2 == 0 && nU % 2 == 0 && (((uintptr_t)A_dev | (uintptr_t)B_dev | (uintptr_t)K_dev) & 15) == 0 && !std::getenv("TREPAMD_TANGENT_NO_PAIRS");
+            const int nca = pair ? 2 * ((nX + 7) / 8) : (nX + 3) / 4, ncb = pair ? 2 * ((nU + 7) / 8) : (nU + 3) / 4, nck = pair ? 2 * ((nX + 15) / 16) : (nX + 7) / 8;
+            pl.kernel = 1; pl.pair = pair; pl.threads = nt;
+            pl.lds = sizeof(double) * (2 * (size_t)(8 * nck) + 4 * ncb + nt);
+            if (nca <= 8 && ncb <= 4 && nck <= 4) { pl.ca = 8; pl.cb = 4; pl.ck = 4; }
+            else if (nca <= 20 && ncb <= 6 && nck <= 10) { pl.ca = 20; pl.cb = 6; pl.ck = 10; }
+            else { pl.ca = 24; pl.cb = 8; pl.ck = 12; }
+            return TG_SUCCESS;
+        }
+    }
+    if (nX < 1 || nU < 1) return fail(TG_ERR_INVALID, "bad arguments");
+    const int lda = nX | 1;
+    const size_t lds = sizeof(double) * ((size_t)nX * lda + (size_t)nX * nU + (size_t)nU * lda + 2 * nX + nU + SW_T);
+    if (lds > 160 * 1024 - 64 || nX > 96 || nX * nU > 12 * SW_T) return fail(TG_ERR_UNSUPPORTED, "state dimension too large");
+    pl.kernel = 0; pl.threads = SW_T; pl.lds = lds;
+    return TG_SUCCESS;
+}
+}  // namespace
+
+extern "C" {
+
+int tg_tv_lq_plan(const tg_lq_problem *p, int32_t out[6]) {
+    LqPlan pl;
+    const int rc = lq_plan(p, pl);
+    if (out) {
+        out[0] = pl.kernel; out[1] = pl.cls; out[2] = pl.nr; out[3] = pl.threads; out[4] = (int32_t)pl.lds; out[5] = 0;
+    }
+    return rc;
+}
+
+int tg_tv_lq(int32_t device, const tg_lq_problem *p) {
+    LqPlan pl;
+    const int rc = lq_plan(p, pl);
+    if (rc != TG_SUCCESS) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const int nt = pl.cls, nr = pl.nr;
+    if (pl.kernel == 2) {
+        const size_t ldsd = pl.lds;
+#define TG_LQD_LAUNCH(NT_, NR_)                                                                                                  \
+        do {                                                                                                                     \
+            if (ldsd > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tv_lq_ds<NT_, NR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd)); \
+            hipLaunchKernelGGL((k_tv_lq_ds<NT_, NR_>), dim3(p->n_problems), dim3(LQM_T), ldsd, dopt_stream(device), *p);         \
+        } while (0)
+#define TG_LQD_NR(NT_)                                                                                                           \
+        switch (nr) {                                                                                                            \
+        case 4: TG_LQD_LAUNCH(NT_, 4); break;                                                                                    \
+        case 8: TG_LQD_LAUNCH(NT_, 8); break;                                                                                    \
+        case 20: TG_LQD_LAUNCH(NT_, 20); break;                                                                                  \
+        default: TG_LQD_LAUNCH(NT_, 32); break;                                                                                  \
+        }
+        switch (nt) {
+        case 1: TG_LQD_NR(1) break;
+        case 2: TG_LQD_NR(2) break;
+        case 3: TG_LQD_NR(3) break;
+        case 5: TG_LQD_NR(5) break;
+        default: TG_LQD_NR(6) break;
+        }
+#undef TG_LQD_NR
+#undef TG_LQD_LAUNCH
+        HIP_TRY(hipGetLastError());
+        return TG_SUCCESS;
+    }
+    if (pl.kernel == 1) {
+        const size_t ldsk = pl.lds;
+#define TG_LQ_LAUNCH(NT_, NR_)                                                                                                   \
+        do {                                                                                                                     \
+            if (ldsk > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tv_lq_mfma<NT_, NR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsk)); \
+            hipLaunchKernelGGL((k_tv_lq_mfma<NT_, NR_>), dim3(p->n_problems), dim3(LQM_T), ldsk, dopt_stream(device), *p);       \
+        } while (0)
+#define TG_LQ_NR(NT_)                                                                                                            \
+        switch (nr) {                                                                                                            \
+        case 4: TG_LQ_LAUNCH(NT_, 4); break;                                                                                     \
+        case 8: TG_LQ_LAUNCH(NT_, 8); break;                                                                                     \
+        case 20: TG_LQ_LAUNCH(NT_, 20); break;                                                                                   \
+        default: TG_LQ_LAUNCH(NT_, 32); break;                                                                                   \
+        }
+        switch (nt) {
+        case 1: TG_LQ_NR(1) break;
+        case 2: TG_LQ_NR(2) break;
+        case 3: TG_LQ_NR(3) break;
+        case 5: TG_LQ_NR(5) break;
+        default: TG_LQ_NR(6) break;
+        }
+#undef TG_LQ_NR
+#undef TG_LQ_LAUNCH
+        HIP_TRY(hipGetLastError());
+        return TG_SUCCESS;
+    }
+    const int ts = pl.cls;
+    const size_t lds = pl.lds;
+    const void *fn = ts == 2 ? (const void *)k_tv_lq<2, 4, 1, 2> : (ts == 4 ? (const void *)k_tv_lq<4, 8, 2, 6>
+                     : (ts == 5 ? (const void *)k_tv_lq<5, 10, 3, 8> : (const void *)k_tv_lq<6, 12, 3, 12>));
     if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    switch (cls) {
-    case 0: hipLaunchKernelGGL((k_tv_lq<2, 4, 1, 2>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
-    case 1: hipLaunchKernelGGL((k_tv_lq<4, 8, 2, 6>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
-    case 2: hipLaunchKernelGGL((k_tv_lq<5, 10, 3, 8>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
+    switch (ts) {
+    case 2: hipLaunchKernelGGL((k_tv_lq<2, 4, 1, 2>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
+    case 4: hipLaunchKernelGGL((k_tv_lq<4, 8, 2, 6>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
+    case 5: hipLaunchKernelGGL((k_tv_lq<5, 10, 3, 8>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
     default: hipLaunchKernelGGL((k_tv_lq<6, 12, 3, 12>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
     }
     HIP_TRY(hipGetLastError());
@@ -2194,40 +2262,43 @@ int tg_tangent_rollout(int32_t device, int32_t n_problems, int32_t horizon, int3
                        const double *r_dev, double *dX_dev, double *dU_dev, double *dcost_dev) {
     if (n_problems <= 0 || horizon <= 0 || !A_dev || !B_dev || !K_dev || !C_dev || !q_dev || !r_dev || !dX_dev || !dU_dev || !dcost_dev)
         return fail(TG_ERR_INVALID, "bad arguments");
-    if (nX <= 4 * TR_MAX_CA && nU <= 4 * TR_MAX_CB && nX <= 8 * TR_MAX_CK && nX >= 1 && nU >= 1 && !std::getenv("TREPAMD_TANGENT_LDS")) {     // rows in registers (k_tangent_rows)
-        int nt = 4 * nX > 8 * nU ? 4 * nX : 8 * nU;
-        nt = (nt + 63) & ~63;
-        if (nt <= 384) {
-            HIP_TRY(hipSetDevice(device));
-            // even sizes: pairs of columns per thread, 16-byte loads (rows of A, B, K then start on 16-byte boundaries)
-            const bool pair = nX % 2 == 0 && nU % 2 == 0 && (((uintptr_t)A_dev | (uintptr_t)B_dev | (uintptr_t)K_dev) & 15) == 0 && !std::getenv("TREPAMD_TANGENT_NO_PAIRS");
-            const int nca = pair ? 2 * ((nX + 7) / 8) : (nX + 3) / 4, ncb = pair ? 2 * ((nU + 7) / 8) : (nU + 3) / 4, nck = pair ? 2 * ((nX + 15) / 16) : (nX + 7) / 8;
-            const size_t ldsr = sizeof(double) * (2 * (size_t)(8 * nck) + 4 * ncb + nt);
-#define LAUNCH_TR(CA_, CB_, CK_, PAIR_)                                                                                                              \
-            hipLaunchKernelGGL((k_tangent_rows<CA_, CB_, CK_, PAIR_>), dim3(n_problems), dim3(nt), ldsr, dopt_stream(device), horizon, nX, nU, select_dev, \
-                               A_dev, B_dev, K_dev, C_dev, q_dev, r_dev, dX_dev, dU_dev, dcost_dev)
-            if (pair) {
-                if (nca <= 8 && ncb <= 4 && nck <= 4) LAUNCH_TR(8, 4, 4, true);
-                else if (nca <= 20 && ncb <= 6 && nck <= 10) LAUNCH_TR(20, 6, 10, true);       // the puppet's nX = 80, nU = 18
-                else LAUNCH_TR(24, 8, 12, true);
-            }
-            else if (nca <= 8 && ncb <= 4 && nck <= 4) LAUNCH_TR(8, 4, 4, false);
-            else if (nca <= 20 && ncb <= 6 && nck <= 10) LAUNCH_TR(20, 6, 10, false);
-            else LAUNCH_TR(24, 8, 12, false);
-#undef LAUNCH_TR
-            HIP_TRY(hipGetLastError());
-            return TG_SUCCESS;
-        }
-    }
-    const int lda = nX | 1;
-    const size_t lds = sizeof(double) * ((size_t)nX * lda + (size_t)nX * nU + (size_t)nU * lda + 2 * nX + nU + SW_T);
-    if (lds > 160 * 1024 - 64 || nX > 96 || nX * nU > 12 * SW_T) return fail(TG_ERR_UNSUPPORTED, "state dimension too large");
+    TangentPlan pl;
+    const int rc = tangent_plan(nX, nU, A_dev, B_dev, K_dev, pl);
+    if (rc != TG_SUCCESS) return rc;
     HIP_TRY(hipSetDevice(device));
+    if (pl.kernel == 1) {     // rows in registers (k_tangent_rows)
+        const int nt = pl.threads;
+        const size_t ldsr = pl.lds;
+#define LAUNCH_TR(CA_, CB_, CK_, PAIR_)                                                                                                              \
+        hipLaunchKernelGGL((k_tangent_rows<CA_, CB_, CK_, PAIR_>), dim3(n_problems), dim3(nt), ldsr, dopt_stream(device), horizon, nX, nU, select_dev, \
+                           A_dev, B_dev, K_dev, C_dev, q_dev, r_dev, dX_dev, dU_dev, dcost_dev)
+        if (pl.pair) {
+            if (pl.ca == 8) LAUNCH_TR(8, 4, 4, true);
+            else if (pl.ca == 20) LAUNCH_TR(20, 6, 10, true);       // the puppet's nX = 80, nU = 18
+            else LAUNCH_TR(24, 8, 12, true);
+        }
+        else if (pl.ca == 8) LAUNCH_TR(8, 4, 4, false);
+        else if (pl.ca == 20) LAUNCH_TR(20, 6, 10, false);
+        else LAUNCH_TR(24, 8, 12, false);
+#undef LAUNCH_TR
+        HIP_TRY(hipGetLastError());
+        return TG_SUCCESS;
+    }
+    const size_t lds = pl.lds;
     if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tangent, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_tangent, dim3(n_problems), dim3(SW_T), lds, dopt_stream(device), horizon, nX, nU, select_dev, A_dev, B_dev, K_dev, C_dev, q_dev,
                        r_dev, dX_dev, dU_dev, dcost_dev);
     HIP_TRY(hipGetLastError());
     return TG_SUCCESS;
+}
+
+int tg_tangent_rollout_plan(int32_t nX, int32_t nU, const void *A, const void *B, const void *K, int32_t out[6]) {
+    TangentPlan pl;
+    const int rc = tangent_plan(nX, nU, A, B, K, pl);
+    if (out) {
+        out[0] = pl.kernel; out[1] = pl.ca; out[2] = pl.cb; out[3] = pl.ck; out[4] = pl.pair ? 1 : 0; out[5] = pl.threads;
+    }
+    return rc;
 }
 
 int tg_quadratic_cost(int32_t device, int32_t n_trajectories, int32_t group, const int32_t *select_dev, int32_t horizon,
