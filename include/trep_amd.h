@@ -257,7 +257,14 @@ int tg_batch_set_stream(tg_batch *b, void *hip_stream);
  * set / step uses t[k+1] - t[k]).  A list of `count` step sizes on the batch replaces the scalar dt of the entry points
  * below it: by_trajectory = 0: step k of a rollout / closed-loop rollout uses dt[k] (n_steps <= count); by_trajectory = 1:
  * trajectory t of a one-step batch (tg_batch_step, tg_batch_set_from_trajectories and the derivative kernels that follow:
- * batch = seeds x horizon) uses dt[t % count].  count = 0 removes the list. */
+ * batch = seeds x horizon) uses dt[t % count].  count = 0 removes the list.
+ *   - A refused call (TG_ERR_INVALID: a zero or non-finite entry) changes nothing: the list set before stays in use.
+ *   - A by-step list belongs to the rollouts.  The one-step entry points (tg_batch_step, tg_batch_set_from_trajectories) step by
+ *     what the caller passes (t2_new - t2, dt) unless the list is by trajectory.
+ *   - While a by-trajectory list is set, EVERY kernel mode takes the trajectory's size for t2 - t1: the derivative kernels, calc_f, and
+ *     calc_p2 (tg_batch_calc_p2 of an initialisation from two configurations included: set the list after it).
+ *   - A by-trajectory list belongs to one-step launches.  A rollout or closed-loop rollout of more than one step is refused with
+ *     TG_ERR_INVALID while one is set, before anything is launched. */
 int tg_batch_set_step_sizes(tg_batch *b, int32_t count, const double *dt_host, int32_t by_trajectory);
 
 /* Pivot rule of the Newton-system solve (replaces LU_decomp + LU_solve_vec, math-code.c:337-461, as used by
@@ -394,8 +401,9 @@ int tg_batch_lagrangian_forward(tg_batch *b, const double *q_host, const double 
 
 /* Initial guess of the Newton iteration in the device-resident rollouts.  0 (default): the reference's, q2 <- the previous
  * q2 (midpointvi.py:188-197) -- iteration counts then match the reference's.  1: constant-velocity extrapolation
- * q2 + (q2 - q1); same root to within the solver tolerance, about one Newton iteration fewer per step.  An opt-in
- * that departs from the reference's iteration-by-iteration behaviour; the headline benchmark uses 0. */
+ * q2 + (q2 - q1) dt_k / dt_{k-1} (the last displacement, scaled by the step ratio on a non-uniform time base); same root
+ * to within the solver tolerance, about one Newton iteration fewer per step.  An opt-in that departs from the reference's
+ * iteration-by-iteration behaviour; the headline benchmark uses 0. */
 int tg_batch_set_predictor(tg_batch *b, int32_t mode);
 
 /* Kinetic and potential energy of every state of the batch: energy[b] = {T, V} with T = sum over the massive frames of

@@ -93,6 +93,368 @@ TEAM_CELLS = {
 }
 
 
+# ---- shared by the oracle-comparison tests of the generic kernels (test_gpu_team_sizes.py, the time-base tests) ------------------------
+def starts(name, d, B, N, rng, extra=0):
+    """B starts (Q[k], Q[k+1]) of recorded trajectories at random k and the recorded inputs from there on (N + extra steps); forces
+    get noise and unconstrained systems a random shift of the dynamic configs, so that every team of a wave has its own path."""
+    g = golden(name)
+    trajs = trajectories(name)
+    nd, nu = d.n_dyn, d.n_inputs
+    Q0, Q1, U, K = [], [], [], []
+    for b in range(B):
+        pre, _, u, kk = trajs[int(rng.integers(len(trajs)))]
+        Q = g[pre + "Q"]
+        k = int(rng.integers(0, len(Q) - N - extra - 2))
+        q0, q1 = Q[k].copy(), Q[k + 1].copy()
+        if d.n_constraints == 0:
+            shift = 0.2 * rng.standard_normal(nd)
+            q0[:nd] += shift
+            q1[:nd] += shift
+        uu = u[k + 1:k + 1 + N + extra]
+        Q0.append(q0)
+        Q1.append(q1)
+        U.append(uu + 0.5 * rng.standard_normal(uu.shape) if nu else uu)
+        K.append(kk[k + 1:k + 1 + N + extra])
+    return np.array(Q0), np.array(Q1), np.array(U).reshape(B, N + extra, nu), np.array(K).reshape(B, N + extra, d.n_kin)
+
+
+def oracle_hz(o, d, z, zl):
+    """sum_o z[o] q2_dAdB[o] + z[nq + o] p2_dAdB[o] (+ zl[c] l1_dAdB[c]) from the oracle's full second-derivative tensors."""
+    nq, nd, nu, nk, nc = d.n_configs, d.n_dyn, d.n_inputs, d.n_kin, d.n_constraints
+    sizes = {"dq1": nq, "dp1": nd, "du1": nu, "dk2": nk}
+    offs = {"dq1": 0, "dp1": nq, "du1": nq + nd, "dk2": nq + nd + nu}
+    R = nq + nd + nu + nk
+    H = np.zeros((R, R))
+    for pair in PAIRS:
+        a, b = pair[:3], pair[3:]
+        if not sizes[a] or not sizes[b]:
+            continue
+        blk = o.deriv2("q2_" + pair) @ z[:nd] + o.deriv2("p2_" + pair) @ z[nq:nq + nd]
+        if nc:
+            blk = blk + o.deriv2("l1_" + pair) @ zl
+        H[offs[a]:offs[a] + sizes[a], offs[b]:offs[b] + sizes[b]] = blk
+        H[offs[b]:offs[b] + sizes[b], offs[a]:offs[a] + sizes[a]] = blk.T
+    return H
+
+
+# ---- the non-uniform time base (tg_batch_set_step_sizes): test_time_base_cpu.py keeps the table honest with the oracle alone and runs
+# the emulated generic kernels over it, test_gpu_time_base.py runs it on the device, tools/time_base_parity.py records it.
+# system -> (team the generic kernels get, specialised library prebuilt by build(), the path the system is in the table for)
+TB_DT = 0.01
+TB_N = 24
+TB_SYSTEMS = collections.OrderedDict([
+    ("pend_on_cart", (4, True, "nu = 1, small team")),
+    ("scissor4", (64, True, "8 constraints, fused rates")),
+    ("puppet40", (64, True, "18 kinematic configs, 6 constraints, team 64")),
+    ("puppet_basic", (64, True, "team 64")),
+    ("damper_link", (4, False, "velocity forces")),
+    ("spring_arm", (16, False, "SPRINGS, one kinematic config")),
+    ("wrench_arm", (16, False, "3 inputs plus one kinematic config")),
+    ("puppet_forces", (64, False, "18 inputs")),
+    ("plane_link", (16, False, "constraints at a small team")),
+])
+TB_PATTERNS = ("alternating", "random")
+TB_CASES = [(n, p) for n in TB_SYSTEMS for p in TB_PATTERNS]
+TB_KINDS = [(n, False) for n in TB_SYSTEMS] + [(n, True) for n in TB_SYSTEMS if TB_SYSTEMS[n][1]]
+TB_CLOSED_LOOP = ("pend_on_cart", "wrench_arm", "spring_arm", "puppet_forces", "puppet40")
+TB_GROUP = 2                                        # trajectories per gain set of the closed loops
+# closed loops: (size of the move of rows 1..N of bX, 1-norm of the config columns of every gain row), chosen per system so that the
+# feedback moves X by 1e-6 .. 1e-2 (test_time_base_cpu.py checks it): forces on a heavy puppet move it little, kinematic configs are
+# set by their input directly, and on the puppet a move above 1e-4 makes the reference loop itself diverge through the string lengths
+TB_LOOP = {"pend_on_cart": (3e-3, 1.0), "wrench_arm": (1e-4, 0.3), "spring_arm": (1e-4, 0.3), "puppet_forces": (3e-2, 1.0),
+           "puppet40": (1e-4, 0.1)}
+# another start where the first one is badly conditioned (conditioning rule, test_time_base_cpu.py): of eight scissor-lift draws, the
+# 1-ulp floor of X over 24 steps ranges from 3e-13 to 4e-11; this one has 3e-13
+TB_START = {"scissor4": 3}
+# (case, quantity) whose bound needs the second term of max(tolerance, 64 e_ref) whatever the start and whatever the horizon: the
+# scissor lift's multipliers are conditioned by 1 / dt^2 at each step, and the floor does not accumulate along the rollout.  One ulp of
+# the start moves lambda1 by (worst of five trajectories and both patterns, per draw of TB_START 0 .. 7)
+#   24 steps: 2.7e-11 2.6e-11 1.6e-11 1.0e-11 1.3e-10 1.1e-11 2.3e-11 1.4e-11
+#   12 steps: 2.1e-11 1.6e-11 9.8e-12 1.8e-11 1.6e-11 3.4e-11 1.7e-11 1.6e-11
+#    6 steps: 2.6e-11 1.5e-11 8.6e-12 1.4e-11 8.5e-12 9.5e-12 1.5e-11 1.4e-11
+#    1 step:  5.3e-11 5.8e-11 3.4e-11 6.7e-11 4.4e-11 3.0e-11 3.9e-11 8.1e-11
+# so neither another start nor a shorter horizon brings 64 e_ref under 3e-10 (that needs 4.7e-12); draw 3 at 24 steps is the best.
+TB_SECOND_TERM = {("scissor4", "lambda1")}
+# The project's tolerances per quantity: states 1e-10 (BASELINE north star), the others as in test_gpu_team_sizes.py.  U of a closed
+# loop is bU - K (X - bX) with every row of K below one in the 1-norm (tb_closed_loop_inputs): it inherits X's tolerance.
+TB_TOL = {"X": 1e-10, "U": 1e-10, "p1": 1e-10, "p2": 1e-10, "calc_p2": 1e-12, "f": 1e-12, "lambda1": 3e-10, "d1": 1e-9, "AB": 1e-9,
+          "hz": 1e-8}
+_tb = {}
+
+
+def tb_seed(*key):
+    import zlib
+    return zlib.crc32(" ".join(str(k) for k in key).encode())
+
+
+def tb_batch(name):
+    """One full block of teams plus a ragged one; 5 at a team of 64 (the closed-loop subset needs two gain groups and a rest)."""
+    return max(2 * (64 // TB_SYSTEMS[name][0]) + 1, 5)
+
+
+def tb_step_sizes(pattern, N=TB_N, name=""):
+    """alternating: DT x (0.6, 1.5, 0.6, ...), the largest ratio between neighbours, so a dt taken from the step before or after is as
+    wrong as it gets; random: DT x (0.6 + 0.9 r), seeded.  (Nothing below 0.6 DT: momenta and multipliers are conditioned by 1 / dt
+    and 1 / dt^2, and the project's tolerances were set at DT.)"""
+    if pattern == "alternating":
+        return TB_DT * np.where(np.arange(N) % 2 == 0, 0.6, 1.5)
+    assert pattern == "random"
+    return TB_DT * (0.6 + 0.9 * np.random.default_rng(tb_seed("steps", name)).random(N))       # (a shorter list is a prefix)
+
+
+def tb_wrong_step_sizes(dts):
+    """The three ways of getting the time base wrong that the tests must tell from the right one."""
+    return collections.OrderedDict([("uniform mean", np.full(len(dts), dts.mean())), ("one step forward", np.roll(dts, -1)),
+                                    ("one step back", np.roll(dts, 1))])
+
+
+TB_EXTRA = 5                 # steps recorded behind a case's N: a second rollout of the same batch, a list longer than the rollout
+
+
+def tb_case(name, pattern, N=TB_N, B=None):
+    """dict(d, B, N, Q0, Q1, U [B][N][nu], K [B][N][nk], dts [N]) of a case: distinct starts (starts() above); U_all, K_all, dts_all are
+    TB_EXTRA steps longer."""
+    key = ("case", name, pattern, N, B)
+    if key not in _tb:
+        _, d = build(name)
+        B_ = tb_batch(name) if B is None else B
+        Q0, Q1, U, K = starts(name, d, B_, N, np.random.default_rng(tb_seed("starts", name, TB_START.get(name, 0))), extra=TB_EXTRA)
+        dts = tb_step_sizes(pattern, N + TB_EXTRA, name)
+        _tb[key] = dict(name=name, pattern=pattern, d=d, B=B_, N=N, Q0=Q0, Q1=Q1, U=np.ascontiguousarray(U[:, :N]),
+                        K=np.ascontiguousarray(K[:, :N]), dts=dts[:N].copy(), U_all=U, K_all=K, dts_all=dts)
+    return _tb[key]
+
+
+def tb_state(o, dt):
+    """X = [q2; p2; (k2 - k1) / dt] of an oracle (DSystem's state, dsystem.py:276-281)."""
+    q1, q2 = o.q1, o.q2
+    return np.concatenate([q2, o.p2, (q2[o.nd:] - q1[o.nd:]) / dt])
+
+
+def tb_AB(d, d1, dt):
+    """DSystem.fdx / fdu (dsystem.py:284-317) of one step of size dt from the twelve first-derivative blocks [variable][output]."""
+    nq, nd, nk, nu = d.n_configs, d.n_dyn, d.n_kin, d.n_inputs
+    nX, nU, nqd = nq + nd + nk, nu + nk, nq + nd
+    A, B = np.zeros((nX, nX)), np.zeros((nX, nU))
+    A[:nd, :nq], A[:nd, nq:nqd] = d1["q2_dq1"].T, d1["q2_dp1"].T
+    A[nq:nqd, :nq], A[nq:nqd, nq:nqd] = d1["p2_dq1"].T, d1["p2_dp1"].T
+    A[nqd:, nd:nq] = -np.eye(nk) / dt
+    B[:nd, :nu], B[:nd, nu:] = d1["q2_du1"].T, d1["q2_dk2"].T
+    B[nq:nqd, :nu], B[nq:nqd, nu:] = d1["p2_du1"].T, d1["p2_dk2"].T
+    B[nd:nq, nu:] = np.eye(nk)
+    B[nqd:, nu:] = np.eye(nk) / dt
+    return A, B
+
+
+def tb_oracle_derivs(o, d, dt, z=None, zl=None):
+    """dict(d1, A, B[, hz]) of the oracle's last step (of size dt)."""
+    o.calc_deriv1()
+    d1 = dict((n, o.deriv1(n)) for n in D1)
+    A, B = tb_AB(d, d1, dt)
+    out = dict(d1=d1, A=A, B=B)
+    if z is not None:
+        o.calc_deriv2()
+        out["hz"] = oracle_hz(o, d, z, zl)
+    return out
+
+
+def tb_oracle_rollout(d, q0, q1, dts, U=None, K=None, feedback=None, z=None, zl=None, o=None):
+    """The reference of every time-base test: OracleMVI from (0, q0, DT, q1) (or a given oracle o, continued), stepped with
+    o.step(o.times()[1] + dts[k], ...).  feedback = (Kp [N][nU][nX], bX [N+1][nX], bU [N][nU]): the closed loop U_k = bU_k - K_k (X_k -
+    bX_k) with no correction at k = 0 and X_0 = bX_0 by definition of the projection (dsystem.py:441).  z (and zl): also the
+    derivatives of the last step.  Every step must converge (OracleError otherwise).  Returns dict(X, U, iterations, o, p1, p2,
+    lambda1, f, calc_p2, times[, d1, A, B, hz])."""
+    from oracle.oracle import OracleMVI
+    if o is None:
+        o = OracleMVI(d)
+        o.initialize_from_configs(0.0, q0, TB_DT, q1)
+    N, nu = len(dts), o.nu
+    X = np.zeros((N + 1, o.nq + o.nd + o.nk))
+    Uo = np.zeros((N, o.nu + o.nk))
+    t1, t2 = o.times()
+    X[0] = tb_state(o, t2 - t1) if feedback is None else feedback[1][0]
+    its = 0
+    for k in range(N):
+        if feedback is None:
+            Uo[k] = np.concatenate([U[k], K[k]])
+        else:
+            Kp, bX, bU = feedback
+            Uo[k] = bU[k] - (Kp[k].dot(X[k] - bX[k]) if k > 0 else 0.0)
+        its += o.step(o.times()[1] + dts[k], Uo[k, :nu], Uo[k, nu:])
+        X[k + 1] = tb_state(o, dts[k])
+    out = dict(X=X, U=Uo, iterations=its, o=o, p1=o.p1, p2=o.p2, lambda1=o.lambda1, f=o.calc_f(), times=o.times())
+    o.calc_p2()                                   # p2 = D2L2(q1, q2) of the last step with t2 - t1 (the solve's own p2 is put back)
+    out["calc_p2"] = o.p2
+    o.p2 = out["p2"]
+    if z is not None:
+        out.update(tb_oracle_derivs(o, d, dts[N - 1], z, zl))
+    return out
+
+
+def tb_contraction(name, B):
+    """Z [B][nX], ZL [B][nc] of a case's deriv2z checks."""
+    _, d = build(name)
+    rng = np.random.default_rng(tb_seed("z", name))
+    return rng.standard_normal((B, d.n_configs + d.n_dyn + d.n_kin)), rng.standard_normal((B, d.n_constraints))
+
+
+def tb_reference(name, pattern, N=TB_N, B=None):
+    """Open-loop oracle runs of every trajectory of a case (list of tb_oracle_rollout dicts, with derivatives), computed once."""
+    key = ("ref", name, pattern, N, B)
+    if key not in _tb:
+        c = tb_case(name, pattern, N, B)
+        Z, ZL = tb_contraction(name, c["B"])
+        _tb[key] = [tb_oracle_rollout(c["d"], c["Q0"][b], c["Q1"][b], c["dts"], c["U"][b], c["K"][b], z=Z[b], zl=ZL[b])
+                    for b in range(c["B"])]
+    return _tb[key]
+
+
+
+# The extrapolating predictor accepts a warm start that is already inside the solver's tolerance ball, so its trajectory is the exact
+# one only to that tolerance -- and so is the oracle's: at the default 1e-10 the oracle itself is up to 2.7e-10 (pend_on_cart), 2.8e-9
+# (plane_link) from the oracle at 1e-11 over the table's 24 steps.  The predictor tests therefore tighten the solver tolerance of both
+# sides to 1e-11, the tightest decade at which the reference converges on every step of their systems (at 1e-12 the cart's does not),
+# and keep X's tolerance.
+TB_PREDICTOR_TOL = 1e-11
+TB_PREDICTOR_SYSTEMS = ("pend_on_cart", "spring_arm", "puppet40")       # unconstrained, SPRINGS + a kinematic config, constrained
+
+
+def tb_predictor_reference(name, pattern, N=TB_N, B=None):
+    """Open-loop oracle runs of a case at the solver tolerance TB_PREDICTOR_TOL (every step must converge)."""
+    key = ("predref", name, pattern, N, B)
+    if key not in _tb:
+        from oracle.oracle import OracleMVI
+        c = tb_case(name, pattern, N, B)
+        out = []
+        for b in range(c["B"]):
+            o = OracleMVI(c["d"], tolerance=TB_PREDICTOR_TOL)
+            o.initialize_from_configs(0.0, c["Q0"][b], TB_DT, c["Q1"][b])
+            out.append(tb_oracle_rollout(c["d"], None, None, c["dts"], c["U"][b], c["K"][b], o=o))
+        _tb[key] = out
+    return _tb[key]
+
+
+def tb_wave_spread_feedback(d, team, n_items):
+    """The condition under which run_trajectory spreads the feedback's gain rows over the wavefront (csrc/mvi_core.hpp, the closed-loop
+    branch of the rollout loop); otherwise the per-row loop runs."""
+    nX, nU = d.n_configs + d.n_dyn + d.n_kin, d.n_inputs + d.n_kin
+    if team != 64 or nU == 0 or 2 * nU > 64:
+        return False
+    parts = min(4, 64 // nU)
+    return nX <= 32 * parts and nX + 4 * nU <= 6 * n_items
+
+
+def tb_closed_loop_inputs(name, pattern, N=TB_N, B=None):
+    """(Kp [groups][N][nU][nX], bX [B][N+1][nX], bU [B][N][nU]) of a case's closed loop, TB_GROUP trajectories per gain set.  bX / bU
+    are the oracle's open-loop trajectory on the non-uniform grid; rows 1..N of bX are moved (row 0 is exact: X_0 = bX_0).  Gains:
+    random; the config columns of every row have the 1-norm g of TB_LOOP (at most 1: U inherits X's tolerance), the v columns that
+    times DT and the p columns that times DT^2 -- feedback on the kinematic configs through momenta and velocities of size 1 / DT makes
+    the reference loop itself diverge otherwise."""
+    key = ("cl", name, pattern, N, B)
+    if key not in _tb:
+        c = tb_case(name, pattern, N, B)
+        d, Bn = c["d"], c["B"]
+        nq, nd, nk, nu = d.n_configs, d.n_dyn, d.n_kin, d.n_inputs
+        nX, nU = nq + nd + nk, nu + nk
+        move, g = TB_LOOP[name]
+        ref = tb_reference(name, pattern, N, B)
+        rng = np.random.default_rng(tb_seed("gains", name, pattern))
+        bX = np.array([r["X"] for r in ref])
+        bX[:, 1:] += move * rng.standard_normal(bX[:, 1:].shape)
+        bU = np.array([r["U"] for r in ref])
+        groups = (Bn + TB_GROUP - 1) // TB_GROUP
+        Kp = rng.standard_normal((groups, N, nU, nX))
+        for cols, scale in ((slice(0, nq), g), (slice(nq, nq + nd), g * TB_DT ** 2), (slice(nq + nd, nX), g * TB_DT)):
+            if cols.stop > cols.start:
+                Kp[..., cols] *= scale / np.abs(Kp[..., cols]).sum(axis=-1, keepdims=True)
+        _tb[key] = (Kp, bX, bU)
+    return _tb[key]
+
+
+def tb_closed_loop_reference(name, pattern, N=TB_N, B=None):
+    """The numpy loop over oracle steps of every trajectory of a case's closed loop."""
+    key = ("clref", name, pattern, N, B)
+    if key not in _tb:
+        c = tb_case(name, pattern, N, B)
+        Kp, bX, bU = tb_closed_loop_inputs(name, pattern, N, B)
+        _tb[key] = [tb_oracle_rollout(c["d"], c["Q0"][b], c["Q1"][b], c["dts"], feedback=(Kp[b // TB_GROUP], bX[b], bU[b]))
+                    for b in range(c["B"])]
+    return _tb[key]
+
+
+def _ulp(a, sign):
+    return np.nextafter(a, sign * np.inf)
+
+
+def tb_e_ref(name, pattern, N=TB_N, B=None, closed_loop=False):
+    """Conditioning floor of a case: the start (q0, q1) of every trajectory moved by one unit in the last place (q0 up, q1 down: the
+    start velocity moves most) and the oracle rerun; {quantity: largest relerr against the unperturbed run}.  Taken from the
+    reference alone, never from a kernel."""
+    key = ("eref", name, pattern, N, B, closed_loop)
+    if key not in _tb:
+        c = tb_case(name, pattern, N, B)
+        out = collections.OrderedDict()
+
+        def worst(q, e):
+            out[q] = max(out.get(q, 0.0), e)
+        if closed_loop:
+            Kp, bX, bU = tb_closed_loop_inputs(name, pattern, N, B)
+            ref = tb_closed_loop_reference(name, pattern, N, B)
+        else:
+            Z, ZL = tb_contraction(name, c["B"])
+            ref = tb_reference(name, pattern, N, B)
+        for b in range(c["B"]):
+            q0, q1 = _ulp(c["Q0"][b], 1.0), _ulp(c["Q1"][b], -1.0)
+            if closed_loop:
+                r = tb_oracle_rollout(c["d"], q0, q1, c["dts"], feedback=(Kp[b // TB_GROUP], bX[b], bU[b]))
+            else:
+                r = tb_oracle_rollout(c["d"], q0, q1, c["dts"], c["U"][b], c["K"][b], z=Z[b], zl=ZL[b])
+            for q in ("X", "U", "p1", "p2", "lambda1") + (() if closed_loop else ("hz",)):
+                worst(q, relerr(r[q], ref[b][q]))
+            if not closed_loop:
+                worst("d1", max(relerr(r["d1"][n], ref[b]["d1"][n]) for n in D1))
+                worst("AB", max(relerr(r["A"], ref[b]["A"]), relerr(r["B"], ref[b]["B"])))
+        _tb[key] = out
+    return _tb[key]
+
+
+
+TB_HORIZON = (2, 5)          # seeds x steps of the one-step-per-trajectory batches: batch = 10, list of 5, so t % count wraps once
+
+
+def tb_horizon(name, pattern):
+    """The horizon batch BatchDOptimizer builds (tg_batch_set_from_trajectories): dict(d, X [S][H+1][nX], U [S][H][nU], dts [H], Z, ZL = 0,
+    refs [S * H]) with refs[s * H + k] = the oracle set to X[s][k] (lambda1 = 0), stepped by dts[k] towards the hint X[s][k+1], and its
+    derivatives: dict(q2, p2, lambda1, iterations, d1, A, B, hz)."""
+    key = ("horizon", name, pattern)
+    if key not in _tb:
+        from oracle.oracle import OracleMVI
+        S, H = TB_HORIZON
+        c = tb_case(name, pattern, H, S)
+        d, dts = c["d"], c["dts"]
+        nq, nd, nu = d.n_configs, d.n_dyn, d.n_inputs
+        runs = [tb_oracle_rollout(d, c["Q0"][s], c["Q1"][s], dts, c["U"][s], c["K"][s]) for s in range(S)]
+        X, U = np.array([r["X"] for r in runs]), np.array([r["U"] for r in runs])
+        Z = np.random.default_rng(tb_seed("zh", name)).standard_normal((S * H, X.shape[2]))
+        ZL = np.zeros((S * H, d.n_constraints))
+        refs = []
+        for s in range(S):
+            for k in range(H):
+                o = OracleMVI(d)
+                o.initialize_from_state(0.0, X[s, k, :nq], X[s, k, nq:nq + nd])
+                it = o.step(dts[k], U[s, k, :nu], U[s, k, nu:], q2_hint=X[s, k + 1, :nd])
+                r = dict(q2=o.q2, p2=o.p2, lambda1=o.lambda1, iterations=it)
+                r.update(tb_oracle_derivs(o, d, dts[k], Z[s * H + k], ZL[s * H + k]))
+                refs.append(r)
+        _tb[key] = dict(d=d, X=X, U=U, dts=dts, Z=Z, ZL=ZL, refs=refs)
+    return _tb[key]
+
+
+def tb_bound(quantity, e_ref=None):
+    """max(project tolerance, 64 e_ref): the rule of the LQ tests, the floor from the reference's own error."""
+    return max(TB_TOL[quantity], 64.0 * (e_ref or {}).get(quantity, 0.0))
+
+
 # ---- shared by the discopt device tests (test_gpu_discopt_device.py, test_gpu_lq_classes.py, test_gpu_discopt_sizes.py) ----
 
 

@@ -99,6 +99,15 @@ class EmuBatch(object):
         self.status = np.zeros(batch, dtype=np.int32)
         self.t1 = self.t2 = 0.0
         self.tol = tolerance
+        self._by_trajectory = None
+        self.predictor = 0                 # RunArgs.predictor: 1 = the extrapolating warm start of the rollouts
+
+    def set_step_sizes(self, dts=None, by_trajectory=True):
+        """RunArgs.dt_steps with dt_period = len(dts): trajectory t of every later launch (one-step rollout, deriv1 / linearize,
+        deriv2z) steps by dts[t % len(dts)], as after tg_batch_set_step_sizes(..., by_trajectory = 1).  None clears.  (A by-step list
+        is an argument of the rollouts: dts=.)"""
+        assert by_trajectory
+        self._by_trajectory = None if dts is None else np.ascontiguousarray(dts, dtype=float)
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -109,11 +118,14 @@ class EmuBatch(object):
         a = RunArgs()
         a.batch, a.n_steps, a.max_iterations, a.mode = self.B, n_steps, max_it, mode
         a.group_size = 1
+        a.predictor = self.predictor
         a.dt, a.t1, a.t2, a.tolerance = dt, self.t1, self.t2, self.tol
         a.q1, a.q2, a.p1, a.p2, a.lam, a.u1 = _p(self.q1), _p(self.q2), _p(self.p1), _p(self.p2), _p(self.lam), _p(self.u1)
         a.U, a.K, a.X, a.f_out, a.q2_hint, a.lam_hint = _p(U), _p(K), _p(X), _p(f), _p(q2_hint), _p(lam_hint)
         a.iters = self.iters.ctypes.data_as(_I)
         a.status = self.status.ctypes.data_as(_I)
+        if self._by_trajectory is not None:
+            a.dt_steps, a.dt_period = _p(self._by_trajectory), len(self._by_trajectory)
         return a
 
     def _run(self, a, seeds=None):
@@ -165,8 +177,8 @@ class EmuBatch(object):
         self.L.emu_run(self.h, ctypes.byref(a))
         return A, Bm
 
-    def rollout_closed_loop(self, n_steps, dt, Kproj, bX, bU, group_size=1):
-        """U_k = bU_k - Kproj_k (X_k - bX_k) in-kernel; returns (X [B][N+1][nX], U [B][N][nU])."""
+    def rollout_closed_loop(self, n_steps, dt, Kproj, bX, bU, group_size=1, dts=None):
+        """U_k = bU_k - Kproj_k (X_k - bX_k) in-kernel; returns (X [B][N+1][nX], U [B][N][nU]).  dts: one step size per step."""
         Kproj = np.ascontiguousarray(Kproj, dtype=float)
         bX = np.ascontiguousarray(bX, dtype=float)
         bU = np.ascontiguousarray(bU, dtype=float)
@@ -174,9 +186,22 @@ class EmuBatch(object):
         Uo = np.zeros((self.B, n_steps, self.nu + self.nk))
         a = self._args(0, n_steps, dt, None, None, X)
         a.Kproj, a.bX, a.bU, a.Uout, a.group_size = _p(Kproj), _p(bX), _p(bU), _p(Uo), group_size
+        if dts is not None:
+            dts = np.ascontiguousarray(dts, dtype=float)
+            a.dt_steps, a.dt_period = _p(dts), 0
         self.L.emu_run(self.h, ctypes.byref(a))
-        self.t1, self.t2 = self.t2 + (n_steps - 1) * dt, self.t2 + n_steps * dt
+        self._advance(n_steps, dt, dts)
         return X, Uo
+
+    def _advance(self, n_steps, dt, dts):
+        """t1, t2 after a rollout, as the library's advance_times: summed step by step along a by-step list."""
+        if dts is None:
+            self.t1, self.t2 = self.t2 + (n_steps - 1) * dt, self.t2 + n_steps * dt
+            return
+        t = tp = self.t2
+        for k in range(n_steps):
+            tp, t = t, t + float(dts[k])
+        self.t1, self.t2 = tp, t
 
     def dynamics(self, Q, dQ, U=None, ddK=None):
         """Continuous dynamics of every trajectory: returns (ddq [B][nd], lambda [B][nc], status [B])."""
@@ -260,8 +285,5 @@ class EmuBatch(object):
             dts = np.ascontiguousarray(dts, dtype=float)
             a.dt_steps, a.dt_period = _p(dts), 0
         self.L.emu_run(self.h, ctypes.byref(a))
-        if dts is None:
-            self.t1, self.t2 = self.t2 + (n_steps - 1) * dt, self.t2 + n_steps * dt
-        else:
-            self.t1, self.t2 = self.t2 + float(dts[:n_steps - 1].sum()), self.t2 + float(dts[:n_steps].sum())
+        self._advance(n_steps, dt, dts)
         return X

@@ -7,7 +7,8 @@ kernels, and that a trajectory that fails to converge (or sees NaN) leaves its w
 import numpy as np
 import pytest
 
-from common import (BUILDERS, D1, NO_SECOND_ORDER, PAIRS, RANGE_CASES, TEAM_CELLS, build, golden, relerr, trajectories)
+from common import (BUILDERS, D1, NO_SECOND_ORDER, RANGE_CASES, TEAM_CELLS, build, relerr)
+from common import oracle_hz as _oracle_hz, starts as _starts
 from oracle.oracle import OracleError, OracleMVI
 from test_parameters_cpu import random_rows, rebuilt
 from trep_amd import BatchMidpointVI, _lib, descriptor
@@ -50,49 +51,6 @@ def _assert_generic(mvi, modes):
         assert (info["generic_launch_mask"] >> bit) & 1 and not (info["spec_launch_mask"] >> bit) & 1, (m, info)
         if m in BatchMidpointVI.MODES:
             assert m in info["generic_launched"] and m not in info["spec_launched"], (m, info)
-
-
-def _starts(name, d, B, N, rng, extra=0):
-    """B starts (Q[k], Q[k+1]) of recorded trajectories at random k and the recorded inputs from there on (N + extra steps); forces
-    get noise and unconstrained systems a random shift of the dynamic configs, so that every team of a wave has its own path."""
-    g = golden(name)
-    trajs = trajectories(name)
-    nd, nu = d.n_dyn, d.n_inputs
-    Q0, Q1, U, K = [], [], [], []
-    for b in range(B):
-        pre, _, u, kk = trajs[int(rng.integers(len(trajs)))]
-        Q = g[pre + "Q"]
-        k = int(rng.integers(0, len(Q) - N - extra - 2))
-        q0, q1 = Q[k].copy(), Q[k + 1].copy()
-        if d.n_constraints == 0:
-            shift = 0.2 * rng.standard_normal(nd)
-            q0[:nd] += shift
-            q1[:nd] += shift
-        uu = u[k + 1:k + 1 + N + extra]
-        Q0.append(q0)
-        Q1.append(q1)
-        U.append(uu + 0.5 * rng.standard_normal(uu.shape) if nu else uu)
-        K.append(kk[k + 1:k + 1 + N + extra])
-    return np.array(Q0), np.array(Q1), np.array(U).reshape(B, N + extra, nu), np.array(K).reshape(B, N + extra, d.n_kin)
-
-
-def _oracle_hz(o, d, z, zl):
-    """sum_o z[o] q2_dAdB[o] + z[nq + o] p2_dAdB[o] (+ zl[c] l1_dAdB[c]) from the oracle's full second-derivative tensors."""
-    nq, nd, nu, nk, nc = d.n_configs, d.n_dyn, d.n_inputs, d.n_kin, d.n_constraints
-    sizes = {"dq1": nq, "dp1": nd, "du1": nu, "dk2": nk}
-    offs = {"dq1": 0, "dp1": nq, "du1": nq + nd, "dk2": nq + nd + nu}
-    R = nq + nd + nu + nk
-    H = np.zeros((R, R))
-    for pair in PAIRS:
-        a, b = pair[:3], pair[3:]
-        if not sizes[a] or not sizes[b]:
-            continue
-        blk = o.deriv2("q2_" + pair) @ z[:nd] + o.deriv2("p2_" + pair) @ z[nq:nq + nd]
-        if nc:
-            blk = blk + o.deriv2("l1_" + pair) @ zl
-        H[offs[a]:offs[a] + sizes[a], offs[b]:offs[b] + sizes[b]] = blk
-        H[offs[b]:offs[b] + sizes[b], offs[a]:offs[a] + sizes[a]] = blk.T
-    return H
 
 
 def _u(A, j):

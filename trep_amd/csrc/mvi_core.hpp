@@ -212,7 +212,7 @@ enum { MODE_ROLLOUT = 0, MODE_CALC_P2 = 1, MODE_CALC_F = 2, MODE_DERIV1 = 3, MOD
 
 struct RunArgs {
     int batch, n_steps, max_iterations, mode;
-    int predictor;                         // rollout: 0 = the reference's initial guess q2 <- previous q2 (midpointvi.py:188-197), 1 = q2 + (q2 - q1)
+    int predictor;                         // rollout: 0 = the reference's initial guess q2 <- previous q2 (midpointvi.py:188-197), 1 = q2 + (q2 - q1) dt_k / dt_{k-1}
     double dt, t1, t2, tolerance;
     double *q1, *q2, *p1, *p2, *lam, *u1;  // batch state, row-major [batch][width]
     const double *U, *K;                   // [batch][n_steps][nu], [batch][n_steps][nk]
@@ -5268,10 +5268,15 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
         // advance: q1 <- q2, (p1 already holds p2), inputs, kinematic targets, hints (midpointvi.py:188-197)
         if (on) {
             if (A.predictor) {   // opt-in warm start: constant-velocity extrapolation of the dynamic configs
+                // constant velocity, not constant displacement: on a non-uniform time base the last displacement is scaled by
+                // dt_k / dt_{k-1}.  A ratio of exactly 1 keeps the expression the uniform grid always had; step 0 compares with t2 - t1,
+                // a rounded difference after an earlier rollout, and may take the other one (equal within rounding)
+                const double dt_in = step == 0 ? (A.t2 - A.t1) : dt_prev;
+                const double ratio = dt_in != 0.0 ? dt / dt_in : 1.0;
                 TG_FOR(i, nq) {
                     const double prev = S[P.o_q1 + i], cur = S[P.o_q2 + i];
                     S[P.o_q1 + i] = cur;
-                    if (i < nd) S[P.o_q2 + i] = 2.0 * cur - prev;
+                    if (i < nd) S[P.o_q2 + i] = ratio == 1.0 ? 2.0 * cur - prev : cur + (cur - prev) * ratio;
                 }
             } else {
                 TG_FOR(i, nq) S[P.o_q1 + i] = S[P.o_q2 + i];

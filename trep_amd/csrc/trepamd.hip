@@ -7,6 +7,7 @@
 // Trajectories are independent, so there is no inter-workgroup communication at all.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -697,6 +698,7 @@ int tg_batch_step(tg_batch *b, double t2_new, const double *u1_host, const doubl
         if (want_lh) std::memcpy(hl, lambda_hint_host, B * P.nc * sizeof(double));
         tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
         A.n_steps = 1; A.dt = t2_new - b->t2; A.max_iterations = max_iterations;
+        if (!A.dt_period) A.dt_steps = nullptr;      // a by-step list belongs to the rollouts: one step takes the caller's size
         A.U = du; A.K = dk;
         A.q2_hint = q2_hint_host ? dq : nullptr;
         A.lam_hint = want_lh ? dl : nullptr;
@@ -714,6 +716,7 @@ int tg_batch_step(tg_batch *b, double t2_new, const double *u1_host, const doubl
     if (want_lh) HIP_TRY(hipMemcpyAsync(b->stage_lh, lambda_hint_host, B * P.nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
     A.n_steps = 1; A.dt = t2_new - b->t2; A.max_iterations = max_iterations;
+    if (!A.dt_period) A.dt_steps = nullptr;      // a by-step list belongs to the rollouts: one step takes the caller's size
     A.U = b->stage_u; A.K = b->stage_k;
     A.q2_hint = q2_hint_host ? b->stage_qh : nullptr;
     A.lam_hint = want_lh ? b->stage_lh : nullptr;
@@ -739,23 +742,38 @@ static int advance_times(tg_batch *b, int n_steps, double dt) {
 
 int tg_batch_set_step_sizes(tg_batch *b, int32_t count, const double *dt_host, int32_t by_trajectory) {
     if (!b || count < 0 || (count > 0 && !dt_host)) return fail(TG_ERR_INVALID, "bad arguments");
+    // validate first: a refused list leaves the batch's current one in place
+    for (int i = 0; i < count; i++) {
+        if (dt_host[i] == 0.0) return fail(TG_ERR_INVALID, "zero step size");
+        if (!std::isfinite(dt_host[i])) return fail(TG_ERR_INVALID, "step size is not finite");
+    }
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));          // a launch in flight may still read the old list
-    if (b->dt_dev) { HIP_TRY(hipFree(b->dt_dev)); b->dt_dev = nullptr; }
-    b->dt_host.clear();
-    b->dt_by_trajectory = 0;
-    if (count == 0) return TG_SUCCESS;
-    for (int i = 0; i < count; i++) if (dt_host[i] == 0.0) return fail(TG_ERR_INVALID, "zero step size");
-    HIP_TRY(hipMalloc(&b->dt_dev, sizeof(double) * (size_t)count));
-    HIP_TRY(hipMemcpy(b->dt_dev, dt_host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice));
-    b->dt_host.assign(dt_host, dt_host + count);
-    b->dt_by_trajectory = by_trajectory ? 1 : 0;
+    double *fresh = nullptr;
+    if (count > 0) {
+        HIP_TRY(hipMalloc(&fresh, sizeof(double) * (size_t)count));
+        if (hipMemcpy(fresh, dt_host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(TG_ERR_HIP, "copy of the step-size list failed");
+        }
+    }
+    if (b->dt_dev) (void)hipFree(b->dt_dev);
+    b->dt_dev = fresh;
+    if (count > 0) b->dt_host.assign(dt_host, dt_host + count); else b->dt_host.clear();
+    b->dt_by_trajectory = (count > 0 && by_trajectory) ? 1 : 0;
     return TG_SUCCESS;
+}
+
+// a by-trajectory list belongs to one-step batches: every step of a longer rollout would take the trajectory's size while the
+// times advance by the scalar
+static bool refuse_by_trajectory(const tg_batch *b, int n_steps) {
+    return n_steps > 1 && b->dt_by_trajectory;      // (set only with a list)
 }
 
 int tg_batch_rollout(tg_batch *b, int32_t n_steps, double dt, const double *U_dev, const double *K_dev, double *X_dev,
                      int32_t max_iterations) {
     if (!b || n_steps <= 0 || dt == 0.0) return fail(TG_ERR_INVALID, "bad arguments");
+    if (refuse_by_trajectory(b, n_steps)) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
     if (!b->dt_host.empty() && !b->dt_by_trajectory && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
     const tg::DevProg &P = b->P;
     if ((P.nu && !U_dev) || (P.nk && !K_dev)) return fail(TG_ERR_INVALID, "U / K device buffers required");
@@ -773,6 +791,8 @@ int tg_batch_rollout_closed_loop(tg_batch *b, int32_t n_steps, double dt, const 
                                  int32_t max_iterations) {
     if (!b || n_steps <= 0 || dt == 0.0 || !Kproj_dev || !bX_dev || !bU_dev || group_size <= 0)
         return fail(TG_ERR_INVALID, "bad arguments");
+    if (refuse_by_trajectory(b, n_steps)) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
+    if (!b->dt_host.empty() && !b->dt_by_trajectory && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
     HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
     A.n_steps = n_steps; A.dt = dt; A.max_iterations = max_iterations;
@@ -788,6 +808,8 @@ int tg_batch_rollout_closed_loop_subset(tg_batch *b, int32_t n_trajectories, int
     if (!b || n_steps <= 0 || dt == 0.0 || !Kproj_dev || !bX_dev || !bU_dev || group_size <= 0 || n_trajectories <= 0 ||
         n_trajectories > b->batch)
         return fail(TG_ERR_INVALID, "bad arguments");
+    if (refuse_by_trajectory(b, n_steps)) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
+    if (!b->dt_host.empty() && !b->dt_by_trajectory && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
     HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
     A.batch = n_trajectories;
@@ -1106,6 +1128,7 @@ int tg_batch_set_from_trajectories(tg_batch *b, int32_t seeds, int32_t horizon, 
     b->t1 = t0; b->t2 = t0;
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
     A.n_steps = 1; A.dt = dt; A.max_iterations = max_iterations;
+    if (!A.dt_period) A.dt_steps = nullptr;      // (as in tg_batch_step)
     A.U = b->stage_u; A.K = b->stage_k; A.q2_hint = b->stage_qh;
     int rc = launch(b, A);
     if (rc) return rc;

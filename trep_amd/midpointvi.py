@@ -127,7 +127,10 @@ class BatchMidpointVI(object):
 
     def set_step_sizes(self, dts=None, by_trajectory=False):
         """Non-uniform time base (include/trep_amd.h, tg_batch_set_step_sizes): `dts` replaces the scalar dt of the rollouts
-        (step k uses dts[k]) or, with by_trajectory, of a one-step batch (trajectory t uses dts[t % len(dts)]).  None clears."""
+        (step k uses dts[k]) or, with by_trajectory, of a one-step batch (trajectory t uses dts[t % len(dts)]).  None clears.
+        A refused list (a zero or non-finite entry: LibraryError) leaves the list set before in place.  A by-step list leaves
+        step() alone; a by-trajectory list applies to every mode (calc_p2 of initialize_from_configs included: set it after) and
+        refuses rollouts of more than one step."""
         if dts is None:
             _lib.check(self._L.tg_batch_set_step_sizes(self._h, 0, None, 0))
             self._step_sizes = None
@@ -503,7 +506,7 @@ class BatchMidpointVI(object):
     @property
     def predictor(self):
         """Initial guess of the rollouts' Newton iteration: "reference" (q2 <- previous q2, the reference's semantics
-        and iteration counts) or "extrapolate" (q2 + (q2 - q1): same trajectory to solver tolerance, fewer iterations)."""
+        and iteration counts) or "extrapolate" (q2 + (q2 - q1) dt_k / dt_{k-1}: same trajectory to solver tolerance, fewer iterations)."""
         return getattr(self, "_predictor", "reference")
 
     @predictor.setter
