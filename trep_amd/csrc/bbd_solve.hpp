@@ -19,11 +19,7 @@ __device__ __forceinline__ double bbd_bcast(double v) {
 // a += l * (lane K's b)
 template <int K>
 __device__ __forceinline__ void bbd_fmac(double &a, double b, double l) {
-#if defined(TG_BBD_ASM)
-    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(a) : "v"(b), "v"(l), "n"(K));
-#else
     a = fma(l, bbd_bcast<K>(b), a);
-#endif
 }
 
 // One Gauss-Jordan step on column K of a row-per-lane block held in registers a[0 .. NCOL): every lane of a 16-lane row except
@@ -67,24 +63,13 @@ __device__ __forceinline__ BbdRows<NGB> bbd_rows(const int *tab_generic, int lan
     return t;
 }
 
-// The Newton update applied by the solver's own lanes (rollout kernels): the lane that forms x_i also forms q2_i - x_i and the rate
-// (q2_i - q1_i) / dt, or lambda_c - x_{nd + c} -- as a phase of its own the update is an LDS round trip and a barrier behind the solve.
-// nd = 0: no update (the solutions only go to the image's right-hand-side column, where every caller can read them).
-// The LDS offsets of the operands relative to the image are compile-time (BbdUpd: q2, q1, dq, lambda1 minus the image's offset; ND = 0: no
-// update -- the solutions only go to the image's right-hand-side column, where every caller can read them); only dt and 1 / dt travel.
-#if defined(TG_BBD_INLINE)      // (A/B switch: the structured solve inlined into its caller instead of an out-of-line call with its own register allocation)
-#define TG_BBD_ATTR __forceinline__
-#else
-#define TG_BBD_ATTR __noinline__
-#endif
-template <int ND_, int Q2_, int Q1_, int DQ_, int LAM_> struct BbdUpd { static constexpr int nd = ND_, q2 = Q2_, q1 = Q1_, dq = DQ_, lam = LAM_; };
-typedef BbdUpd<0, 0, 0, 0, 0> BbdNoUpdate;
 // Where the solver finds its rows: the dense image [NF][LD] (gathered by the plan tables), or the image in its own order (bbd.hpp,
 // BbdPacked): row r of group g at (g * NR + r) * NC2, trailing row i at TB + i * TC2, solutions to XS + variable
 struct BbdDenseImage { static constexpr bool packed = false; static constexpr int nr = 0, nc2 = 0, tb = 0, tc2 = 0, xs = 0; };
 template <int NR_, int NC2_, int TB_, int TC2_, int XS_> struct BbdPackedImage { static constexpr bool packed = true; static constexpr int nr = NR_, nc2 = NC2_, tb = TB_, tc2 = TC2_, xs = XS_; };
-template <int NF, int LD, int NG, int NB, int T, class UP = BbdNoUpdate, class IMG = BbdDenseImage, class TVAR = const int *>
-__device__ TG_BBD_ATTR bool gj_bbd(double *A_generic, BbdRows<NG + NB> rows, double *scratch_generic, int lane, TVAR tvar, double up_dt = 0.0, double up_inv_dt = 0.0) {
+// Out of line: the solve keeps its own register allocation (inlined into the rollout: 137 instead of 107 SGPR spills, +2 %).
+template <int NF, int LD, int NG, int NB, int T, class IMG = BbdDenseImage, class TVAR = const int *>
+__device__ __noinline__ bool gj_bbd(double *A_generic, BbdRows<NG + NB> rows, double *scratch_generic, int lane, TVAR tvar) {
     typedef __attribute__((address_space(3))) double lds_double;
     lds_double *A = (lds_double *)A_generic, *U = (lds_double *)scratch_generic, *XT = U + T * (T + 1);
     constexpr int NCOL = NG + NB + 1, UL = T + 1;
@@ -99,15 +84,6 @@ __device__ TG_BBD_ATTR bool gj_bbd(double *A_generic, BbdRows<NG + NB> rows, dou
 #pragma unroll
     for (int j = 0; j < NG + NB; j++) wc[j] = rows.wc[j];
     // ---- stage 0: registers.  own rows: everything; border rows: the own columns only (the rest accumulates the Schur update)
-    // operands of the fused update, requested with the rows (the variable of this lane: an own row's, or -- lanes < T -- trailing variable `lane`)
-    // (a lane can hold two variables: an own row of its group, always a config, and -- lanes < T -- trailing variable `lane`)
-    const bool ut_cfg = lane < T && timg < UP::nd, ut_lam = lane < T && timg >= UP::nd, uo = r < NG && row >= 0;
-    double ut_q2 = 0.0, ut_q1 = 0.0, ut_lam_v = 0.0, uo_q2 = 0.0, uo_q1 = 0.0;
-    if constexpr (UP::nd > 0) {
-        const int ci = ut_cfg ? timg : 0, li = ut_lam ? timg - UP::nd : 0, oi = uo ? row : 0;
-        ut_q2 = A[UP::q2 + ci]; ut_q1 = A[UP::q1 + ci]; ut_lam_v = A[UP::lam + li];
-        uo_q2 = A[UP::q2 + oi]; uo_q1 = A[UP::q1 + oi];
-    }
     double a[NCOL];
     const bool own = r < NG, have = row >= 0;
     const int ro = (have ? row : 0) * LD;
@@ -184,11 +160,7 @@ __device__ TG_BBD_ATTR bool gj_bbd(double *A_generic, BbdRows<NG + NB> rows, dou
         bad = bad || !(fabs(trp) * (GUARD * tmax) < 1.0);
         if (tl) XT[lane] = tr[T] * trp;
     }
-#if !defined(TG_MOCK_TIMING)      // (timing mock, mvi_core.hpp: the guards are evaluated and ignored)
     if (__any(bad ? 1 : 0)) return false;
-#else
-    asm volatile("" :: "v"(bad ? 1 : 0));
-#endif
     asm volatile("" ::: "memory");
     // ---- stage 3: solutions.  trailing variables straight, own variables by back-substitution from the border's
     const double xt = tr[T] * trp;
@@ -203,12 +175,6 @@ __device__ TG_BBD_ATTR bool gj_bbd(double *A_generic, BbdRows<NG + NB> rows, dou
         }
         xo = s * myrp;
         A[IMG::packed ? IMG::xs + row : ro + NF] = xo;
-    }
-    if constexpr (UP::nd > 0) {
-        auto rate = [&](double v, double q1v) { const double d = v - q1v, q = d * up_inv_dt; return fma(fma(-q, up_dt, d), up_inv_dt, q); };   // Core::over_dt
-        if (ut_cfg) { const double v = ut_q2 - xt; A[UP::q2 + timg] = v; A[UP::dq + timg] = rate(v, ut_q1); }
-        if (ut_lam) A[UP::lam + timg - UP::nd] = ut_lam_v - xt;
-        if (uo) { const double v = uo_q2 - xo; A[UP::q2 + row] = v; A[UP::dq + row] = rate(v, uo_q1); }
     }
     __syncthreads();
     BBD_STAMP(5);

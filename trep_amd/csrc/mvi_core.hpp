@@ -23,6 +23,18 @@
 #include "program.hpp"
 #include "dual.hpp"
 
+// Retired experiment switches: the A/B variants and timing mocks of rounds 3-5, measured, rejected and removed.  A build that still
+// passes one would be the default kernel under a variant's name, so it stops here.
+#if defined(TG_MOCK_TIMING) || defined(TG_MOCK_REAL_LDS) || defined(TG_MOCK_LDS_D1) || defined(TG_MOCK_LDS_D2) || \
+    defined(TG_BBD_FUSED_UPDATE) || defined(TG_BBD_INLINE) || defined(TG_BBD_ASM) || \
+    defined(TG_WEV_NO_RC_IDENT) || defined(TG_WEV_CLEAR_EARLY) || defined(TG_WEV_MERGE_C) || \
+    defined(TG_NO_BBD) || defined(TG_NO_CMP) || defined(TG_NO_GJ_PANEL) || defined(TG_NO_QUAD_SWEEP) || defined(TG_NO_DUAL_SWEEP) || \
+    defined(TG_NO_AB_MFMA) || defined(TG_NO_HZ_MFMA) || defined(GJR_EXEC32) || defined(GJP_SKIP_STEPS) || defined(GJP_SKIP_UPDATE) || \
+    defined(TG_FRESH_PHASES) || defined(TG_FRESH_STEP) || \
+    defined(TG_CHAIN_PRIO) || defined(TG_PREFIX_GROUP) || defined(TG_LT_TRIPS) || defined(TG_ROLLOUT_WAVES) || defined(TG_DERIV_WAVES)
+#error "a retired experiment switch is defined (TG_MOCK_*, TG_BBD_FUSED_UPDATE / _INLINE / _ASM, TG_WEV_*, TG_NO_* except TG_NO_WEV, GJR_ / GJP_*, TG_FRESH_*, or a former -D tunable): these variants were removed -- verdicts in docs/LOG.md, their source in commit 89f6ce0"
+#endif
+
 #if defined(__HIPCC__)
 #define TG_HD __host__ __device__ __forceinline__
 // Phase boundary.  Lanes of a team exchange data through LDS only, so the fence is restricted to the LDS address
@@ -99,16 +111,10 @@ __device__ __forceinline__ int tg_opaque(int x) { asm volatile("" : "+v"(x)); re
 #else
 inline int tg_opaque(int x) { return x; }
 #endif
-#ifndef TG_CHAIN_PRIO
-#define TG_CHAIN_PRIO 2     // wave priority inside the two longest serial chains (structured solve, chain rounds): the wave that is on one wins
-                            // the SIMD's issue slots against a neighbour in a wide phase (-0.8 %; 3 and a third raised phase measured: no better)
-#endif
-#ifndef TG_PREFIX_GROUP
-#define TG_PREFIX_GROUP 5
-#endif
-#ifndef TG_LT_TRIPS
-#define TG_LT_TRIPS 4
-#endif
+constexpr int TG_CHAIN_PRIO = 2;    // wave priority inside the two longest serial chains (structured solve, chain rounds): the wave that is on one wins
+                                    // the SIMD's issue slots against a neighbour in a wide phase (-0.8 %; 3 and a third raised phase measured: no better)
+constexpr int TG_PREFIX_GROUP = 5;
+constexpr int TG_LT_TRIPS = 4;
 #define TG_FOR(idx, n) for (int idx = tg_opaque(lane); idx < (n); idx += TEAM)
 // the same over all the waves of a trajectory (helper-wave kernels; `wave` is 0 and `nw` 1 everywhere else)
 #define TG_FORW(idx, n) for (int idx = tg_opaque(lane + TEAM * wave); idx < (n); idx += TEAM * nw)
@@ -195,7 +201,7 @@ template <class P> struct tg_static_cmp<P, typename std::enable_if<(P::cmp_ok >=
 
 // ... and the world-frame evaluation of the rollout's residual (program.hpp, wev_*; -DTG_NO_WEV keeps the (body, config) item phases)
 template <class P, class = void> struct tg_static_wev { static constexpr bool value = false; };
-#if !defined(TG_NO_WEV) && !defined(TG_NO_CMP)
+#if !defined(TG_NO_WEV)
 template <class P> struct tg_static_wev<P, typename std::enable_if<(P::wev_ok >= 0)>::type> { static constexpr bool value = P::wev_ok != 0 && P::cmp_ok != 0 && P::tab_ok != 0; };
 #endif
 
@@ -204,7 +210,7 @@ template <class P> struct tg_static_wev<P, typename std::enable_if<(P::wev_ok >=
 // against the dense image on one box: 30.33 against 30.07 ms at a 12-double row stride, 30.44 against 30.15 at the conflict-free 14 --
 // one percent SLOWER either way, so the dense image stays the default (tests/test_gpu_parity.py builds and checks the packed variant).
 template <class P, class = void> struct tg_static_pk { static constexpr bool value = false; };
-#if defined(TG_BBD_PACKED) && !defined(TG_NO_BBD)
+#if defined(TG_BBD_PACKED)
 template <class P> struct tg_static_pk<P, typename std::enable_if<(P::bbd_pk_ok >= 0)>::type> { static constexpr bool value = P::bbd_pk_ok != 0 && tg_static_wev<P>::value && tg_static_bbd<P>::value; };
 #endif
 
@@ -269,37 +275,32 @@ template <class ARGS> TG_HD int tg_remap_trajectory(const ARGS &A, int i) {
 }
 
 // The kernels read the schedule (DevProg) and the launch arguments (RunArgs) through CONSTANT-address-space references:
-// every field access is then a scalar load from the kernel-argument segment.  Left alone the optimiser hoists all of those
-// loop-invariant loads to the kernel prologue and keeps ~150 values alive in SGPRs for the whole rollout -- far more than
-// the 100 or so there are, so it spills them into VGPR lanes and re-reads them with v_readlane at every use (1 267
-// v_readlane + 372 v_writelane in the round-1 rollout kernel, next to 820 fp64 instructions).  tg_fresh() launders the
-// struct's address through an empty asm at the head of every phase: the loads cannot move above it, a phase loads the few
-// fields it needs when it starts (K$-resident, issued back to back) and nothing stays alive across phases.
+// every field access is then a scalar load from the kernel-argument segment (generic kernels) or an immediate (specialised
+// kernels: the schedule's integers are static members).  Left alone the optimiser hoists the loop-invariant loads of the
+// launch arguments to the kernel prologue and keeps them alive in SGPRs for the whole rollout, more than there are, so it
+// spills them into VGPR lanes.  tg_fresh_args() launders the address of the in-memory arguments of a specialised kernel
+// (KArgs) through an empty asm at the head of every step: the loads cannot move above it, a step loads the few fields it
+// needs when it starts (K$-resident) and nothing stays alive across steps.  By-value arguments pass through unchanged.
+// (Laundering the schedule's address the same way, per phase or per step, was measured and removed: docs/LOG.md.)
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) DevProg CProg;
 typedef const RunArgs CArgs;   // by-value kernel argument (few fields are used inside the loops)
 template <class T> __device__ __forceinline__ T &tg_fresh_always(T &r) { T *p = &r; asm volatile("" : "+s"(p)); return *p; }
-#if defined(TG_FRESH_PHASES)
-template <class T> __device__ __forceinline__ T &tg_fresh(T &r) { return tg_fresh_always(r); }
-#else
-template <class T> __device__ __forceinline__ T &tg_fresh(T &r) { return r; }
-#endif
-#if defined(TG_FRESH_STEP)
-template <class T> __device__ __forceinline__ T &tg_fresh_step(T &r) { return tg_fresh_always(r); }
-#else
-template <class T> __device__ __forceinline__ T &tg_fresh_step(T &r) { return r; }
-#endif
 // launch arguments read through a constant-address-space reference (specialised kernel: RunArgs in device memory)
 typedef const __attribute__((address_space(4))) RunArgs KArgs;
 __device__ __forceinline__ KArgs &tg_fresh_args(KArgs &r) { return tg_fresh_always(r); }
 template <class T> __device__ __forceinline__ T &tg_fresh_args(T &r) { return r; }
+// The identity, as an inlined call.  The rollout's step loop and Newton loop take their schedule reference through it: bound directly
+// (`PROG &P = P0`) the rollout kernels with run-time schedules or small teams come out with another scalar register allocation
+// (docs/LOG.md, "Retired switches": 4 238 differing lines in the generic parameter object).  Nothing else needs it.
+// TODO: remove it, and the dead bbd_updated test in run_trajectory, in the first change that is allowed to alter the generic kernels' code.
+template <class T> __device__ __forceinline__ T &tg_rebind(T &r) { return r; }
 #else
 typedef const DevProg CProg;
 typedef const RunArgs CArgs;
 typedef const RunArgs KArgs;
 template <class T> inline T &tg_fresh_args(T &r) { return r; }
-template <class T> inline T &tg_fresh(T &r) { return r; }
-template <class T> inline T &tg_fresh_step(T &r) { return r; }
+template <class T> inline T &tg_rebind(T &r) { return r; }
 #endif
 
 // sin and cos together for joint angles.  |x| < 2^17: three-constant Cody-Waite reduction to [-pi/4, pi/4]
@@ -528,23 +529,18 @@ struct Core {
     // (12 * first joint | chain length << 16) and 12 * parent joint (or -1: the world), length 0 for an empty slot.
     // Keeps global-memory look-ups (and their latency) out of the sweep.
     TG_HD void init_sweep_schedule(bool rollout = false) {
-        PROG &P = tg_fresh(this->P);
         if constexpr (PAR) { TG_FOR(i, 4 * P.n_bodies) S[P.o_I + i] = par[i - 4 * P.n_bodies]; }   // (the row's inertia block)
         else TG_FOR(i, 4 * P.n_bodies) S[P.o_I + i] = P.b_inertia[i];   // body inertias: LDS copy for the whole kernel
         TG_FOR(c, P.nc) S[P.o_ctol + c] = P.c_tol[c];
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_BBD)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (TEAM == 64 && tg_static_bbd<typename std::remove_cv<PROG>::type>::value) {
             // plan tables of the structured Newton solve (bbd.hpp): staged once per rollout kernel behind the base region
             if (rollout) { int *tab = (int *)(S + P.o_bbd); TG_FOR(i, 128) tab[i] = P.bbd_tab[i]; }
         }
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_CMP)
         if constexpr (TEAM == 64 && !SPRINGS && tg_static_cmp<typename std::remove_cv<PROG>::type>::value) {
             // composite Newton matrix: representative item | its body << 12 | subtree group << 20 of every dynamic config
             if (rollout) { int *tab = (int *)(S + P.o_cmpt); TG_FOR(i, P.nd) { const int it = P.cmp_rep[i]; tab[i] = it | (P.it_pack[4 * (size_t)it] << 12) | (P.cmp_grp[i] << 20); } }
         }
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
         if (TEAM == 64 && P.tab_ok) {
             // Lane order of the 2 x n_joints (pose set, joint) items of the sin/cos pass: the rotary joints of both pose sets first,
             // then the prismatic ones -- so that the second trip of the wavefront (puppet: 68 items, 38 of them rotary) has no
@@ -615,7 +611,6 @@ struct Core {
     }
 
     TG_HD void pose_sweep(bool on, int sel) {
-        PROG &P = tg_fresh(this->P);
         Real *sc = S + P.o_sc, *G = S + P.o_G;
         if (on) TG_FOR(j, P.n_joints) {
             const Real x = qval(sel, P.j_cfg[j]);
@@ -715,7 +710,6 @@ struct Core {
     // the Jacobians / prefix velocities are formed), every chain lane carries the two row recurrences side by side
     // (two independent FMA chains per lane), and the local-transform pass covers 2 x 12 x n_joints entries.
     TG_HD void pose_sweep_dual(bool on, bool rollout_lists) {
-        PROG &P = tg_fresh(this->P);
         const int sjn = rollout_lists ? P.n_sj : 2 * P.n_joints;     // (what init_sweep_schedule filled jck from)
         double *sc = S + P.o_sc, *sc2 = S + P.o_J, *G = S + P.o_G, *G2 = S + P.o_W;
         const int nj = P.n_joints;
@@ -723,13 +717,11 @@ struct Core {
         // coefficient rows of local-transform entry idx2 (of the 2 x 12 x n_joints of both pose sets; clamped past the end).  They
         // come from global memory (hundreds of cycles), so every trip's rows are requested one trip ahead -- the first
         // trip's before the sin/cos pass, which does not need them.
-#if !defined(TG_NO_QUAD_SWEEP)
         // quad-lane chain rounds (chain_round_quads): the lane's instance of every pass of the first round, requested a phase ahead
         SwDesc sw0;
         if constexpr (tg_static_sweep<typename std::remove_cv<PROG>::type>::value) {
             if (rollout_lists) sw0 = sw_fetch<typename std::remove_cv<PROG>::type, 0>((const int *)(S + P.o_sched));
         }
-#endif
         if (P.tab_ok) {
             // One lane per (pose set, joint): sin / cos of the joint coordinate AND the joint's local transform pre_j lg(q) in the same
             // phase.  With the pre-transform's columns in the order (axis a, b = a + 1, c = a + 2, translation) -- rows (A, B, C, D) of
@@ -828,7 +820,6 @@ struct Core {
         TG_STAMP(15);
         }
         const int *sched = (const int *)(S + P.o_sched);
-#if !defined(TG_NO_QUAD_SWEEP)
         if constexpr (tg_static_sweep<typename std::remove_cv<PROG>::type>::value) {
             if (rollout_lists) {     // (the instance plan lists the chains the ROLLOUT reads; the derivative kernels sweep every chain below)
                 typedef typename std::remove_cv<PROG>::type SP;
@@ -838,7 +829,6 @@ struct Core {
                 return;
             }
         }
-#endif
         if (P.sched_ok == 2) {
             // at most 8 chains per round: lanes 0-31 sweep the midpoint poses, lanes 32-63 the q2 poses -- one row recurrence
             // per lane, so the instruction stream of a chain step is half that of two recurrences side by side
@@ -952,7 +942,6 @@ struct Core {
     // round's are requested before this round's columns: no LDS round trip between "which chain" and "its transforms")
     template <class SP, int RD> TG_HD void chain_round_quads(bool on, const int *sched, const SwDesc &d) {
         if constexpr (RD < SP::n_rounds) {
-            PROG &P = tg_fresh(this->P);
             constexpr int NP = SP::sw_np[RD], ML = SP::sw_maxlen;
             SwDesc nxt = d;
             if constexpr (RD + 1 < SP::n_rounds) nxt = sw_fetch<SP, RD + 1>(sched);
@@ -1005,7 +994,6 @@ struct Core {
 
     // eval_midpoint followed by eval_constraints(on, 2, true, Dh2) with the two pose sweeps fused
     TG_HD void eval_both(bool on) {
-        PROG &P = tg_fresh(this->P);
         if (on) TG_FOR(i, P.nq) S[P.o_dq + i] = (S[P.o_q2 + i] - S[P.o_q1 + i]) / dt;
         TG_SYNC();
         TG_STAMP(0);
@@ -1106,7 +1094,6 @@ struct Core {
     }
     TG_HD void eval_both_tab(bool on) {
         constexpr bool VJ = tg_items_aligned<typename std::remove_cv<PROG>::type>::value;
-        PROG &P = tg_fresh(this->P);
         const AttachTab at = fetch_attach();
         if (!rates_ready) {      // (the rollout forms the rates in its step set-up and in the Newton update)
             if (on) TG_FOR(i, P.nq) S[P.o_dq + i] = (S[P.o_q2 + i] - S[P.o_q1 + i]) / dt;
@@ -1365,7 +1352,6 @@ struct Core {
         constexpr int nd = SP::nd, NB = SP::n_bodies, NG = SP::n_cgroups, MAXD = SP::wev_depth;
         static_assert(TEAM == 64 && nd + 3 * NB < 64, "eval_world: one lane per config and per (body, axis), and the last lane free");
         static_assert((SP::o_csw & 1) == 0 && (SP::o_I & 1) == 0 && (SP::o_cmp & 1) == 0 && (SP::o_G & 1) == 0, "eval_world: 16-byte LDS accesses");
-        PROG &P = tg_fresh(this->P);
         // table rows of E3, requested ahead of the pose sweep: the end point's anchor row (as fetch_attach), the body lane's constant offset
         const int l0 = tg_opaque(lane);
         const bool blane = l0 >= nd && l0 < nd + 3 * NB;
@@ -1439,11 +1425,7 @@ struct Core {
                 }
                 // world pose of the body: R = Ra Rc, p = Ra pc + pa (Rc = 1 for every body of most models -- the masses sit at translated frames:
                 // a compile-time property of the schedule, wev_rc_ident)
-#if defined(TG_WEV_NO_RC_IDENT)
-                constexpr bool RCI = false;
-#else
                 constexpr bool RCI = SP::wev_rc_ident != 0;
-#endif
                 double R[3][3], p[3];
 #pragma unroll
                 for (int i = 0; i < 3; i++) {
@@ -1545,20 +1527,7 @@ struct Core {
         }
         TG_SYNC();
         TG_STAMP(6);
-        // ---- E5: composites of the subtree groups (lane = entry; membership is compile-time).  The union of poses and Newton image is dead
-        //      from here to the next evaluation (its last readers were the constraint lanes of E4): the image is cleared here, by lanes
-        //      that would idle, instead of at the head of the assembly (wasted by a step's last evaluation: one in four)
-        {
-            typedef double tg_d2 __attribute__((ext_vector_type(2)));
-            static_assert(((SP::o_Df | (SP::nf * SP::df_ld)) & 1) == 0, "eval_world: image not 16-byte aligned");
-            tg_d2 *A2 = reinterpret_cast<tg_d2 *>(S + P.o_Df);
-            const tg_d2 z2 = {0.0, 0.0};
-#if defined(TG_WEV_CLEAR_EARLY)
-            if (on) TG_FOR(i, (SP::nf * SP::df_ld) >> 1) A2[i] = z2;
-#else
-            (void)A2; (void)z2;
-#endif
-        }
+        // ---- E5: composites of the subtree groups (lane = entry; membership is compile-time)
         if (on && lane < 16) {
 #pragma unroll
             for (int g = 0; g < NG; g++) {
@@ -1570,11 +1539,10 @@ struct Core {
         }
         TG_SYNC();
         TG_STAMP(3);
-        // ---- E6: L_dq, L_ddq and the residual entry of config k; and, from the same operands, what the Newton matrix's pair lanes need of
-        //      config k: I s_k, Z_k = Y_k + I w_k, GG_k (phase C of newton_matrix_composite; one evaluation in four does not use them) ----
+        // ---- E6: L_dq, L_ddq and the residual entry of config k ----
         if (on && lane < nd) {
             const double *c = CMP + 16 * ((wvl[3] >> 24) & 0x7F);
-            const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3], Dxx = c[4], Dxy = c[5], Dxz = c[6], Dyy = c[7], Dyz = c[8], Dzz = c[9];
+            const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3];
             const double h0 = c[10], h1 = c[11], h2 = c[12], h3 = c[13], h4 = c[14], h5 = c[15];
             double sk[6];
             ld6<true>(SW + 12 * lane, sk);
@@ -1597,29 +1565,6 @@ struct Core {
             }
             S[P.o_f + i] = f;
             res_f2 = f * f;
-#if defined(TG_WEV_MERGE_C)
-            auto apply = [&](const double *x, double *y) {      // spatial inertia times twist
-                y[0] = M * x[0] - (Cy * x[5] - Cz * x[4]); y[1] = M * x[1] - (Cz * x[3] - Cx * x[5]); y[2] = M * x[2] - (Cx * x[4] - Cy * x[3]);
-                y[3] = (Cy * x[2] - Cz * x[1]) + Dxx * x[3] + Dxy * x[4] + Dxz * x[5];
-                y[4] = (Cz * x[0] - Cx * x[2]) + Dxy * x[3] + Dyy * x[4] + Dyz * x[5];
-                y[5] = (Cx * x[1] - Cy * x[0]) + Dxz * x[3] + Dyz * x[4] + Dzz * x[5];
-            };
-            double Is[6], Iw[6];
-            apply(sk, Is); apply(w, Iw);
-            const double b0 = sk[0], b1 = sk[1], b2 = sk[2], b3 = sk[3], b4 = sk[4], b5 = sk[5];
-            double Z[6];
-            Z[0] = Iw[0] + (b4 * h2 - b5 * h1); Z[1] = Iw[1] + (b5 * h0 - b3 * h2); Z[2] = Iw[2] + (b3 * h1 - b4 * h0);
-            Z[3] = Iw[3] + (b1 * h2 - b2 * h1) + (b4 * h5 - b5 * h4);
-            Z[4] = Iw[4] + (b2 * h0 - b0 * h2) + (b5 * h3 - b3 * h5);
-            Z[5] = Iw[5] + (b0 * h1 - b1 * h0) + (b3 * h4 - b4 * h3);
-            double *o = S + P.o_ccz + 15 * lane;
-#pragma unroll
-            for (int r = 0; r < 6; r++) { o[r] = Is[r]; o[6 + r] = Z[r]; }
-            o[12] = Gy * gz - Gz * gy; o[13] = Gz * gx - Gx * gz; o[14] = Gx * gy - Gy * gx;
-            st6<true>(SW + 12 * lane + 6, wev_w);        // (the u-half of the record: its readers finished two barriers ago)
-#else
-            (void)Dxx; (void)Dxy; (void)Dxz; (void)Dyy; (void)Dyz; (void)Dzz;
-#endif
         } else res_f2 = 0.0;
         TG_STAMP(4);
     }
@@ -1627,7 +1572,6 @@ struct Core {
 
     // ---- poses of the massive frames and positions of the constraint end points --------------------
     TG_HD void attach_points(bool on, bool bodies, bool endpoints) {
-        PROG &P = tg_fresh(this->P);
         const Real *G = S + P.o_G;
         // Branch-free: an unanchored frame (anchor < 0: fixed to the world) reads joint 0 and weights it out.  A branch
         // would split the loop body into basic blocks that each wait for their own loads.
@@ -1671,7 +1615,6 @@ struct Core {
 
     // ---- body Jacobian columns J_{F,k} and gravity in body coordinates ------------------------------
     TG_HD void jacobians(bool on) {
-        PROG &P = tg_fresh(this->P);
         const Real *G = S + P.o_G;
         struct JacOut { Real J[6], dq; };
         if (on) for_pairs(P.n_items, [&](int it) {
@@ -1710,7 +1653,6 @@ struct Core {
 
     // ---- prefix velocities, W_j = [P_j, J_j], body velocity v_F --------------------------------------
     TG_HD void velocities(bool on) {
-        PROG &P = tg_fresh(this->P);
         // (1) one lane per (body, twist component): serial prefix sum along the body's path,
         //     P_j = sum_{k<j} J_k dq_k written into the W slot of item j, total = body velocity;
         // (2) one lane per item: W_j = [P_j, J_j] in place.
@@ -1746,7 +1688,6 @@ struct Core {
 
     // ---- L_dq, L_ddq per config and the dynamic part of the DEL residual (midpointvi.c:533-551) -------
     TG_HD void residual_dyn(bool on) {
-        PROG &P = tg_fresh(this->P);
         // per-item terms <J,v> and <W,v> + m gam.Jv, stored in config-sorted order in the (now dead) joint
         // pose area, then one contiguous sum per dynamic config
         double *terms = S + P.o_G;
@@ -1812,7 +1753,6 @@ struct Core {
     // ---- constraint values (into f[nd..]) and Jacobian Dh (into dest) at the swept state -------------
     // distance.c:16-63, point.c:16-38.  `sel` picks the config vector for the length configs.
     TG_HD void constraints(bool on, int sel, bool want_h, Real *Dh, int ld) {
-        PROG &P = tg_fresh(this->P);
         if (on && want_h) TG_FOR(c, P.nc) {
             const Real *a = S + P.o_pE + 3 * P.c_e1[c], *b = S + P.o_pE + 3 * P.c_e2[c];
             const Real vx = a[0] - b[0], vy = a[1] - b[1], vz = a[2] - b[2];
@@ -1856,7 +1796,7 @@ struct Core {
         TG_SYNC();
     }
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_CMP)
+#if defined(__HIP_DEVICE_COMPILE__)
     // ---- Newton matrix, inertial part in COMPOSITE form (system-specialised rollout kernels of full-wave teams) -----------------------
     // newton_matrix() below walks every (body, item a <= item b) pair -- 442 for the puppet -- and evaluates L_dqdq, L_ddqdq, L_ddqddq
     // (system.c:158-202, 294-334, 459-489) of that body for that pair from its body-frame Jacobian columns.  All bodies below config b
@@ -1871,7 +1811,6 @@ struct Core {
     // body, 16 per subtree group (9) and 27 per config.  Same matrix up to rounding; the scratch lives in the J / W area, which is dead
     // between the residual and the next evaluation (the structured solve's scratch follows in the same place).
     TG_HD void newton_matrix_composite(bool on) {
-        PROG &P = tg_fresh(this->P);
         typedef typename std::remove_cv<PROG>::type SP;
         constexpr int nd = SP::nd, nf = SP::nf, ld = SP::df_ld, NB = SP::n_bodies, NG = SP::n_cgroups, NP = SP::n_cmpairs;
         constexpr int TP = (NP + TEAM - 1) / TEAM;
@@ -2031,25 +1970,21 @@ struct Core {
     // table rows; !PK: the dense image [nf][ld], which the pivoting fallback solves.  SKIPC: the per-config vectors are in place already
     // (the dense re-assembly after a failed structured solve).
     template <bool PK, bool SKIPC = false> TG_HD void newton_matrix_world(bool on) {
-        PROG &P = tg_fresh(this->P);
         typedef typename std::remove_cv<PROG>::type SP;
         constexpr int nd = SP::nd, nf = SP::nf, ld = SP::df_ld, NP = SP::n_cmpairs;
         constexpr int NCLEAR = PK ? SP::bbd_pk_size : nf * ld;
         constexpr int TP = (NP + TEAM - 1) / TEAM;
         double *A = S + P.o_Df, *SW = S + P.o_csw, *CZ = S + P.o_ccz;
         constexpr int SWS = 12;
-        // phase C: the image is cleared, per config b: I s_b, Z_b = Y_b + I w_b, GG_b (measured variants, both slower: -DTG_WEV_MERGE_C forms the per-config vectors in
-        // eval_world's last phase -- 30.4 against 30.0 ms: every evaluation then pays for them --, -DTG_WEV_CLEAR_EARLY clears the image in E5)
-#if !defined(TG_WEV_CLEAR_EARLY)
+        // phase C: the image is cleared, per config b: I s_b, Z_b = Y_b + I w_b, GG_b (both here and not in eval_world: an evaluation that
+        // converges -- one in four -- would form the vectors and clear the image in vain; measured 30.4 against 30.0 and 30.6 against 30.2 ms)
         {
             typedef double tg_d2 __attribute__((ext_vector_type(2)));
-            static_assert((NCLEAR & 1) == 0, "newton_matrix_world: image size");
+            static_assert(((SP::o_Df | NCLEAR) & 1) == 0, "newton_matrix_world: image not 16-byte aligned");
             tg_d2 *A2 = reinterpret_cast<tg_d2 *>(A);
             const tg_d2 z2 = {0.0, 0.0};
             if (on) TG_FOR(i, NCLEAR >> 1) A2[i] = z2;
         }
-#endif
-#if !defined(TG_WEV_MERGE_C)
         if (!SKIPC && on && lane < nd) {
             const double *c = S + P.o_cmp + 16 * ((wvl[3] >> 24) & 0x7F);
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3], Dxx = c[4], Dxy = c[5], Dxz = c[6], Dyy = c[7], Dyz = c[8], Dzz = c[9];
@@ -2079,7 +2014,6 @@ struct Core {
             o[12] = Gy * gz - Gz * gy; o[13] = Gz * gx - Gx * gz; o[14] = Gx * gy - Gy * gx;
             st6<true>(SW + SWS * lane + 6, wev_w);
         }
-#endif
         TG_SYNC();
         TG_STAMP(7);
         // ---- phase D: the constant entries (right-hand side, damping, -Dh1' / Dh2) and the config pairs: one lane per pair
@@ -2121,11 +2055,10 @@ struct Core {
 
     // ---- Newton matrix [Df | f] (midpointvi.c:577-670) ---------------------------------------------------
     TG_HD void newton_matrix(bool on) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_CMP)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (TEAM == 64 && !SPRINGS && tg_static_wev<typename std::remove_cv<PROG>::type>::value) { if (wev_on) { if (tg_static_pk<typename std::remove_cv<PROG>::type>::value && pk_image) newton_matrix_world<true>(on); else newton_matrix_world<false>(on); return; } }
         if constexpr (TEAM == 64 && !SPRINGS && tg_static_cmp<typename std::remove_cv<PROG>::type>::value) { newton_matrix_composite(on); return; }
 #endif
-        PROG &P = tg_fresh(this->P);
         const int nd = P.nd, nf = P.nf, ld = P.df_ld;
         double *A = S + P.o_Df;
         // zero fill, then the few structurally non-zero constant entries: damping on the diagonal
@@ -2501,9 +2434,6 @@ struct Core {
             scale = 1.0 / s;
         }
         bool ok = true;
-#if defined(GJR_EXEC32)
-        if (lane < 32)
-#endif
 #pragma unroll
         for (int k = 0; k < N; k++) {
             const float cand = (mine && mycol < 0) ? (float)fabs(row[k] * scale) : 0.0f;
@@ -2642,7 +2572,6 @@ struct Core {
             int srcs[4] = {0, 0, 0, 0};
             double b0 = 0.0, b1 = 0.0;
             const bool live0 = 4 * p + 4 < 16;
-#if !defined(GJP_SKIP_STEPS)
 #pragma unroll
             for (int t = 0; t < 4; t++) {
                 const int k = 4 * p + t;
@@ -2683,8 +2612,6 @@ struct Core {
                     scale = is_piv ? 0.0 : scale;
                 }
             }
-#endif
-#if !defined(GJP_SKIP_UPDATE)
             // 4. Z -> A-operand form; pivot rows from the LDS image (as of the panel's start); trailing update; write back
             //    (tile column 0 is dead once the panel has passed column 11)
             if (lane < 32) {
@@ -2713,7 +2640,6 @@ struct Core {
             if (live0) write_back(0);
             if (in1) write_back(1);
             lds_fence();
-#endif
         }
         // x = b / pivot, row by row: the right-hand side is column n of the image
         const double xr = A[myrow + n] * rdiag;
@@ -3002,7 +2928,7 @@ struct Core {
         TG_SYNC();
         // constraints at q1: Jacobian (held in the KKT matrix) and lambda-weighted Hessian
         if (nc) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_DUAL_SWEEP) && defined(TG_GJ_PANEL_DEFAULT)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(TG_GJ_PANEL_DEFAULT)
             // (system-specialised kernels only: with the schedule interpreted at run time the fused sweep is 5 % slower here)
             if (dual_ok()) {      // the q1 and the q2 poses in one fused sweep (second set in the W area, dead until the midpoint evaluation)
                 if (w0) {
@@ -3198,7 +3124,7 @@ struct Core {
             TG_SYNC();
         }
         TG_STAMP(8);
-#if defined(__HIP_DEVICE_COMPILE__) && defined(TG_GJ_PANEL_DEFAULT) && !defined(TG_NO_GJ_PANEL)
+#if defined(__HIP_DEVICE_COMPILE__) && defined(TG_GJ_PANEL_DEFAULT)
         // system-specialised kernels, full-wave team, 17..31 unknowns, at most 128 columns: panels of four columns with every
         // right-hand side in the rank-4 matrix-core update (sizes are compile-time constants of the specialisation header)
         {
@@ -3254,7 +3180,7 @@ struct Core {
                 const int nX = P.nX, nU = nu + nk, nqd = nq + nd;
                 double *Ao = A.A_out + t * (size_t)nX * nX, *Bo = A.B_out + t * (size_t)nX * nU;
                 bool rows_done = false;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_AB_MFMA)
+#if defined(__HIP_DEVICE_COMPILE__)
                 if (TEAM == 64 && nd <= 32) {
                     // The p2 rows are a dense product, P[o][v] = T1x[v][o] + sum_i T22[i][o] X[i][v] (nd x (nX + nU), K = nd): on the
                     // matrix cores, one v_mfma_f64_16x16x4 tile per 16 outputs x 16 variables, four tiles of a tile row side by side
@@ -4341,7 +4267,7 @@ struct Core {
                 TG_SYNC();
             }
         };
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_HZ_MFMA)
+#if defined(__HIP_DEVICE_COMPILE__)
         // ---- the same assembly on the matrix cores (full-wave teams) --------------------------------------------------
         // HZ = Y2' H22 Y2 + N + N' + D with Y2 = [X; e_k2] the q2 tangents, N = [H12 Y2 + G1 L; 0] the rows of the q1 variables and
         // D the H11 block.  Per block of 16 columns b:  TB = H22 Y2[:, b] (staged in LDS), then every 16 x 16 output tile (a, b) is ONE
@@ -4510,7 +4436,6 @@ struct Core {
 
     // team-uniform convergence test (midpointvi.c:672-689)
     TG_HD bool solved(double tolerance) const {
-        PROG &P = tg_fresh(this->P);
         // four partial sums: a single accumulator is a chain of nd dependent fp64 FMAs (~30 cycles each on this part)
         double n0 = 0.0, n1 = 0.0, n2 = 0.0, n3 = 0.0;
         int i = 0;
@@ -5028,7 +4953,6 @@ struct Core {
 
     // midpoint evaluation shared by every mode: rates, poses, Jacobians, velocities, residual
     TG_HD void eval_midpoint(bool on) {
-        PROG &P = tg_fresh(this->P);
         if (on) TG_FOR(i, P.nq) S[P.o_dq + i] = (S[P.o_q2 + i] - S[P.o_q1 + i]) / dt;
         TG_SYNC();
         TG_STAMP(0);
@@ -5100,7 +5024,7 @@ TG_HD void run_forward(PROG &P, ARGS &A, Real *S, int lane, int traj) {
 // PAR: masses / inertias, gravity and damping come from the trajectory's row of the parameter table T (ParTable) instead of the schedule
 template <int TEAM, int MODE, bool SPRINGS = false, class PROG = CProg, class ARGS = CArgs, int PIVOT = -1, bool PAR = false>
 TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int wave = 0, int nw = 1, const ParTable T = ParTable{nullptr, 1, 0}) {
-    PROG &P = tg_fresh(P0);
+    PROG &P = P0;
     ARGS &A = A0;
     const int nq = P.nq, nd = P.nd, nk = P.nk, nu = P.nu, nc = P.nc;
     const bool live = traj < A.batch;
@@ -5187,8 +5111,8 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
     double pre_u = 0.0, pre_k = 0.0;
     bool pre_ok = false;
     for (int step = 0; step < A.n_steps; step++) {
-        PROG &P = tg_fresh_step(P0);      // per step: nothing of the schedule / the arguments stays in SGPRs across steps
-        ARGS &A = tg_fresh_args(A0);
+        PROG &P = tg_rebind(P0);
+        ARGS &A = tg_fresh_args(A0);      // per step: nothing of the arguments stays in SGPRs across steps
         const int nq = P.nq, nd = P.nd, nk = P.nk, nu = P.nu, nc = P.nc, nX = P.nX;
         const double dt_prev = dt;             // step size of the step that produced the incoming state (feedback: v = dq_k / dt_prev)
         if (A.dt_steps && A.dt_period == 0) { dt = A.dt_steps[step]; core.dt = dt; core.inv_dt = 1.0 / dt; }   // non-uniform time base (dsystem.py:229-274 takes any t)
@@ -5298,7 +5222,7 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
         // Dh2 of the previous step's converged q2 (same point, same inputs), so only step 0 sweeps.
         // rates dq = (q2 - q1) / dt of the first evaluation: here (no reader before the barriers below) and, for the later evaluations, in the
         // Newton update itself -- a phase of its own at the head of every evaluation otherwise (eval_both_tab)
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_DUAL_SWEEP)
+#if defined(__HIP_DEVICE_COMPILE__)
         const bool fuse_rates = core.dual_ok() && P.tab_ok;
 #else
         const bool fuse_rates = false;
@@ -5322,9 +5246,9 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
         { long long t_ = (long long)__builtin_amdgcn_s_memtime(); core.prof[9] += t_ - core.prof_last; core.prof_last = t_; }
 #endif
         for (;;) {
-            PROG &P = tg_fresh(P0);
+            PROG &P = tg_rebind(P0);
             const int nd = P.nd, nc = P.nc;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_DUAL_SWEEP)
+#if defined(__HIP_DEVICE_COMPILE__)
             if constexpr (TEAM == 64 && !SPRINGS && tg_static_wev<typename std::remove_cv<PROG>::type>::value) { core.wev_on = true; core.pk_image = PIVOT == 0; core.eval_world(!done); }
             else if (core.dual_ok()) { if (P.tab_ok) core.eval_both_tab(!done); else core.eval_both(!done); }
             else
@@ -5333,17 +5257,11 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 core.eval_midpoint(!done);
                 core.eval_constraints(!done, 2, true, S + P.o_Dh2);
             }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_DUAL_SWEEP)
+#if defined(__HIP_DEVICE_COMPILE__)
             if (core.dual_ok() && P.tab_ok) { if (!done && core.solved_fused(A.tolerance)) done = true; }
             else
 #endif
             if (!done && core.solved(A.tolerance)) done = true;
-#if defined(TG_MOCK_TIMING)
-            // TIMING MOCK (tools/mock_third_wave.sh; never loadable by the package): the same instruction stream on numbers that may be
-            // garbage -- exactly three Newton iterations per step whatever the residual says, the structured solve's guards ignored, the
-            // iterate frozen (the update's stores go to a dead word).  Only for builds whose LDS areas are deliberately aliased.
-            done = live && !failed ? iterations >= 3 : true;
-#endif
 #if defined(TG_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
             { long long t_ = (long long)__builtin_amdgcn_s_memtime(); core.prof[12] += t_ - core.prof_last; core.prof_last = t_; }
 #endif
@@ -5354,7 +5272,7 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
 #else
             if (done) break;
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_BBD)
+#if defined(__HIP_DEVICE_COMPILE__)
             // the structured solve's table rows of this lane, requested ahead of the matrix assembly
             BbdRows<tg_static_bbd_cols<TEAM == 64 && PIVOT == 0, typename std::remove_cv<PROG>::type>::value> bbd_tab_rows;
             if constexpr (TEAM == 64 && PIVOT == 0 && tg_static_bbd<typename std::remove_cv<PROG>::type>::value)
@@ -5364,8 +5282,9 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
             bool ok;
 #if defined(__HIP_DEVICE_COMPILE__)
             const int nb4 = (P.nf + 3) >> 2;   // matrix size in blocks of 4 rows
-            bool bbd_done = false, bbd_updated = false;
-#if !defined(TG_NO_BBD)
+            bool bbd_done = false;
+            bool bbd_updated = false;      // never set: the fused update is gone, but without this dead test below the GENERIC rollout kernels
+                                           // change (docs/LOG.md, "Retired switches": 921 differing lines in the generic parameter object)
             if constexpr (TEAM == 64 && PIVOT == 0 && tg_static_bbd<typename std::remove_cv<PROG>::type>::value) {
                 // structured solve along the system's bordered-block-diagonal plan (bbd.hpp): no pivot search; a failed pivot guard
                 // leaves the image untouched and the pivoting solver below takes over (a full-wave team: done is false here and
@@ -5378,17 +5297,7 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 constexpr bool PKI = tg_static_pk<SP>::value;
                 typedef typename std::conditional<PKI, BbdPackedImage<SP::bbd_pk_nr, SP::bbd_pk_nc2, SP::bbd_pk_tb, SP::bbd_pk_tc2, SP::bbd_pk_xs>, BbdDenseImage>::type Img;
                 double *bscr = PKI ? S + P.o_W + 12 * P.n_joints : S + P.o_J;
-#if !defined(TG_BBD_FUSED_UPDATE) || defined(TG_MOCK_TIMING)
-                bbd_done = gj_bbd<SP::nf, SP::df_ld, SP::bbd_ng, SP::bbd_nb, SP::bbd_t, BbdNoUpdate, Img>(S + P.o_Df, bbd_tab_rows, bscr, lane, P.bbd_tvar);
-#else
-                // -DTG_BBD_FUSED_UPDATE (measured: 30.03 against 30.01 ms, i.e. nothing, for 2 spilled registers; off by default): the Newton update
-                // rides on the solve's last stage in the kernels whose update also forms the rates (implied by the world-frame evaluation's conditions)
-                typedef BbdUpd<SP::nd, SP::o_q2 - SP::o_Df, SP::o_q1 - SP::o_Df, SP::o_dq - SP::o_Df, SP::o_lam - SP::o_Df> Upd;
-                if constexpr (tg_static_wev<SP>::value) {
-                    bbd_done = gj_bbd<SP::nf, SP::df_ld, SP::bbd_ng, SP::bbd_nb, SP::bbd_t, Upd, Img>(S + P.o_Df, bbd_tab_rows, bscr, lane, P.bbd_tvar, core.dt, core.inv_dt);
-                    bbd_updated = bbd_done;
-                } else bbd_done = gj_bbd<SP::nf, SP::df_ld, SP::bbd_ng, SP::bbd_nb, SP::bbd_t, BbdNoUpdate, Img>(S + P.o_Df, bbd_tab_rows, bscr, lane, P.bbd_tvar);
-#endif
+                bbd_done = gj_bbd<SP::nf, SP::df_ld, SP::bbd_ng, SP::bbd_nb, SP::bbd_t, Img>(S + P.o_Df, bbd_tab_rows, bscr, lane, P.bbd_tvar);
                 if (!bbd_done) n_fallback++;
                 if constexpr (PKI) {
                     // guard failed (rare): the pivoting solver wants the dense image -- the packed one (untouched by the failed solve) unpacked
@@ -5414,11 +5323,7 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 }
                 __builtin_amdgcn_s_setprio(0);
                 ok = true;
-#if defined(TG_MOCK_TIMING)
-                bbd_done = true;
-#endif
             }
-#endif
             if (bbd_done) { }
             else if (TEAM >= 4 && 4 * nb4 <= TEAM && nb4 <= 8) {
                 double *Ad = S + P.o_Df;
@@ -5434,7 +5339,7 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 default: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 32 ? 32 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
                 }
                 } else
-#if defined(TG_GJ_PANEL_DEFAULT) && !defined(TG_NO_GJ_PANEL)
+#if defined(TG_GJ_PANEL_DEFAULT)
                 // full-wave teams, 17..31 unknowns: panels of four columns + matrix-core trailing update (scratch: the Jacobian
                 // columns, dead between the Newton matrix's assembly and the next evaluation).  System-specialised kernels only
                 // (spec_kernel.hip defines TG_GJ_PANEL_DEFAULT): with run-time sizes the panel code carries guards and address
@@ -5465,25 +5370,16 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
 #if defined(TG_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
             { long long t_ = (long long)__builtin_amdgcn_s_memtime(); core.prof[14] += t_ - core.prof_last; core.prof_last = t_; }
 #endif
-#if !defined(TG_MOCK_TIMING)
             if (!done && !ok) { done = true; failed = true; status = TG_SINGULAR; }
-#endif
-#if defined(TG_MOCK_TIMING)
-            if (!done) {      // (the same loads, operations and stores; the stores hit dead words of the scale / closed-loop input areas)
-                TG_FOR(i, nd) { const double v = S[P.o_q2 + i] - S[P.o_Df + i * P.df_ld + P.nf]; S[P.o_scal + (i & 15)] = v; S[P.o_nu + (i & 15)] = core.over_dt(v - S[P.o_q1 + i]); }
-                TG_FOR(c, nc) S[P.o_scal + 16 + c] = S[P.o_lam + c] - S[P.o_Df + (nd + c) * P.df_ld + P.nf];
-                iterations++;
-            }
-#else
             if (!done) {
 #if defined(__HIP_DEVICE_COMPILE__)
-                if (bbd_updated) { }      // (the structured solve applied the update itself)
+                if (bbd_updated) { }
                 else
 #endif
                 {
                 // the solution: the image's right-hand-side column, or the packed image's solution vector (the structured solve's own order)
                 auto sol = [&](int i) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(TG_NO_BBD)
+#if defined(__HIP_DEVICE_COMPILE__)
                     if constexpr (TEAM == 64 && PIVOT == 0 && tg_static_pk<typename std::remove_cv<PROG>::type>::value) {
                         typedef typename std::remove_cv<PROG>::type SP;
                         if (bbd_done) return S[P.o_Df + SP::bbd_pk_xs + i];
@@ -5498,17 +5394,12 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 }
                 iterations++;
             }
-#endif
             TG_SYNC();
         }
         if (on && !failed) {
             total_iters += iterations;
             // p2 = D2L2 at the converged midpoint (midpointvi.c:742-743); it becomes p1 of the next step
-#if defined(TG_MOCK_TIMING)
-            TG_FOR(i, nd) S[P.o_scal + (i & 15)] = 0.5 * dt * S[P.o_Ldq + i] + S[P.o_Lddq + i];
-#else
             TG_FOR(i, nd) S[P.o_p1 + i] = 0.5 * dt * S[P.o_Ldq + i] + S[P.o_Lddq + i];
-#endif
         }
         TG_SYNC();
         if (on && !failed && A.X) {

@@ -33,15 +33,11 @@ template <int MODE> constexpr int spec_waves() { return ((MODE == tg::MODE_DERIV
 static_assert(TG_NW >= 1 && TG_NW <= 2, "helper waves: the pair lists of program.hpp are split in exactly two parts (wave_part, wp_* / wt_* / wcp4)");
 static_assert(TG_NW == 1 || SPEC_TEAM == 64, "helper waves are for full-wave teams (trep_amd/specialize.py passes TG_HELPER_WAVES only then)");
 
-// waves per SIMD the rollout kernel is compiled for (its register budget: 2 -> 256, 3 -> 168): -DTG_ROLLOUT_WAVES=3 is an occupancy
-// experiment (tools/ab_spec.sh), not a product setting -- the LDS slice of a trajectory allows 8 per CU = 2 per SIMD
-#ifndef TG_DERIV_WAVES
-#define TG_DERIV_WAVES 1      // wavefronts per SIMD the second-derivative kernel's register allocation leaves room for (its LDS slice allows one; the first-
-                              // derivative kernel: two when its compact slice lets three workgroups of two waves share a CU)
-#endif
-#ifndef TG_ROLLOUT_WAVES
-#define TG_ROLLOUT_WAVES 2
-#endif
+// waves per SIMD the rollout kernel is compiled for (its register budget: 2 -> 256, 3 -> 168): the LDS slice of a trajectory allows
+// 8 per CU = 2 per SIMD
+constexpr int TG_ROLLOUT_WAVES = 2;
+constexpr int TG_DERIV_WAVES = 1;     // wavefronts per SIMD the second-derivative kernel's register allocation leaves room for (its LDS slice allows one; the first-
+                                      // derivative kernel: two when its compact slice lets three workgroups of two waves share a CU)
 template <int MODE, int PIVOT = 0>
 __global__ __launch_bounds__(64 * spec_waves<MODE>(), MODE == tg::MODE_DERIV1 ? (SpecProg::a_ok ? 2 : 1) : (MODE == tg::MODE_DERIV2Z ? TG_DERIV_WAVES : TG_ROLLOUT_WAVES)) void k_spec(SPEC_KERNEL_ARGS) {
     SPEC_ARGS_REF;
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(64, 2) void k_spec_debug_solve(const double *A_in, 
         } else load_dense();
         __syncthreads();
         typedef typename std::conditional<PKI, tg::BbdPackedImage<SpecProg::bbd_pk_nr, SpecProg::bbd_pk_nc2, SpecProg::bbd_pk_tb, SpecProg::bbd_pk_tc2, SpecProg::bbd_pk_xs>, tg::BbdDenseImage>::type Img;
-        if (!skip_structured && tg::gj_bbd<nf, ld, SpecProg::bbd_ng, SpecProg::bbd_nb, SpecProg::bbd_t, tg::BbdNoUpdate, Img>(S + P.o_Df, tg::bbd_rows<SpecProg::bbd_ng + SpecProg::bbd_nb>(tab, lane), PKI ? S + P.o_W + 12 * P.n_joints : S + P.o_J, lane, P.bbd_tvar)) { ok = true; path = 1; }
+        if (!skip_structured && tg::gj_bbd<nf, ld, SpecProg::bbd_ng, SpecProg::bbd_nb, SpecProg::bbd_t, Img>(S + P.o_Df, tg::bbd_rows<SpecProg::bbd_ng + SpecProg::bbd_nb>(tab, lane), PKI ? S + P.o_W + 12 * P.n_joints : S + P.o_J, lane, P.bbd_tvar)) { ok = true; path = 1; }
         __syncthreads();
         if (PKI && ok && lane < nf) x_out[(size_t)blockIdx.x * nf + lane] = S[P.o_Df + SpecProg::bbd_pk_xs + lane];
         if (PKI && !ok) load_dense();
@@ -157,13 +153,8 @@ int launch_mode_par(const tg::RunArgs *A, tg::RunArgs *slot, int grid, size_t ld
 
 extern "C" {
 const int *tg_spec_sizes(void) {
-#if defined(TG_MOCK_REAL_LDS)      // timing mock with aliased LDS areas (tools/mock_third_wave.py): answer with the real schedule's slice
-    constexpr int lds_doubles = TG_MOCK_REAL_LDS;
-#else
-    constexpr int lds_doubles = SpecProg::lds_per_team;
-#endif
     static const int s[8] = {(int)sizeof(tg::DevProg), (int)sizeof(tg::RunArgs), SpecProg::nq, SpecProg::nd, SpecProg::nc, SpecProg::n_items,
-                             SpecProg::n_pairs, lds_doubles};
+                             SpecProg::n_pairs, SpecProg::lds_per_team};
     return s;
 }
 // hash of the generated header this library was compiled against (tg_system_spec_key; trep_amd/specialize.py passes it)
@@ -195,15 +186,6 @@ int tg_spec_debug_solve(const double *A_dev, double *x_dev, int *path_dev, int n
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 int tg_spec_launch(int mode, const tg::RunArgs *A, tg::RunArgs *device_slot, int grid, size_t lds, void *stream) {
-#if defined(TG_MOCK_TIMING)     // the mock's header aliases LDS areas: its slice is smaller than the one the host computed from the real schedule
-    if (mode == tg::MODE_ROLLOUT) lds = sizeof(double) * (size_t)SpecProg::lds_per_team * (64 / SPEC_TEAM);
-#endif
-#if defined(TG_MOCK_LDS_D1)   // timing mock: another LDS size (another number of resident workgroups) for the first-derivative kernel; wrong numbers
-    if (mode == tg::MODE_DERIV1) lds = TG_MOCK_LDS_D1;
-#endif
-#if defined(TG_MOCK_LDS_D2)
-    if (mode == tg::MODE_DERIV2Z) lds = TG_MOCK_LDS_D2;
-#endif
     switch (mode) {
     case tg::MODE_ROLLOUT:
         return A->exact_pivot ? launch_mode<tg::MODE_ROLLOUT, 1>(A, device_slot, grid, lds, (hipStream_t)stream)
