@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: golden fixtures + the systems they were made from."""
 import collections
+import functools
 import os
 
 import numpy as np
@@ -793,3 +794,345 @@ def lq_singular_problem(ds, N, S, seed, u, steps):
         pr["hz"][seed, k][nxh + u, :] = 0.0; pr["hz"][seed, k][:, nxh + u] = 0.0
     pr["R_sk"] = R
     return pr
+
+
+# ---- the forward-mode (dual-number) kernels of the continuous dynamics (k_forward, run_forward, csrc/dual.hpp): test_forward_cpu.py
+# keeps the table honest with the oracle alone and runs the emulated kernels over it, test_gpu_forward.py runs it on the device,
+# tools/forward_parity.py records it.  A kernel's output along variable v (numbered q | dq | ddq_k | u) is the directional derivative of
+# arrays the oracle has in analytic form (OracleMVI.dynamics_deriv1 / lagrangian); the reference is a Richardson-extrapolated central
+# difference of those arrays, accumulated in long double (fw_ladder), nested for two directions.
+FW_KERNELS = ("dyn", "lag1", "lag2")        # MODE_DYN_DERIV1 on Dual<double>, MODE_LAGRANGIAN on Dual<double> and on Dual<Dual<double>>
+FW_DYN_NAMES = ("f_dq", "f_ddq", "f_dddk", "f_du", "lambda_dq", "lambda_ddq", "lambda_dddk", "lambda_du")
+FW_LAG_NAMES = ("L_dq", "L_ddq", "L_dqdq", "L_ddqdq", "L_ddqddq")
+FW_TOL = {"dyn": 1e-10, "lag1": 1e-12, "lag2": 1e-12}       # the project's figures (test_dynamics.py)
+FW_FLOOR = {"dyn": 1e-10 / 64, "lag1": 1e-12 / 64, "lag2": 1e-12 / 64}
+FW_BLOCKS = ("q", "dq", "ddq_k", "u")
+# system -> (trajectories, scale of the noise on the golden q); dq, ddq_k and u get unit-normal draws.
+FW_SYSTEMS = collections.OrderedDict([
+    ("pend_on_cart", (24, 0.05)),
+    ("scissor4", (24, 0.05)),
+    ("puppet40", (12, 0.05)),
+    ("puppet_basic", (12, 0.05)),
+    ("plane_link", (24, 0.05)),
+    ("spring_arm", (24, 0.05)),
+    ("spring_link", (24, 0.05)),
+    ("dual_pendulums", (24, 0.05)),
+    ("damper_link", (24, 0.05)),
+    ("nonlinear_spring_arm", (24, 0.05)),
+    ("wrench_arm", (24, 0.05)),
+    ("wrench_spatial", (24, 0.05)),
+    ("wrench_body", (24, 0.05)),
+    ("puppet_forces", (12, 0.05)),
+    ("extensor_tendon", (24, 0.05)),
+])
+FW_CASES = [(n, k) for n in FW_SYSTEMS for k in FW_KERNELS]
+# The ladder: (base step along a q variable, halvings) per kernel, and per (system, kernel) where the default misses the floor rule of
+# test_forward_cpu.py.  Along q the arrays are trigonometric (the scissor lift's and the puppets' steeply so): the step trades the
+# truncation the extrapolation leaves against the rounding of the oracle's fp64 arrays, eps / h per direction.  Along dq, ddq_k and u
+# every array is a polynomial of degree <= 2, so a central difference is exact at any step and the large FW_STEP_V keeps the rounding
+# small.
+FW_STEP_V = 0.5
+FW_LADDER_DEFAULT = {"dyn": (0.08, 3), "lag1": (0.16, 3), "lag2": (0.16, 3)}
+FW_LADDER = {("scissor4", "dyn"): (0.02, 3), ("scissor4", "lag2"): (0.32, 3), ("plane_link", "dyn"): (0.08, 5), ("damper_link", "dyn"): (0.02, 3),
+             ("puppet_basic", "lag2"): (0.32, 3),
+             ("nonlinear_spring_arm", "dyn"): (0.01, 3), ("nonlinear_spring_arm", "lag1"): (0.005, 2), ("nonlinear_spring_arm", "lag2"): (0.01, 2),
+             ("dual_pendulums", "dyn"): (0.16, 5), ("dual_pendulums", "lag1"): (0.08, 4), ("spring_link", "lag1"): (0.16, 4), ("dual_pendulums", "lag2"): (0.16, 5),
+             ("extensor_tendon", "dyn"): (0.16, 4), ("extensor_tendon", "lag1"): (0.16, 4), ("extensor_tendon", "lag2"): (0.08, 3)}
+
+
+def fw_ladder_of(name, kernel):
+    return FW_LADDER.get((name, kernel), FW_LADDER_DEFAULT[kernel])
+# another draw where the first one fails the sensitivity rule of test_forward_cpu.py: (system, kernel) -> draw number
+# (puppet_basic: seven of twelve references of draw 0 are under the bound.  nonlinear_spring_arm: a ladder that straddles a knot of one of
+# the force splines differences a kink, and the floor of such a trajectory is 1e-6 ... 1e-3; these are draws on which no ladder does)
+FW_DRAW = {("puppet_basic", "lag2"): 1, ("nonlinear_spring_arm", "lag1"): 4, ("nonlinear_spring_arm", "lag2"): 3}
+# (system, kernel, array) whose bound needs the second term of max(tolerance, 64 e_ref): measured floor e_ref (test_forward_cpu.py
+# asserts that exactly these are over FW_FLOOR, and each under twice the figure here)
+FW_SECOND_TERM = {
+    ("pend_on_cart", "lag1"): {"L_dq": 1.7e-14, "L_ddq": 6.0e-14, "L_dqdq": 7.2e-14},
+    ("pend_on_cart", "lag2"): {"L_dq": 4.8e-12, "L_ddq": 1.1e-11, "L_dqdq": 2.6e-12, "L_ddqdq": 6.2e-13, "L_ddqddq": 7.2e-13},
+    ("scissor4", "dyn"): {"f_dq": 2.2e-11, "f_ddq": 2.4e-11, "lambda_dq": 4.1e-11, "lambda_ddq": 2.1e-11},
+    ("scissor4", "lag1"): {"L_dq": 1.1e-13, "L_ddq": 2.0e-13, "L_dqdq": 1.9e-13, "L_ddqdq": 1.3e-13, "L_ddqddq": 5.3e-14},
+    ("scissor4", "lag2"): {"L_dq": 3.5e-11, "L_ddq": 9.8e-12, "L_dqdq": 1.1e-11, "L_ddqdq": 7.7e-12, "L_ddqddq": 9.7e-13},
+    ("puppet40", "dyn"): {"f_dq": 4.2e-12, "lambda_dq": 9.7e-12},
+    ("puppet40", "lag1"): {"L_dq": 9.7e-14, "L_ddq": 1.6e-13, "L_dqdq": 1.0e-13, "L_ddqdq": 1.1e-13, "L_ddqddq": 2.1e-13},
+    ("puppet40", "lag2"): {"L_dq": 2.2e-11, "L_ddq": 6.3e-12, "L_dqdq": 4.0e-12, "L_ddqdq": 4.5e-12, "L_ddqddq": 4.5e-12},
+    ("puppet_basic", "dyn"): {"f_dq": 5.8e-12, "f_ddq": 5.0e-12, "lambda_dq": 2.6e-12, "lambda_ddq": 2.2e-12},
+    ("puppet_basic", "lag1"): {"L_dq": 8.2e-13, "L_ddq": 2.0e-13, "L_dqdq": 7.8e-13, "L_ddqdq": 1.5e-13, "L_ddqddq": 4.9e-13},
+    ("puppet_basic", "lag2"): {"L_dq": 7.7e-11, "L_ddq": 2.5e-11, "L_dqdq": 5.2e-11, "L_ddqdq": 5.4e-11, "L_ddqddq": 1.4e-11},
+    ("plane_link", "dyn"): {"f_ddq": 2.1e-12},
+    ("plane_link", "lag1"): {"L_dq": 1.6e-13, "L_ddq": 3.1e-14, "L_dqdq": 1.9e-13, "L_ddqdq": 7.4e-14, "L_ddqddq": 2.0e-14},
+    ("plane_link", "lag2"): {"L_dq": 5.2e-12, "L_ddq": 9.3e-13, "L_dqdq": 1.2e-11, "L_ddqdq": 1.7e-12, "L_ddqddq": 1.2e-12},
+    ("spring_arm", "lag1"): {"L_dq": 8.2e-14, "L_ddq": 6.0e-14, "L_dqdq": 2.3e-13, "L_ddqdq": 1.0e-13, "L_ddqddq": 4.8e-14},
+    ("spring_arm", "lag2"): {"L_dq": 1.5e-11, "L_ddq": 2.5e-12, "L_dqdq": 2.6e-11, "L_ddqdq": 5.1e-12, "L_ddqddq": 7.9e-12},
+    ("spring_link", "lag1"): {"L_dq": 1.7e-13, "L_ddq": 6.6e-14, "L_dqdq": 9.4e-14, "L_ddqdq": 5.1e-14, "L_ddqddq": 1.0e-13},
+    ("spring_link", "lag2"): {"L_dq": 2.9e-11, "L_ddq": 1.2e-12, "L_dqdq": 3.7e-11, "L_ddqdq": 1.4e-12, "L_ddqddq": 4.8e-13},
+    ("dual_pendulums", "dyn"): {"f_dq": 2.7e-12},
+    ("dual_pendulums", "lag1"): {"L_dq": 2.7e-14, "L_dqdq": 2.3e-12},
+    ("dual_pendulums", "lag2"): {"L_dq": 3.3e-10, "L_dqdq": 2.9e-10},
+    ("damper_link", "lag1"): {"L_dq": 5.2e-14, "L_ddq": 7.8e-14, "L_dqdq": 3.8e-14, "L_ddqdq": 6.5e-14, "L_ddqddq": 3.9e-14},
+    ("damper_link", "lag2"): {"L_dq": 6.4e-12, "L_ddq": 6.8e-12, "L_dqdq": 5.5e-12, "L_ddqdq": 1.7e-12, "L_ddqddq": 9.5e-12},
+    ("nonlinear_spring_arm", "dyn"): {"f_ddq": 2.6e-12},
+    ("nonlinear_spring_arm", "lag1"): {"L_dq": 4.0e-13, "L_ddq": 5.3e-13, "L_dqdq": 1.0e-12, "L_ddqdq": 1.1e-12, "L_ddqddq": 1.1e-12},
+    ("nonlinear_spring_arm", "lag2"): {"L_dq": 4.0e-10, "L_ddq": 4.7e-10, "L_dqdq": 1.3e-09, "L_ddqdq": 5.2e-10, "L_ddqddq": 3.3e-10},
+    ("wrench_arm", "lag1"): {"L_dq": 1.6e-13, "L_ddq": 1.3e-13, "L_dqdq": 6.0e-14, "L_ddqdq": 6.4e-14, "L_ddqddq": 3.8e-14},
+    ("wrench_arm", "lag2"): {"L_dq": 8.6e-12, "L_ddq": 1.4e-11, "L_dqdq": 7.1e-12, "L_ddqdq": 5.5e-12, "L_ddqddq": 3.8e-12},
+    ("wrench_spatial", "lag1"): {"L_dq": 7.6e-14, "L_ddq": 5.3e-14, "L_dqdq": 1.5e-13, "L_ddqdq": 1.1e-13, "L_ddqddq": 6.1e-14},
+    ("wrench_spatial", "lag2"): {"L_dq": 4.9e-12, "L_ddq": 4.5e-12, "L_dqdq": 8.3e-12, "L_ddqdq": 3.1e-12, "L_ddqddq": 4.0e-12},
+    ("wrench_body", "lag1"): {"L_dq": 5.0e-14, "L_ddq": 7.0e-14, "L_dqdq": 1.1e-13, "L_ddqdq": 4.6e-14, "L_ddqddq": 3.8e-14},
+    ("wrench_body", "lag2"): {"L_dq": 9.1e-12, "L_ddq": 9.8e-12, "L_dqdq": 1.2e-11, "L_ddqdq": 8.3e-12, "L_ddqddq": 9.6e-12},
+    ("puppet_forces", "lag1"): {"L_dq": 1.6e-13, "L_ddq": 1.8e-13, "L_dqdq": 8.4e-14, "L_ddqdq": 1.4e-13, "L_ddqddq": 8.1e-14},
+    ("puppet_forces", "lag2"): {"L_dq": 2.7e-11, "L_ddq": 1.6e-11, "L_dqdq": 1.3e-11, "L_ddqdq": 9.1e-12, "L_ddqddq": 5.8e-12},
+    ("extensor_tendon", "dyn"): {"f_dq": 6.1e-12, "f_ddq": 3.4e-12},
+    ("extensor_tendon", "lag1"): {"L_dq": 5.1e-13, "L_ddq": 7.7e-13, "L_dqdq": 7.3e-13, "L_ddqdq": 1.2e-13, "L_ddqddq": 4.6e-13},
+    ("extensor_tendon", "lag2"): {"L_dq": 1.3e-10, "L_ddq": 1.0e-10, "L_dqdq": 1.1e-10, "L_ddqdq": 3.1e-11, "L_ddqddq": 1.5e-10},
+}
+
+
+def fw_golden_states(name):
+    """The recorded configurations the draws are made near: the states of dynamics.npz, or (the two systems it does not have) every
+    fifth configuration of the system's recorded trajectory."""
+    g = dict(np.load(os.path.join(GOLDEN, "dynamics.npz"))) if "dynamics" not in _cache else _cache["dynamics"]
+    _cache["dynamics"] = g
+    if name + "_q" in g:
+        return g[name + "_q"]
+    return golden(name)["b0_Q"][::5][:4]
+
+
+def fw_sizes(d):
+    nq, nk, nu = d.n_configs, d.n_kin, d.n_inputs
+    return nq, nk, nu, 2 * nq + nk + nu
+
+
+def fw_block(d, v):
+    """Index into FW_BLOCKS of direction variable v (None for -1)."""
+    nq, nk, nu, nvar = fw_sizes(d)
+    if v < 0:
+        return None
+    return 0 if v < nq else (1 if v < 2 * nq else (2 if v < 2 * nq + nk else 3))
+
+
+def fw_neighbour(d, kernel, v):
+    """The variable next to v (the one before the last): what a seed offset that is off by one would follow."""
+    nq, nk, nu, nvar = fw_sizes(d)
+    top = nvar if kernel == "dyn" else 2 * nq
+    return v + 1 if v + 1 < top else v - 1
+
+
+@functools.lru_cache(maxsize=None)
+def fw_case(name, kernel):
+    """dict(d, B, Q, dQ, U, ddK, seeds) of a case: every trajectory has its own state (golden q plus noise, unit-normal dq, u, ddq_k) and
+    its own direction(s); seeds = (s1,) or, for "lag2", (s1, s2).  Over the case the seeds cover the first and the last variable of
+    every block the system has (dyn: q | dq | ddq_k | u, "lag1": q | dq); "lag2" has the pairs (q, q) with equal and unequal indices,
+    (q, dq), (dq, q), (dq, dq) and (v, -1).  Trajectory 2 has no direction (-1) and the last trajectory is an
+    exact copy of an earlier one whose derivative is not zero (duplicates = (earlier, last)).  The arrays are read-only."""
+    _, d = build(name)
+    B, scale = FW_SYSTEMS[name]
+    nq, nk, nu, nvar = fw_sizes(d)
+    rng = np.random.default_rng(tb_seed("fw", name, kernel, FW_DRAW.get((name, kernel), 0)))
+    gq = fw_golden_states(name)
+    Q = gq[rng.integers(len(gq), size=B)] + scale * rng.standard_normal((B, nq))
+    dQ, U, ddK = rng.standard_normal((B, nq)), rng.standard_normal((B, nu)), rng.standard_normal((B, nk))
+    q0, q1, v0, v1 = 0, nq - 1, nq, 2 * nq - 1
+    if kernel == "dyn":
+        must = [(v,) for lo, hi in ((0, nq), (nq, 2 * nq), (2 * nq, 2 * nq + nk), (2 * nq + nk, nvar)) if hi > lo for v in (lo, hi - 1)]
+        top, width = nvar, 1
+    elif kernel == "lag1":
+        must, top, width = [(q0,), (q1,), (v0,), (v1,)], 2 * nq, 1
+    else:
+        # (random dynamic configs instead of the first and last variable: on the puppets those are a translation and a string length, which
+        # the Lagrangian's third and fourth derivatives do not see)
+        must = []
+        for _ in range(2):
+            a, b = (int(x) for x in rng.choice(d.n_dyn, size=2, replace=False))
+            must += [(a, a), (a, b), (a, nq + b), (nq + a, b)]
+        must += [(nq + a, nq + b), (b, -1)]
+        top, width = 2 * nq, 2
+    assert len(must) + 2 <= B
+    if kernel == "dyn":
+        free = [(int(rng.integers(0, top)),) for _ in range(B - 2 - len(must))]
+    elif kernel == "lag1":
+        # (free directions: the dynamic configurations and their velocities -- the Lagrangian does not see a massless string length)
+        free = [(int(rng.integers(0, d.n_dyn) + nq * rng.integers(0, 2)),) for _ in range(B - 2 - len(must))]
+    else:
+        # (free pairs: a variable of q | dq and a configuration next to its own -- coupled in a linkage, where two drawn at random
+        # mostly are not, and two velocities leave only L_dqdq)
+        free = []
+        for _ in range(B - 2 - len(must)):
+            a = int(rng.integers(0, top))
+            free.append((a, int(np.clip(a % nq + rng.integers(-1, 2), 0, nq - 1))))
+    rows = must + free
+    rows = [rows[i] for i in rng.permutation(len(rows))]
+    rows.insert(2, (-1,) * width)
+    # the trajectory that is repeated: the first whose derivative is there to be compared (one plain central difference of the oracle's
+    # arrays has an entry above 1e-6), so that equal bits are not equal zeros
+    from oracle.oracle import OracleMVI
+    o, names = OracleMVI(d), FW_DYN_NAMES if kernel == "dyn" else FW_LAG_NAMES
+    probe = lambda b: fw_derivative(name, kernel, np.concatenate([Q[b], dQ[b], ddK[b], U[b]]), rows[b], o, d, (fw_ladder_of(name, kernel)[0], 0))[0]
+    dup = next(b for b in range(1, B - 1) if min(rows[b]) >= 0 and max(np.abs(a).max(initial=0.0) for a in probe(b).values()) > 1e-6)
+    rows.append(rows[dup])
+    for a in (Q, dQ, U, ddK):
+        a[B - 1] = a[dup]
+    S = np.array(rows, dtype=np.int32)
+    out = dict(name=name, kernel=kernel, d=d, B=B, Q=Q, dQ=dQ, U=U, ddK=ddK, seeds=tuple(np.ascontiguousarray(S[:, i]) for i in range(width)),
+               duplicates=(dup, B - 1), names=names)
+    for a in (Q, dQ, U, ddK) + out["seeds"]:
+        a.setflags(write=False)
+    return out
+
+
+def fw_x(c, b):
+    """The state of trajectory b as one vector in the numbering of the direction variables: q | dq | ddq_k | u."""
+    return np.concatenate([c["Q"][b], c["dQ"][b], c["ddK"][b], c["U"][b]])
+
+
+def fw_oracle_arrays(o, kernel, x):
+    """The oracle's analytic arrays at x = q | dq | ddq_k | u as one flat long-double vector (fw_split undoes it): the eight first-derivative
+    arrays of the continuous dynamics ("dyn", [output][variable] each), or L_dq, L_ddq, L_dqdq, L_ddqdq, L_ddqddq."""
+    nq, nk = o.nq, o.nk
+    q, dq = x[:nq], x[nq:2 * nq]
+    if kernel == "dyn":
+        r = o.dynamics_deriv1(q, dq, x[2 * nq + nk:], x[2 * nq:2 * nq + nk])
+        parts = [r[n.replace("lambda_", "lam_")] for n in FW_DYN_NAMES]
+    else:
+        parts = o.lagrangian(q, dq)
+    return np.concatenate([np.asarray(p, dtype=np.longdouble).ravel() for p in parts])
+
+
+def fw_split(d, kernel, flat):
+    """dict of the arrays of a flat vector, in the layout of BatchMidpointVI.dynamics_deriv1 / lagrangian for one trajectory."""
+    nq, nd, nk, nu, nc = d.n_configs, d.n_dyn, d.n_kin, d.n_inputs, d.n_constraints
+    if kernel == "dyn":
+        shapes = [(o_, w) for o_ in (nd, nc) for w in (nq, nq, nk, nu)]
+        names = FW_DYN_NAMES
+    else:
+        shapes, names = [(nq,), (nq,), (nq, nq), (nq, nq), (nq, nq)], FW_LAG_NAMES
+    out, at = {}, 0
+    for n, s in zip(names, shapes):
+        size = int(np.prod(s))
+        out[n] = np.asarray(flat[at:at + size], dtype=np.float64).reshape(s)
+        at += size
+    return out
+
+
+def fw_ladder(fun, x, v, h, levels):
+    """Richardson-extrapolated central difference of fun (-> long-double array) along variable v of x: the steps h / 2^k, k = 0 ..
+    levels + 1, each divided by the step actually taken, x+ - x-; returns the extrapolation of steps 0 .. levels (the reference) and
+    that of steps 1 .. levels + 1 (its rival: the two base steps differ by a factor of two, their disagreement is the floor e_ref)."""
+    D = []
+    for k in range(levels + 2):
+        xp, xm = x.copy(), x.copy()
+        xp[v] += h / 2.0 ** k
+        xm[v] -= h / 2.0 ** k
+        D.append((fun(xp) - fun(xm)) / (np.longdouble(xp[v]) - np.longdouble(xm[v])))
+
+    def extrapolate(T):
+        j = 1
+        while len(T) > 1:
+            T = [T[i + 1] + (T[i + 1] - T[i]) / (np.longdouble(4.0) ** j - 1) for i in range(len(T) - 1)]
+            j += 1
+        return T[0]
+    return extrapolate(D[:levels + 1]), extrapolate(D[1:])
+
+
+def fw_derivative(name, kernel, x, seeds, o=None, d=None, ladder=None):
+    """(reference, rival) dicts of arrays: the derivative of the oracle's arrays at x along seeds = (v,) or nested along (v1, v2), by the
+    ladder at the system's base step and at half of it.  A -1 among the seeds: zeros.  (d, ladder: a system outside the table.)"""
+    if d is None:
+        _, d = build(name)
+    if o is None:
+        from oracle.oracle import OracleMVI
+        o = OracleMVI(d)
+    hq, levels = ladder or fw_ladder_of(name, kernel)
+    step = lambda v: hq if v < d.n_configs else FW_STEP_V
+    base = lambda y: fw_oracle_arrays(o, kernel, y)
+    x = np.asarray(x, dtype=np.float64)
+    if min(seeds) < 0:
+        z = np.zeros_like(base(x))
+        return fw_split(d, kernel, z), fw_split(d, kernel, z)
+    if len(seeds) == 1:
+        a, b = fw_ladder(base, x, seeds[0], step(seeds[0]), levels)
+    else:
+        inner = lambda y: np.stack(fw_ladder(base, y, seeds[0], step(seeds[0]), levels))
+        (a, _), (_, b) = fw_ladder(inner, x, seeds[1], step(seeds[1]), levels)
+    return fw_split(d, kernel, a), fw_split(d, kernel, b)
+
+
+@functools.lru_cache(maxsize=None)
+def fw_reference(name, kernel):
+    """Per trajectory of a case (reference, rival) of fw_derivative, computed once."""
+    from oracle.oracle import OracleMVI
+    c = fw_case(name, kernel)
+    o = OracleMVI(c["d"])
+    return [fw_derivative(name, kernel, fw_x(c, b), tuple(int(s[b]) for s in c["seeds"]), o) for b in range(c["B"])]
+
+
+@functools.lru_cache(maxsize=None)
+def fw_e_ref(name, kernel):
+    """{array: floor} of a case: the largest relerr between the ladders of the two base steps.  From the reference alone."""
+    c = fw_case(name, kernel)
+    return collections.OrderedDict((n, max(relerr(alt[n], ref[n]) for ref, alt in fw_reference(name, kernel))) for n in c["names"])
+
+
+def fw_bound(name, kernel, array):
+    """max(project tolerance, 64 e_ref)"""
+    return max(FW_TOL[kernel], 64.0 * fw_e_ref(name, kernel)[array])
+
+
+def fw_errors(name, kernel, got):
+    """{array: worst relerr over the trajectories} of got = {array: [B][...]} against the reference."""
+    ref = fw_reference(name, kernel)
+    return collections.OrderedDict((n, max(relerr(got[n][b], ref[b][0][n]) for b in range(len(ref)))) for n in fw_case(name, kernel)["names"])
+
+
+# ---- the LDS limit of the forward-mode kernels: one wavefront per trajectory, the slice is sizeof(Real) / 8 times the double kernel's
+FW_LDS_LIMIT = 160 * 1024
+FW_REAL_BYTES = {"dyn": 16, "lag1": 16, "lag2": 32}
+
+
+def fw_lds_bytes(d, kernel):
+    """The LDS block launch_forward_mode asks for (csrc/trepamd.hip), from the host emulation's slice sizes."""
+    import emu_harness
+    s = emu_harness.lds_slices(d)
+    per_team = max(s["rollout"], s["dynamics_deriv1"]) if kernel == "dyn" else s["rollout"]
+    return per_team * FW_REAL_BYTES[kernel]
+
+
+@functools.lru_cache(maxsize=None)
+def fw_chain(links):
+    from trep_amd import systems
+    system = systems.pendulum(links)
+    return system, descriptor.flatten(system)
+
+
+@functools.lru_cache(maxsize=None)
+def fw_chain_limit(kernel, most=64):
+    """The shortest n-link pendulum (the chain of test_long_chain_matches_oracle) whose forward-mode block is over the limit, by
+    bisection (the slice grows with the chain); None if a chain of `most` links still fits."""
+    over = lambda n: fw_lds_bytes(fw_chain(n)[1], kernel) > FW_LDS_LIMIT
+    if not over(most):
+        return None
+    lo, hi = 1, most                      # lo fits, hi does not
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if over(mid) else (mid, hi)
+    return hi
+
+
+@functools.lru_cache(maxsize=None)
+def fw_chain_case(kernel, links, B=3):
+    """B states of the chain with a direction in q, in dq and in q again (lag2: a (q, q), a (q, dq) and a (dq, dq) pair), and their
+    (reference, rival) by the default ladder of the kernel."""
+    from oracle.oracle import OracleMVI
+    _, d = fw_chain(links)
+    rng = np.random.default_rng(tb_seed("fw chain", kernel, links))
+    Q, dQ = rng.uniform(-0.6, 0.6, (B, links)), 0.3 * rng.standard_normal((B, links))
+    a, b = (int(x) for x in rng.choice(links, size=2, replace=False))
+    rows = [(a,), (links + b,), (links - 1,)] if kernel != "lag2" else [(a, b), (b, links + a), (links + a, links + b)]
+    S = np.array(rows[:B], dtype=np.int32)
+    o = OracleMVI(d)
+    c = dict(d=d, B=B, Q=Q, dQ=dQ, U=np.zeros((B, 0)), ddK=np.zeros((B, 0)), seeds=tuple(np.ascontiguousarray(S[:, i]) for i in range(S.shape[1])),
+             names=FW_DYN_NAMES if kernel == "dyn" else FW_LAG_NAMES)
+    c["reference"] = [fw_derivative(None, kernel, fw_x(c, t), tuple(int(s_[t]) for s_ in c["seeds"]), o, d, FW_LADDER_DEFAULT[kernel]) for t in range(B)]
+    c["e_ref"] = dict((n, max(relerr(alt[n], ref[n]) for ref, alt in c["reference"])) for n in c["names"])
+    return c

@@ -308,6 +308,7 @@ int launch_forward_mode(tg_batch *b, const tg::RunArgs &A) {
     const size_t lds = (size_t)per_team * sizeof(Real);
     if (lds > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident forward-mode kernel");
     const bool springs = b->P.has_cs || b->P.n_springs || b->P.has_plane || b->P.n_wrenches;
+    b->generic_launched_modes |= 1u << MODE; b->generic_launches++;      // no forward-mode kernel is ever specialised (tg_batch_info)
     int rc = springs ? launch_forward_variant<MODE, true, Real>(b, A, lds) : launch_forward_variant<MODE, false, Real>(b, A, lds);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
     return rc;
