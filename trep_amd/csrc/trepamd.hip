@@ -11,9 +11,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "device_buffer.hpp"
 #include "mvi_core.hpp"
 #include "spec_emit.inc"
 #include <dlfcn.h>
@@ -75,7 +77,7 @@ struct tg_batch {
     tg_system *sys = nullptr;
     int batch = 0, device = 0;
     tg::DevProg P{};           // device-pointer view
-    tg::DevProg *d_prog = nullptr;   // the same view in device memory: what the kernels read (constant address space)
+    tg::DeviceBuffer<tg::DevProg> d_prog;   // the same view in device memory: what the kernels read (constant address space)
     // optional system-specialised rollout kernel (tg_batch_load_specialized): launcher exported by a generated library
     void *spec_lib = nullptr;
     int (*spec_launch)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *) = nullptr;
@@ -84,50 +86,49 @@ struct tg_batch {
     int spec_par_modes = 0;
     // per-trajectory parameter table (tg_batch_set_parameters): par_rows rows of par_stride doubles (tg::ParTable layout) on the device;
     // par_rows == 0: none set, the default kernels run
-    double *par_dev = nullptr;
-    size_t par_cap = 0;
+    tg::DeviceBuffer<double> par_dev;
     int par_rows = 0, par_group = 1, par_stride = 0;
-    unsigned int par_spec_launched_modes = 0, par_generic_launched_modes = 0;   // bit m: a mode-m launch went through a parameter kernel of that kind
-    long long par_spec_launches = 0, par_generic_launches = 0;                   // (tg_batch_par_info; tg_batch_info counts the default kernels)
+    // launches so far, [parameter kernel?][specialised?]: bit m of modes = a mode-m launch went through a kernel of that kind
+    // (tg_batch_info reports the default kernels, tg_batch_par_info the parameter kernels)
+    struct Launched { unsigned int modes = 0; long long n = 0; void add(int mode) { modes |= 1u << mode; n++; } } launched[2][2];
     // argument blocks of the specialised kernels: ARG_SLOTS device-side blocks fed from a pinned host ring (a truly asynchronous
     // hipMemcpyAsync; a slot is reused only after the launch that read it has finished: arg_done[i])
     static constexpr int ARG_SLOTS = 4;
-    tg::RunArgs *d_args = nullptr;   // [ARG_SLOTS] device
-    tg::RunArgs *h_args = nullptr;   // [ARG_SLOTS] pinned host
-    hipEvent_t arg_done[ARG_SLOTS] = {nullptr, nullptr, nullptr, nullptr};
+    tg::DeviceBuffer<tg::RunArgs> d_args;   // [ARG_SLOTS] device
+    tg::PinnedBuffer<tg::RunArgs> h_args;   // [ARG_SLOTS] pinned host
+    tg::Event arg_done[ARG_SLOTS];
     bool arg_used[ARG_SLOTS] = {false, false, false, false};
     int arg_next = 0;
     // small batches (the B = 1 drop-in path): tg_batch_step stages its inputs through ONE pinned block, and a pack kernel + ONE
     // copy bring (q2, p2, lambda1, iterations, status) back into a pinned host mirror that later tg_batch_get / tg_batch_status
     // calls answer from, until anything else touches the batch (launch(), tg_batch_set, restore ...)
-    double *io_host = nullptr, *io_dev = nullptr;
+    tg::PinnedBuffer<double> io_host;
+    double *io_dev = nullptr;          // the same block as the device sees it
     size_t io_in = 0, io_out = 0;      // doubles in the input / output part
     bool mirror_valid = false;
     int spec_modes = 0, spec_waves = 1;
-    unsigned int spec_launched_modes = 0, generic_launched_modes = 0;   // bit m: a kernel of mode m went through that path (tg_batch_info)
-    long long spec_launches = 0, generic_launches = 0;
     std::string spec_path;
-    int *d_ints = nullptr;
-    double *d_dbls = nullptr;
-    double *q1 = nullptr, *q2 = nullptr, *p1 = nullptr, *p2 = nullptr, *lam = nullptr, *u1 = nullptr;
-    double *stage_u = nullptr, *stage_k = nullptr, *stage_qh = nullptr, *stage_lh = nullptr, *f_out = nullptr;
-    int *iters = nullptr, *status = nullptr, *fallbacks = nullptr;
-    double *z_dev = nullptr, *hz_dev = nullptr, *zl_dev = nullptr;
-    double *dyn = nullptr;     // staging of the host-facing continuous-dynamics call: q, dq, u, ddq_k, ddq, lambda
-    double *dyn_d1 = nullptr;  // ... and of its eight first-derivative arrays
-    double *energy = nullptr;  // [batch][2] output of tg_batch_energy
-    double *lag = nullptr;     // outputs of tg_batch_lagrangian
-    int *dyn_ints = nullptr;   // its status / iteration words (the integrator's own stay untouched)
-    int *seeds = nullptr;      // [2][batch] direction variables of the forward-mode calls
-    double *d1[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    tg::DeviceBuffer<int> d_ints;
+    tg::DeviceBuffer<double> d_dbls;
+    tg::DeviceBuffer<double> q1, q2, p1, p2, lam, u1;
+    tg::DeviceBuffer<double> stage_u, stage_k, stage_qh, stage_lh, f_out;
+    tg::DeviceBuffer<int> iters, status, fallbacks;
+    tg::DeviceBuffer<double> z_dev, hz_dev, zl_dev;
+    tg::DeviceBuffer<double> dyn;     // staging of the host-facing continuous-dynamics call: q, dq, u, ddq_k, ddq, lambda
+    tg::DeviceBuffer<double> dyn_d1;  // ... and of its eight first-derivative arrays
+    tg::DeviceBuffer<double> energy;  // [batch][2] output of tg_batch_energy
+    tg::DeviceBuffer<double> lag;     // outputs of tg_batch_lagrangian
+    tg::DeviceBuffer<int> dyn_ints;   // its status / iteration words (the integrator's own stay untouched)
+    tg::DeviceBuffer<int> seeds;      // [2][batch] direction variables of the forward-mode calls
+    tg::DeviceBuffer<double> d1[12];
     bool have_d1 = false;
-    long long *prof = nullptr; // diagnostic build only (TG_PROFILE)
-    double *snap = nullptr;    // snapshot of (q1,q2,p1,p2,lam,u1)
+    tg::DeviceBuffer<long long> prof; // diagnostic build only (TG_PROFILE)
+    tg::DeviceBuffer<double> snap;    // snapshot of (q1,q2,p1,p2,lam,u1)
     double snap_t1 = 0.0, snap_t2 = 0.0;
     long long total_iters = 0;
     double t1 = 0.0, t2 = 0.0, tolerance = 1.0e-10;
     int predictor = 0;
-    double *dt_dev = nullptr;  // optional non-uniform time base (tg_batch_set_step_sizes)
+    tg::DeviceBuffer<double> dt_dev;  // optional non-uniform time base (tg_batch_set_step_sizes)
     std::vector<double> dt_host;
     int dt_by_trajectory = 0;
     int exact_pivot = 0;       // 1: Newton systems solved with the reference's exact pivot rule (gj_rows_exact)
@@ -137,8 +138,8 @@ struct tg_batch {
     bool timing = false;       // HIP-event timing of the launches: off until tg_batch_timing is called once
     double folded_ms = 0.0;    // launches recycled past TIMING_CAP
     long long folded_n = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-    std::vector<hipEvent_t> pool;
+    std::vector<std::pair<tg::Event, tg::Event>> events;
+    std::vector<tg::Event> pool;
 };
 
 namespace {
@@ -161,15 +162,15 @@ int widths(const tg_batch *b, int field) {
 }
 double *field_ptr(tg_batch *b, int field) {
     switch (field) {
-    case TG_F_Q1: return b->q1;
-    case TG_F_Q2: return b->q2;
-    case TG_F_P1: return b->p1;
-    case TG_F_P2: return b->p2;
-    case TG_F_U1: return b->u1;
-    case TG_F_LAMBDA1: return b->lam;
+    case TG_F_Q1: return b->q1.get();
+    case TG_F_Q2: return b->q2.get();
+    case TG_F_P1: return b->p1.get();
+    case TG_F_P2: return b->p2.get();
+    case TG_F_U1: return b->u1.get();
+    case TG_F_LAMBDA1: return b->lam.get();
     default: break;
     }
-    if (field >= TG_F_Q2_DQ1 && field <= TG_F_L1_DK2) return b->d1[field - TG_F_Q2_DQ1];
+    if (field >= TG_F_Q2_DQ1 && field <= TG_F_L1_DK2) return b->d1[field - TG_F_Q2_DQ1].get();
     return nullptr;
 }
 
@@ -197,21 +198,26 @@ template <int TEAM, int MODE, bool SPRINGS>
 int launch_variant(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
     if (lds > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_run<TEAM, MODE, SPRINGS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_run<TEAM, MODE, SPRINGS>), dim3(grid), dim3(64), lds, b->stream, b->d_prog, A);
+    hipLaunchKernelGGL((k_run<TEAM, MODE, SPRINGS>), dim3(grid), dim3(64), lds, b->stream, b->d_prog.get(), A);
     return TG_SUCCESS;
 }
 
-bool launch_springs(const tg_batch *b) { return b->P.has_cs || b->P.n_springs || b->P.has_plane || b->P.n_wrenches; }
+bool launch_springs(const tg::DevProg &P) { return P.has_cs || P.n_springs || P.has_plane || P.n_wrenches; }
+bool launch_springs(const tg_batch *b) { return launch_springs(b->P); }
+// doubles of LDS that one team of a mode-`mode` kernel keeps (the slice k_run strides its teams by)
+int lds_per_team(const tg::DevProg &P, int mode) {
+    return mode == tg::MODE_DERIV2Z ? P.e_lds_per_team : (mode == tg::MODE_DERIV1 ? P.a_lds_per_team : (mode == tg::MODE_DYN_DERIV1 ? P.g_lds_per_team : P.lds_per_team));
+}
 
 // systems with spring potentials run their own instantiation of every kernel (mvi_core.hpp, Core<TEAM, SPRINGS>)
 template <int TEAM, int MODE>
 int launch_one(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
 #if defined(TG_PROFILE)   // the diagnostic build only instruments the plain kernels of full-wave teams (fewer instantiations)
-    if (TEAM != 64 || b->P.has_cs || b->P.n_springs || b->P.has_plane || b->P.n_wrenches)
+    if (TEAM != 64 || launch_springs(b))
         return fail(TG_ERR_UNSUPPORTED, "the profiling build covers full-wave teams without spring / plane / wrench features");
     return launch_variant<64, MODE, false>(b, A, grid, lds);
 #else
-    return (b->P.has_cs || b->P.n_springs || b->P.has_plane || b->P.n_wrenches) ? launch_variant<TEAM, MODE, true>(b, A, grid, lds) : launch_variant<TEAM, MODE, false>(b, A, grid, lds);
+    return launch_springs(b) ? launch_variant<TEAM, MODE, true>(b, A, grid, lds) : launch_variant<TEAM, MODE, false>(b, A, grid, lds);
 #endif
 }
 
@@ -237,26 +243,25 @@ int launch(tg_batch *b, tg::RunArgs &A) {
     b->mirror_valid = false;
     const int team = b->sys->team, per_block = 64 / team;
     const int grid = ((A.remap_len > 0 ? A.remap_count : A.batch) + per_block - 1) / per_block;
-    const int per_team = A.mode == tg::MODE_DERIV2Z ? b->P.e_lds_per_team : (A.mode == tg::MODE_DERIV1 ? b->P.a_lds_per_team : (A.mode == tg::MODE_DYN_DERIV1 ? b->P.g_lds_per_team : b->P.lds_per_team));
-    const size_t lds = (size_t)per_block * per_team * sizeof(double);
+    const size_t lds = (size_t)per_block * lds_per_team(b->P, A.mode) * sizeof(double);
     if (lds > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident kernel");
     // HIP-event timing is opt-in (the first tg_batch_timing call switches it on): a plain MidpointVI.step() loop creates
     // no events.  When on, at most TIMING_CAP launches are kept; older pairs are recycled (their time is folded into
     // the running totals), and every error path hands the pair back to the pool.
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    tg::Event e0, e1;
+    auto recycle = [&] { b->pool.push_back(std::move(e0)); b->pool.push_back(std::move(e1)); };
     if (b->timing) {
         if (b->events.size() >= tg_batch::TIMING_CAP) {
-            auto old = b->events.front();
             float t = 0.f;
-            if (hipEventSynchronize(old.second) == hipSuccess && hipEventElapsedTime(&t, old.first, old.second) == hipSuccess) { b->folded_ms += t; b->folded_n++; }
+            e0 = std::move(b->events.front().first); e1 = std::move(b->events.front().second);
+            if (hipEventSynchronize(e1.get()) == hipSuccess && hipEventElapsedTime(&t, e0.get(), e1.get()) == hipSuccess) { b->folded_ms += t; b->folded_n++; }
             b->events.erase(b->events.begin());
-            e0 = old.first; e1 = old.second;
-        } else if (b->pool.size() >= 2) { e0 = b->pool.back(); b->pool.pop_back(); e1 = b->pool.back(); b->pool.pop_back(); }
+        } else if (b->pool.size() >= 2) { e0 = std::move(b->pool.back()); b->pool.pop_back(); e1 = std::move(b->pool.back()); b->pool.pop_back(); }
         else {
-            HIP_TRY(hipEventCreate(&e0));
-            if (hipEventCreate(&e1) != hipSuccess) { b->pool.push_back(e0); return fail(TG_ERR_HIP, "hipEventCreate failed"); }
+            HIP_TRY(e0.create());
+            if (e1.create() != hipSuccess) { b->pool.push_back(std::move(e0)); return fail(TG_ERR_HIP, "hipEventCreate failed"); }
         }
-        if (hipEventRecord(e0, b->stream) != hipSuccess) { b->pool.push_back(e0); b->pool.push_back(e1); return fail(TG_ERR_HIP, "hipEventRecord failed"); }
+        if (hipEventRecord(e0.get(), b->stream) != hipSuccess) { recycle(); return fail(TG_ERR_HIP, "hipEventRecord failed"); }
     }
     int rc;
     // a parameter table selects the PAR kernels: the library's specialised one of the mode if it has it, else the generic one
@@ -265,31 +270,30 @@ int launch(tg_batch *b, tg::RunArgs &A) {
         const int i = b->arg_next;
         b->arg_next = (i + 1) % tg_batch::ARG_SLOTS;
         rc = TG_SUCCESS;
-        if (b->arg_used[i] && hipEventSynchronize(b->arg_done[i]) != hipSuccess) rc = fail(TG_ERR_HIP, "hipEventSynchronize failed");
+        if (b->arg_used[i] && hipEventSynchronize(b->arg_done[i].get()) != hipSuccess) rc = fail(TG_ERR_HIP, "hipEventSynchronize failed");
         if (rc == TG_SUCCESS) {
-            b->h_args[i] = A;
-            const int lrc = par ? b->spec_launch_par(A.mode, &b->h_args[i], b->d_args + i, grid, lds, (void *)b->stream, b->par_dev, b->par_group, b->par_stride)
-                                : b->spec_launch(A.mode, &b->h_args[i], b->d_args + i, grid, lds, (void *)b->stream);
+            tg::RunArgs *h = b->h_args.get() + i, *d = b->d_args.get() + i;
+            *h = A;
+            const int lrc = par ? b->spec_launch_par(A.mode, h, d, grid, lds, (void *)b->stream, b->par_dev.get(), b->par_group, b->par_stride)
+                                : b->spec_launch(A.mode, h, d, grid, lds, (void *)b->stream);
             rc = lrc == 0 ? TG_SUCCESS : fail(TG_ERR_HIP, "specialised kernel launch failed");
-            b->arg_used[i] = hipEventRecord(b->arg_done[i], b->stream) == hipSuccess;
+            b->arg_used[i] = hipEventRecord(b->arg_done[i].get(), b->stream) == hipSuccess;
             if (!b->arg_used[i]) hipStreamSynchronize(b->stream);
-            if (par) { b->par_spec_launched_modes |= 1u << A.mode; b->par_spec_launches++; }
-            else { b->spec_launched_modes |= 1u << A.mode; b->spec_launches++; }
+            b->launched[par][1].add(A.mode);
         }
     } else {
-        if (par) { b->par_generic_launched_modes |= 1u << A.mode; b->par_generic_launches++; }
-        else { b->generic_launched_modes |= 1u << A.mode; b->generic_launches++; }
-        rc = par ? tg_detail::launch_par(team, launch_springs(b), b->d_prog, A, tg::ParTable{b->par_dev, b->par_group, b->par_stride}, grid, lds, b->stream)
+        b->launched[par][0].add(A.mode);
+        rc = par ? tg_detail::launch_par(team, launch_springs(b), b->d_prog.get(), A, tg::ParTable{b->par_dev.get(), b->par_group, b->par_stride}, grid, lds, b->stream)
                  : (team == 64 ? launch_team<64>(b, A, grid, lds) : (team == 16 ? launch_team<16>(b, A, grid, lds)
                     : (team == 4 ? launch_team<4>(b, A, grid, lds) : launch_team<1>(b, A, grid, lds))));
     }
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
     if (b->timing) {
-        if (rc != TG_SUCCESS || hipEventRecord(e1, b->stream) != hipSuccess) {
-            b->pool.push_back(e0); b->pool.push_back(e1);
+        if (rc != TG_SUCCESS || hipEventRecord(e1.get(), b->stream) != hipSuccess) {
+            recycle();
             return rc != TG_SUCCESS ? rc : fail(TG_ERR_HIP, "hipEventRecord failed");
         }
-        b->events.emplace_back(e0, e1);
+        b->events.emplace_back(std::move(e0), std::move(e1));
     }
     return rc;
 }
@@ -299,17 +303,15 @@ template <int MODE, bool SPRINGS, class Real>
 int launch_forward_variant(tg_batch *b, const tg::RunArgs &A, size_t lds) {
     if (lds > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_forward<MODE, SPRINGS, Real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_forward<MODE, SPRINGS, Real>), dim3(A.batch), dim3(64), lds, b->stream, b->d_prog, A);
+    hipLaunchKernelGGL((k_forward<MODE, SPRINGS, Real>), dim3(A.batch), dim3(64), lds, b->stream, b->d_prog.get(), A);
     return TG_SUCCESS;
 }
 template <int MODE, class Real>
 int launch_forward_mode(tg_batch *b, const tg::RunArgs &A) {
-    const int per_team = std::max(b->P.lds_per_team, MODE == tg::MODE_DYN_DERIV1 ? b->P.g_lds_per_team : 0);
-    const size_t lds = (size_t)per_team * sizeof(Real);
+    const size_t lds = (size_t)std::max(b->P.lds_per_team, lds_per_team(b->P, MODE)) * sizeof(Real);
     if (lds > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident forward-mode kernel");
-    const bool springs = b->P.has_cs || b->P.n_springs || b->P.has_plane || b->P.n_wrenches;
-    b->generic_launched_modes |= 1u << MODE; b->generic_launches++;      // no forward-mode kernel is ever specialised (tg_batch_info)
-    int rc = springs ? launch_forward_variant<MODE, true, Real>(b, A, lds) : launch_forward_variant<MODE, false, Real>(b, A, lds);
+    b->launched[0][0].add(MODE);      // no forward-mode kernel is ever specialised (tg_batch_info)
+    int rc = launch_springs(b) ? launch_forward_variant<MODE, true, Real>(b, A, lds) : launch_forward_variant<MODE, false, Real>(b, A, lds);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
     return rc;
 }
@@ -338,9 +340,9 @@ int stage_seeds(tg_batch *b, const int32_t *seed1_host, const int32_t *seed2_hos
         if (seed1_host[i] < -1 || seed1_host[i] >= nvar) return fail(TG_ERR_INVALID, "direction variable out of range (q | dq | ddq_k | u)");
         if (seed2_host && (seed2_host[i] < -1 || seed2_host[i] >= nvar)) return fail(TG_ERR_INVALID, "direction variable out of range (q | dq | ddq_k | u)");
     }
-    if (!b->seeds) HIP_TRY(hipMalloc(&b->seeds, 2 * B * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(b->seeds, seed1_host, B * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    if (seed2_host) HIP_TRY(hipMemcpyAsync(b->seeds + B, seed2_host, B * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(b->seeds.ensure(2 * B));
+    HIP_TRY(hipMemcpyAsync(b->seeds.get(), seed1_host, B * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (seed2_host) HIP_TRY(hipMemcpyAsync(b->seeds.get() + B, seed2_host, B * sizeof(int), hipMemcpyHostToDevice, b->stream));
     return TG_SUCCESS;
 }
 
@@ -350,17 +352,10 @@ int stage_seeds(tg_batch *b, const int32_t *seed1_host, const int32_t *seed2_hos
 int ensure_deriv_buffers(tg_batch *b, bool first, bool second) {
     const tg::DevProg &P = b->P;
     const size_t B = (size_t)b->batch;
-    auto dalloc = [&](double **p, size_t n) -> bool {
-        if (*p) return true;
-        return hipMalloc(p, (n ? n : 1) * sizeof(double)) == hipSuccess && hipMemset(*p, 0, (n ? n : 1) * sizeof(double)) == hipSuccess;
-    };
     bool ok = true;
-    if (first) for (int k = 0; k < 12 && ok; k++) {
-        const int var = k % 4, out = k / 4;
-        const size_t rows = var == 0 ? P.nq : (var == 1 ? P.nd : (var == 2 ? P.nu : P.nk));
-        ok = dalloc(&b->d1[k], B * rows * (out == 2 ? P.nc : P.nd));
-    }
-    if (second && ok) ok = dalloc(&b->z_dev, B * P.nX) && dalloc(&b->zl_dev, B * P.nc) && dalloc(&b->hz_dev, B * (size_t)P.d_nrhs * P.d_nrhs);
+    if (first) for (int k = 0; k < 12 && ok; k++) ok = b->d1[k].ensure(B * widths(b, TG_F_Q2_DQ1 + k), true) == hipSuccess;
+    if (second && ok) ok = b->z_dev.ensure(B * P.nX, true) == hipSuccess && b->zl_dev.ensure(B * P.nc, true) == hipSuccess &&
+                           b->hz_dev.ensure(B * (size_t)P.d_nrhs * P.d_nrhs, true) == hipSuccess;
     return ok ? TG_SUCCESS : fail(TG_ERR_HIP, "device allocation failed");
 }
 
@@ -368,15 +363,48 @@ tg::RunArgs base_args(tg_batch *b, int mode) {
     tg::RunArgs A{};
     A.batch = b->batch; A.mode = mode; A.max_iterations = 200;
     A.t1 = b->t1; A.t2 = b->t2; A.tolerance = b->tolerance; A.predictor = b->predictor; A.exact_pivot = b->exact_pivot;
-    A.dt_steps = b->dt_host.empty() ? nullptr : b->dt_dev;
+    A.dt_steps = b->dt_host.empty() ? nullptr : b->dt_dev.get();
     A.dt_period = (b->dt_by_trajectory && !b->dt_host.empty()) ? (int)b->dt_host.size() : 0;
-    A.q1 = b->q1; A.q2 = b->q2; A.p1 = b->p1; A.p2 = b->p2; A.lam = b->lam; A.u1 = b->u1;
-    A.iters = b->iters; A.status = b->status; A.f_out = b->f_out; A.fallbacks = b->fallbacks;
-    A.prof_out = b->prof;
-    for (int i = 0; i < 12; i++) A.d1[i] = b->d1[i];
-    A.z = b->z_dev; A.hz = b->hz_dev;
+    A.q1 = b->q1.get(); A.q2 = b->q2.get(); A.p1 = b->p1.get(); A.p2 = b->p2.get(); A.lam = b->lam.get(); A.u1 = b->u1.get();
+    A.iters = b->iters.get(); A.status = b->status.get(); A.f_out = b->f_out.get(); A.fallbacks = b->fallbacks.get();
+    A.prof_out = b->prof.get();
+    for (int i = 0; i < 12; i++) A.d1[i] = b->d1[i].get();
+    A.z = b->z_dev.get(); A.hz = b->hz_dev.get();
     A.group_size = 1;
     return A;
+}
+
+// the one-step rollout of tg_batch_step / tg_batch_set_from_trajectories: inputs and hints (null: none) in the given device buffers
+tg::RunArgs step_args(tg_batch *b, double dt, int max_iterations, const double *U, const double *K, const double *q2_hint, const double *lam_hint) {
+    tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
+    A.n_steps = 1; A.dt = dt; A.max_iterations = max_iterations;
+    if (!A.dt_period) A.dt_steps = nullptr;      // a by-step list belongs to the rollouts: one step takes the caller's size
+    A.U = U; A.K = K; A.q2_hint = q2_hint; A.lam_hint = lam_hint;
+    return A;
+}
+
+// Staging block of the host-facing continuous-dynamics calls, b->dyn: (q, dq, u, ddq_k) in, (ddq, lambda) out, [batch][width] each.
+// Allocated on first use with the calls' status / iteration words; uploads the inputs the call has (null: none).
+struct DynStage { double *q, *dq, *u, *ddk, *ddq, *lam; };
+int stage_dynamics(tg_batch *b, const double *q_host, const double *dq_host, const double *u_host, const double *ddqk_host, DynStage &s) {
+    const tg::DevProg &P = b->P;
+    const size_t B = (size_t)b->batch, nq = P.nq, nd = P.nd, nk = P.nk, nu = P.nu, nc = P.nc;
+    HIP_TRY(b->dyn.ensure(B * (2 * nq + nu + nk + nd + nc)));
+    HIP_TRY(b->dyn_ints.ensure(2 * B));
+    s.q = b->dyn.get(); s.dq = s.q + B * nq; s.u = s.dq + B * nq; s.ddk = s.u + B * nu; s.ddq = s.ddk + B * nk; s.lam = s.ddq + B * nd;
+    HIP_TRY(hipMemcpyAsync(s.q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(s.dq, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (nu && u_host) HIP_TRY(hipMemcpyAsync(s.u, u_host, B * nu * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (nk && ddqk_host) HIP_TRY(hipMemcpyAsync(s.ddk, ddqk_host, B * nk * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    return TG_SUCCESS;
+}
+
+// the system's own values in the layout of a parameter row (tg::ParTable): inertia [n_bodies][4] | gravity [3] | damping [nd]
+void base_parameter_row(const tg::HostProgram &H, double *row) {
+    const int nb = H.p.n_bodies;
+    std::copy(H.b_inertia.begin(), H.b_inertia.end(), row);
+    for (int k = 0; k < 3; k++) row[4 * nb + k] = H.p.grav[k];
+    for (int i = 0; i < H.p.nd; i++) row[4 * nb + 3 + i] = H.damp.empty() ? 0.0 : H.damp[i];
 }
 
 // DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for trajectory t = s*horizon + k (dsystem.py:229-251):
@@ -523,30 +551,22 @@ tg_batch *tg_batch_create(tg_system *sys, int32_t batch, int32_t device) {
     // all index / constant tables live in two device buffers; bind() points the DevProg into them
     const std::vector<int> &ints = H.ipool;
     const std::vector<double> &dbls = H.dpool;
-    bool ok = hipMalloc(&b->d_ints, ints.size() * sizeof(int)) == hipSuccess &&
-              hipMalloc(&b->d_dbls, dbls.size() * sizeof(double)) == hipSuccess &&
-              hipMemcpy(b->d_ints, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(b->d_dbls, dbls.data(), dbls.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    bool ok = b->d_ints.ensure(ints.size()) == hipSuccess && b->d_dbls.ensure(dbls.size()) == hipSuccess &&
+              hipMemcpy(b->d_ints.get(), ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(b->d_dbls.get(), dbls.data(), dbls.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     tg::DevProg &P = b->P;
-    H.bind(P, b->d_ints, b->d_dbls);
-    if (ok) ok = hipMalloc(&b->d_prog, sizeof(tg::DevProg)) == hipSuccess &&
-                 hipMemcpy(b->d_prog, &P, sizeof(tg::DevProg), hipMemcpyHostToDevice) == hipSuccess;
-    auto dalloc = [&](double **p, size_t n) {
-        if (!ok) return;
-        ok = hipMalloc(p, (n ? n : 1) * sizeof(double)) == hipSuccess && hipMemset(*p, 0, (n ? n : 1) * sizeof(double)) == hipSuccess;
-    };
+    H.bind(P, b->d_ints.get(), b->d_dbls.get());
+    if (ok) ok = b->d_prog.ensure(1) == hipSuccess && hipMemcpy(b->d_prog.get(), &P, sizeof(tg::DevProg), hipMemcpyHostToDevice) == hipSuccess;
+    auto zeroed = [&](auto &buf, size_t n) { ok = ok && buf.ensure(n, true) == hipSuccess; };
     const size_t B = (size_t)batch;
-    dalloc(&b->q1, B * P.nq); dalloc(&b->q2, B * P.nq); dalloc(&b->p1, B * P.nd); dalloc(&b->p2, B * P.nd);
-    dalloc(&b->lam, B * P.nc); dalloc(&b->u1, B * P.nu);
-    dalloc(&b->stage_u, B * P.nu); dalloc(&b->stage_k, B * P.nk); dalloc(&b->stage_qh, B * P.nd); dalloc(&b->stage_lh, B * P.nc);
-    dalloc(&b->f_out, B * P.nf);
+    zeroed(b->q1, B * P.nq); zeroed(b->q2, B * P.nq); zeroed(b->p1, B * P.nd); zeroed(b->p2, B * P.nd);
+    zeroed(b->lam, B * P.nc); zeroed(b->u1, B * P.nu); zeroed(b->f_out, B * P.nf);
+    zeroed(b->stage_u, B * P.nu); zeroed(b->stage_k, B * P.nk); zeroed(b->stage_qh, B * P.nd); zeroed(b->stage_lh, B * P.nc);
     // derivative outputs (d1[12], z, hz) are allocated on first use: ensure_deriv_buffers()
-    dalloc(&b->snap, B * (2 * (size_t)P.nq + 2 * (size_t)P.nd + P.nc + P.nu));
-    if (ok) ok = hipMalloc(&b->iters, B * sizeof(int)) == hipSuccess && hipMalloc(&b->status, B * sizeof(int)) == hipSuccess &&
-                 hipMemset(b->iters, 0, B * sizeof(int)) == hipSuccess && hipMemset(b->status, 0, B * sizeof(int)) == hipSuccess;
-    if (ok) ok = hipMalloc(&b->fallbacks, B * sizeof(int)) == hipSuccess && hipMemset(b->fallbacks, 0, B * sizeof(int)) == hipSuccess;
+    zeroed(b->snap, B * (2 * (size_t)P.nq + 2 * (size_t)P.nd + P.nc + P.nu));
+    zeroed(b->iters, B); zeroed(b->status, B); zeroed(b->fallbacks, B);
 #if defined(TG_PROFILE)
-    if (ok) ok = hipMalloc(&b->prof, 16 * sizeof(long long)) == hipSuccess && hipMemset(b->prof, 0, 16 * sizeof(long long)) == hipSuccess;
+    zeroed(b->prof, 16);
 #endif
     if (ok) ok = hipStreamCreate(&b->stream) == hipSuccess;
     if (!ok) { fail(TG_ERR_HIP, "device allocation failed"); tg_batch_destroy(b); return nullptr; }
@@ -557,18 +577,9 @@ void tg_batch_destroy(tg_batch *b) {
     if (!b) return;
     hipSetDevice(b->device);
     if (b->stream) hipStreamSynchronize(b->stream);
-    for (auto &e : b->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    for (auto &e : b->pool) hipEventDestroy(e);
-    void *ptrs[] = {b->d_args, b->dt_dev, b->par_dev, b->d_prog, b->d_ints, b->d_dbls, b->q1, b->q2, b->p1, b->p2, b->lam, b->u1, b->stage_u, b->stage_k,
-                    b->stage_qh, b->stage_lh, b->f_out, b->iters, b->status, b->fallbacks, b->snap, b->z_dev, b->hz_dev, b->zl_dev, b->dyn, b->dyn_ints, b->seeds, b->dyn_d1, b->energy, b->lag,
-                    b->d1[0], b->d1[1], b->d1[2], b->d1[3], b->d1[4], b->d1[5], b->d1[6], b->d1[7], b->d1[8], b->d1[9], b->d1[10], b->d1[11]};
-    for (void *p : ptrs) if (p) hipFree(p);
-    if (b->h_args) hipHostFree(b->h_args);
-    if (b->io_host) hipHostFree(b->io_host);
-    for (auto &e : b->arg_done) if (e) hipEventDestroy(e);
     if (b->stream && b->own_stream) hipStreamDestroy(b->stream);
     if (b->spec_lib) dlclose(b->spec_lib);
-    delete b;
+    delete b;      // every buffer and event of the batch frees itself
 }
 
 int tg_batch_set_tolerance(tg_batch *b, double tolerance) {
@@ -609,7 +620,7 @@ int tg_batch_get(tg_batch *b, int32_t field, double *host) {
     if (b->mirror_valid && (field == TG_F_Q2 || field == TG_F_P2 || field == TG_F_LAMBDA1)) {   // answered from the last step's mirror
         const tg::DevProg &P = b->P;
         const size_t B = (size_t)b->batch;
-        const double *m = b->io_host + b->io_in + (field == TG_F_Q2 ? 0 : (field == TG_F_P2 ? B * P.nq : B * (P.nq + P.nd)));
+        const double *m = b->io_host.get() + b->io_in + (field == TG_F_Q2 ? 0 : (field == TG_F_P2 ? B * P.nq : B * (P.nq + P.nd)));
         std::memcpy(host, m, B * w * sizeof(double));
         return TG_SUCCESS;
     }
@@ -624,8 +635,7 @@ int tg_batch_calc_p2(tg_batch *b) {
     if (b->t2 == b->t1) return fail(TG_ERR_STATE, "calc_p2 needs t2 != t1");
     HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_CALC_P2);
-    int rc = launch(b, A);
-    if (rc) return rc;
+    if (int rc = launch(b, A)) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -635,9 +645,8 @@ int tg_batch_calc_f(tg_batch *b, double *f_host) {
     if (b->t2 == b->t1) return fail(TG_ERR_STATE, "calc_f needs t2 != t1");
     HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_CALC_F);
-    int rc = launch(b, A);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f_host, b->f_out, (size_t)b->batch * b->P.nf * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (int rc = launch(b, A)) return rc;
+    HIP_TRY(hipMemcpyAsync(f_host, b->f_out.get(), (size_t)b->batch * b->P.nf * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -648,7 +657,7 @@ int tg_batch_calc_f(tg_batch *b, double *f_host) {
 int tg_batch_solver_fallbacks(tg_batch *b, int32_t *fallbacks_out) {
     if (!b || !fallbacks_out) return fail(TG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipMemcpyAsync(fallbacks_out, b->fallbacks, (size_t)b->batch * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(fallbacks_out, b->fallbacks.get(), (size_t)b->batch * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -658,14 +667,14 @@ int tg_batch_status(tg_batch *b, int32_t *iterations_out, int32_t *status_out) {
     if (b->mirror_valid) {
         const tg::DevProg &P = b->P;
         const size_t B = (size_t)b->batch;
-        const int32_t *m = reinterpret_cast<const int32_t *>(b->io_host + b->io_in + B * (P.nq + P.nd + P.nc));
+        const int32_t *m = reinterpret_cast<const int32_t *>(b->io_host.get() + b->io_in + B * (P.nq + P.nd + P.nc));
         if (iterations_out) std::memcpy(iterations_out, m, B * sizeof(int32_t));
         if (status_out) std::memcpy(status_out, m + B, B * sizeof(int32_t));
         return TG_SUCCESS;
     }
     HIP_TRY(hipSetDevice(b->device));
-    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, b->iters, (size_t)b->batch * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, b->status, (size_t)b->batch * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, b->iters.get(), (size_t)b->batch * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, b->status.get(), (size_t)b->batch * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -684,61 +693,33 @@ int tg_batch_step(tg_batch *b, double t2_new, const double *u1_host, const doubl
     // iterations, status) into it beside the device state -- one launch on the stream, no copy engine, no packing kernel.
     const size_t n_in = B * ((size_t)P.nu + P.nk + P.nd + P.nc), n_out = B * ((size_t)P.nq + P.nd + P.nc) + B;   // 2 B ints = B doubles
     // (gated on the trajectory count: the path was measured at B = 1 .. 64 only; larger batches take the copy engine below)
-    if (B <= 64 && (n_in + n_out) * sizeof(double) <= (1u << 20)) {
+    const bool pinned = B <= 64 && (n_in + n_out) * sizeof(double) <= (1u << 20);
+    double *du, *dk, *dq, *dl;       // where the kernel reads (u1, k2, hints)
+    if (pinned) {
         if (!b->io_host) {
-            if (hipHostMalloc(&b->io_host, (n_in + n_out) * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-                hipHostGetDevicePointer(reinterpret_cast<void **>(&b->io_dev), b->io_host, 0) != hipSuccess)
-                return fail(TG_ERR_HIP, "allocation of the step staging block failed");
+            if (b->io_host.ensure(n_in + n_out, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+                hipHostGetDevicePointer(reinterpret_cast<void **>(&b->io_dev), b->io_host.get(), 0) != hipSuccess) { b->io_host.reset(); return fail(TG_ERR_HIP, "allocation of the step staging block failed"); }
             b->io_in = n_in; b->io_out = n_out;
         }
-        double *hu = b->io_host, *hk = hu + B * P.nu, *hq = hk + B * P.nk, *hl = hq + B * P.nd;
-        double *du = b->io_dev, *dk = du + B * P.nu, *dq = dk + B * P.nk, *dl = dq + B * P.nd;    // the same block as the device sees it
+        double *hu = b->io_host.get(), *hk = hu + B * P.nu, *hq = hk + B * P.nk, *hl = hq + B * P.nd;
+        du = b->io_dev; dk = du + B * P.nu; dq = dk + B * P.nk; dl = dq + B * P.nd;
         if (P.nu) std::memcpy(hu, u1_host, B * P.nu * sizeof(double));
         if (P.nk) std::memcpy(hk, k2_host, B * P.nk * sizeof(double));
         if (q2_hint_host) std::memcpy(hq, q2_hint_host, B * P.nd * sizeof(double));
         if (want_lh) std::memcpy(hl, lambda_hint_host, B * P.nc * sizeof(double));
-        tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
-        A.n_steps = 1; A.dt = t2_new - b->t2; A.max_iterations = max_iterations;
-        if (!A.dt_period) A.dt_steps = nullptr;      // a by-step list belongs to the rollouts: one step takes the caller's size
-        A.U = du; A.K = dk;
-        A.q2_hint = q2_hint_host ? dq : nullptr;
-        A.lam_hint = want_lh ? dl : nullptr;
-        A.mirror = b->io_dev + n_in;
-        int rc = launch(b, A);
-        if (rc) return rc;
-        b->t1 = b->t2; b->t2 = t2_new;
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        b->mirror_valid = true;
-        return tg_batch_status(b, iterations_out, status_out);
-    }
-    if (P.nu) HIP_TRY(hipMemcpyAsync(b->stage_u, u1_host, B * P.nu * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (P.nk) HIP_TRY(hipMemcpyAsync(b->stage_k, k2_host, B * P.nk * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (q2_hint_host) HIP_TRY(hipMemcpyAsync(b->stage_qh, q2_hint_host, B * P.nd * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (want_lh) HIP_TRY(hipMemcpyAsync(b->stage_lh, lambda_hint_host, B * P.nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
-    A.n_steps = 1; A.dt = t2_new - b->t2; A.max_iterations = max_iterations;
-    if (!A.dt_period) A.dt_steps = nullptr;      // a by-step list belongs to the rollouts: one step takes the caller's size
-    A.U = b->stage_u; A.K = b->stage_k;
-    A.q2_hint = q2_hint_host ? b->stage_qh : nullptr;
-    A.lam_hint = want_lh ? b->stage_lh : nullptr;
-    int rc = launch(b, A);
-    if (rc) return rc;
-    b->t1 = b->t2; b->t2 = t2_new;
-    return tg_batch_status(b, iterations_out, status_out);
-}
-
-// t1, t2 after n_steps steps from t2 with the uniform step dt or the batch's step-size list
-static int advance_times(tg_batch *b, int n_steps, double dt) {
-    if (!b->dt_host.empty() && !b->dt_by_trajectory) {
-        if ((size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list of tg_batch_set_step_sizes");
-        double t = b->t2, tp = b->t2;
-        for (int k = 0; k < n_steps; k++) { tp = t; t += b->dt_host[k]; }
-        b->t1 = tp; b->t2 = t;
     } else {
-        b->t1 = b->t2 + (n_steps - 1) * dt;
-        b->t2 = b->t2 + n_steps * dt;
+        du = b->stage_u.get(); dk = b->stage_k.get(); dq = b->stage_qh.get(); dl = b->stage_lh.get();
+        if (P.nu) HIP_TRY(hipMemcpyAsync(du, u1_host, B * P.nu * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (P.nk) HIP_TRY(hipMemcpyAsync(dk, k2_host, B * P.nk * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (q2_hint_host) HIP_TRY(hipMemcpyAsync(dq, q2_hint_host, B * P.nd * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (want_lh) HIP_TRY(hipMemcpyAsync(dl, lambda_hint_host, B * P.nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
     }
-    return TG_SUCCESS;
+    tg::RunArgs A = step_args(b, t2_new - b->t2, max_iterations, du, dk, q2_hint_host ? dq : nullptr, want_lh ? dl : nullptr);
+    if (pinned) A.mirror = b->io_dev + n_in;
+    if (int rc = launch(b, A)) return rc;
+    b->t1 = b->t2; b->t2 = t2_new;
+    if (pinned) { HIP_TRY(hipStreamSynchronize(b->stream)); b->mirror_valid = true; }
+    return tg_batch_status(b, iterations_out, status_out);
 }
 
 int tg_batch_set_step_sizes(tg_batch *b, int32_t count, const double *dt_host, int32_t by_trajectory) {
@@ -750,41 +731,45 @@ int tg_batch_set_step_sizes(tg_batch *b, int32_t count, const double *dt_host, i
     }
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));          // a launch in flight may still read the old list
-    double *fresh = nullptr;
-    if (count > 0) {
-        HIP_TRY(hipMalloc(&fresh, sizeof(double) * (size_t)count));
-        if (hipMemcpy(fresh, dt_host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(TG_ERR_HIP, "copy of the step-size list failed");
-        }
-    }
-    if (b->dt_dev) (void)hipFree(b->dt_dev);
-    b->dt_dev = fresh;
+    tg::DeviceBuffer<double> fresh;
+    if (count > 0) HIP_TRY(fresh.ensure((size_t)count));
+    if (count > 0 && hipMemcpy(fresh.get(), dt_host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(TG_ERR_HIP, "copy of the step-size list failed");
+    b->dt_dev = std::move(fresh);
     if (count > 0) b->dt_host.assign(dt_host, dt_host + count); else b->dt_host.clear();
     b->dt_by_trajectory = (count > 0 && by_trajectory) ? 1 : 0;
     return TG_SUCCESS;
 }
 
-// a by-trajectory list belongs to one-step batches: every step of a longer rollout would take the trajectory's size while the
-// times advance by the scalar
-static bool refuse_by_trajectory(const tg_batch *b, int n_steps) {
-    return n_steps > 1 && b->dt_by_trajectory;      // (set only with a list)
+// What the three rollouts share: the step-size-list refusals, the launch and the new times.  A: base_args plus the caller's buffers.
+static int run_rollout(tg_batch *b, tg::RunArgs &A, int n_steps, double dt, int max_iterations) {
+    const bool by_step = !b->dt_host.empty() && !b->dt_by_trajectory;
+    // a by-trajectory list (set only with a list) belongs to one-step batches: every step of a longer rollout would take the
+    // trajectory's size while the times advance by the scalar
+    if (n_steps > 1 && b->dt_by_trajectory) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
+    if (by_step && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
+    if (!A.Kproj && ((b->P.nu && !A.U) || (b->P.nk && !A.K))) return fail(TG_ERR_INVALID, "U / K device buffers required");   // open loop
+    HIP_TRY(hipSetDevice(b->device));
+    A.n_steps = n_steps; A.dt = dt; A.max_iterations = max_iterations;
+    if (int rc = launch(b, A)) return rc;
+    // t1, t2 after n_steps steps from t2 with the uniform step dt or the batch's step-size list
+    if (by_step) {
+        double t = b->t2;
+        for (int k = 0; k < n_steps; k++) { b->t1 = t; t += b->dt_host[k]; }
+        b->t2 = t;
+    } else {
+        b->t1 = b->t2 + (n_steps - 1) * dt;
+        b->t2 = b->t2 + n_steps * dt;
+    }
+    return TG_SUCCESS;
 }
 
 int tg_batch_rollout(tg_batch *b, int32_t n_steps, double dt, const double *U_dev, const double *K_dev, double *X_dev,
                      int32_t max_iterations) {
     if (!b || n_steps <= 0 || dt == 0.0) return fail(TG_ERR_INVALID, "bad arguments");
-    if (refuse_by_trajectory(b, n_steps)) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
-    if (!b->dt_host.empty() && !b->dt_by_trajectory && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
-    const tg::DevProg &P = b->P;
-    if ((P.nu && !U_dev) || (P.nk && !K_dev)) return fail(TG_ERR_INVALID, "U / K device buffers required");
-    HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
-    A.n_steps = n_steps; A.dt = dt; A.max_iterations = max_iterations;
     A.U = U_dev; A.K = K_dev; A.X = X_dev;
-    int rc = launch(b, A);
-    if (rc) return rc;
-    return advance_times(b, n_steps, dt);
+    return run_rollout(b, A, n_steps, dt, max_iterations);
 }
 
 int tg_batch_rollout_closed_loop(tg_batch *b, int32_t n_steps, double dt, const double *Kproj_dev, int32_t group_size,
@@ -792,15 +777,9 @@ int tg_batch_rollout_closed_loop(tg_batch *b, int32_t n_steps, double dt, const 
                                  int32_t max_iterations) {
     if (!b || n_steps <= 0 || dt == 0.0 || !Kproj_dev || !bX_dev || !bU_dev || group_size <= 0)
         return fail(TG_ERR_INVALID, "bad arguments");
-    if (refuse_by_trajectory(b, n_steps)) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
-    if (!b->dt_host.empty() && !b->dt_by_trajectory && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
-    HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
-    A.n_steps = n_steps; A.dt = dt; A.max_iterations = max_iterations;
     A.Kproj = Kproj_dev; A.bX = bX_dev; A.bU = bU_dev; A.Uout = U_dev; A.group_size = group_size; A.X = X_dev;
-    int rc = launch(b, A);
-    if (rc) return rc;
-    return advance_times(b, n_steps, dt);
+    return run_rollout(b, A, n_steps, dt, max_iterations);
 }
 
 int tg_batch_rollout_closed_loop_subset(tg_batch *b, int32_t n_trajectories, int32_t n_steps, double dt, const double *Kproj_dev,
@@ -809,17 +788,11 @@ int tg_batch_rollout_closed_loop_subset(tg_batch *b, int32_t n_trajectories, int
     if (!b || n_steps <= 0 || dt == 0.0 || !Kproj_dev || !bX_dev || !bU_dev || group_size <= 0 || n_trajectories <= 0 ||
         n_trajectories > b->batch)
         return fail(TG_ERR_INVALID, "bad arguments");
-    if (refuse_by_trajectory(b, n_steps)) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
-    if (!b->dt_host.empty() && !b->dt_by_trajectory && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "rollout longer than the step-size list");
-    HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
     A.batch = n_trajectories;
-    A.n_steps = n_steps; A.dt = dt; A.max_iterations = max_iterations;
     A.Kproj = Kproj_dev; A.bX = bX_dev; A.bU = bU_dev; A.Uout = U_dev; A.group_size = group_size; A.X = X_dev;
     A.group_map = group_select_dev;
-    int rc = launch(b, A);
-    if (rc) return rc;
-    return advance_times(b, n_steps, dt);
+    return run_rollout(b, A, n_steps, dt, max_iterations);
 }
 
 int tg_batch_rollout_stats(tg_batch *b, int64_t *total_iterations, int32_t *n_failed) {
@@ -837,13 +810,13 @@ int tg_batch_rollout_stats(tg_batch *b, int64_t *total_iterations, int32_t *n_fa
 static int snapshot_copy(tg_batch *b, bool save) {
     const tg::DevProg &P = b->P;
     const size_t B = (size_t)b->batch;
-    double *fields[6] = {b->q1, b->q2, b->p1, b->p2, b->lam, b->u1};
+    double *fields[6] = {b->q1.get(), b->q2.get(), b->p1.get(), b->p2.get(), b->lam.get(), b->u1.get()};
     const size_t w[6] = {(size_t)P.nq, (size_t)P.nq, (size_t)P.nd, (size_t)P.nd, (size_t)P.nc, (size_t)P.nu};
     size_t off = 0;
     for (int i = 0; i < 6; i++) {
         if (w[i]) {
-            double *dst = save ? b->snap + off : fields[i];
-            const double *src = save ? fields[i] : b->snap + off;
+            double *dst = save ? b->snap.get() + off : fields[i];
+            const double *src = save ? fields[i] : b->snap.get() + off;
             HIP_TRY(hipMemcpyAsync(dst, src, B * w[i] * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
         }
         off += B * w[i];
@@ -872,7 +845,7 @@ int tg_batch_profile(tg_batch *b, int64_t out[16]) {
     if (!b->prof) return fail(TG_ERR_UNSUPPORTED, "library was not built with TG_PROFILE");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipMemcpy(out, b->prof, 16 * sizeof(long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, b->prof.get(), 16 * sizeof(long long), hipMemcpyDeviceToHost));
     return TG_SUCCESS;
 }
 
@@ -880,11 +853,9 @@ int tg_batch_deriv1(tg_batch *b) {
     if (!b) return fail(TG_ERR_INVALID, "null batch");
     if (b->t2 == b->t1) return fail(TG_ERR_STATE, "Integrator has not solved the next time step yet.");
     HIP_TRY(hipSetDevice(b->device));
-    int rc = ensure_deriv_buffers(b, true, false);
-    if (rc) return rc;
+    if (int rc = ensure_deriv_buffers(b, true, false)) return rc;
     tg::RunArgs A = base_args(b, tg::MODE_DERIV1);
-    rc = launch(b, A);
-    if (rc) return rc;
+    if (int rc = launch(b, A)) return rc;
     HIP_TRY(hipStreamSynchronize(b->stream));
     b->have_d1 = true;
     return TG_SUCCESS;
@@ -892,18 +863,7 @@ int tg_batch_deriv1(tg_batch *b) {
 
 int tg_batch_deriv2_contract(tg_batch *b, const double *z_host, double *hz_host) {
     if (!b || !z_host || !hz_host) return fail(TG_ERR_INVALID, "null argument");
-    if (b->P.n_true_springs) return fail(TG_ERR_UNSUPPORTED, "V_dqdqdq() is undefined for LinearSpring (as in the reference): no second derivatives");
-    if (b->t2 == b->t1) return fail(TG_ERR_STATE, "Integrator has not solved the next time step yet.");
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch, R = (size_t)b->P.d_nrhs;
-    if (int rc0 = ensure_deriv_buffers(b, false, true)) return rc0;
-    HIP_TRY(hipMemcpyAsync(b->z_dev, z_host, B * b->P.nX * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    tg::RunArgs A = base_args(b, tg::MODE_DERIV2Z);
-    int rc = launch(b, A);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(hz_host, b->hz_dev, B * R * R * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return TG_SUCCESS;
+    return tg_batch_deriv2_contract_lambda(b, z_host, nullptr, hz_host);
 }
 
 int tg_batch_deriv2_contract_lambda(tg_batch *b, const double *z_host, const double *zlambda_host, double *hz_host) {
@@ -913,14 +873,13 @@ int tg_batch_deriv2_contract_lambda(tg_batch *b, const double *z_host, const dou
     HIP_TRY(hipSetDevice(b->device));
     const size_t B = (size_t)b->batch, R = (size_t)b->P.d_nrhs;
     if (int rc0 = ensure_deriv_buffers(b, false, true)) return rc0;
-    if (z_host) HIP_TRY(hipMemcpyAsync(b->z_dev, z_host, B * b->P.nX * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    else HIP_TRY(hipMemsetAsync(b->z_dev, 0, B * b->P.nX * sizeof(double), b->stream));
-    if (zlambda_host && b->P.nc) HIP_TRY(hipMemcpyAsync(b->zl_dev, zlambda_host, B * b->P.nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (z_host) HIP_TRY(hipMemcpyAsync(b->z_dev.get(), z_host, B * b->P.nX * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    else HIP_TRY(hipMemsetAsync(b->z_dev.get(), 0, B * b->P.nX * sizeof(double), b->stream));
+    if (zlambda_host && b->P.nc) HIP_TRY(hipMemcpyAsync(b->zl_dev.get(), zlambda_host, B * b->P.nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
     tg::RunArgs A = base_args(b, tg::MODE_DERIV2Z);
-    A.zl = (zlambda_host && b->P.nc) ? b->zl_dev : nullptr;
-    int rc = launch(b, A);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(hz_host, b->hz_dev, B * R * R * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    A.zl = (zlambda_host && b->P.nc) ? b->zl_dev.get() : nullptr;
+    if (int rc = launch(b, A)) return rc;
+    HIP_TRY(hipMemcpyAsync(hz_host, b->hz_dev.get(), B * R * R * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -931,35 +890,31 @@ int tg_batch_dynamics_device(tg_batch *b, const double *q_dev, const double *dq_
     const tg::DevProg &P = b->P;
     if ((P.nu && !u_dev) || (P.nk && !ddqk_dev) || (P.nc && !lambda_dev)) return fail(TG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    if (!b->dyn_ints) HIP_TRY(hipMalloc(&b->dyn_ints, 2 * (size_t)b->batch * sizeof(int)));
+    HIP_TRY(b->dyn_ints.ensure(2 * (size_t)b->batch));
     tg::RunArgs A = base_args(b, tg::MODE_DYNAMICS);
     // the state is an argument of this call: nothing of the integrator (q1, q2, p, lambda1, status) is touched
     A.q1 = A.q2 = const_cast<double *>(q_dev);
-    A.u1 = const_cast<double *>(u_dev ? u_dev : b->u1);
+    A.u1 = const_cast<double *>(u_dev ? u_dev : b->u1.get());
     A.dq_in = dq_dev; A.ddqk_in = ddqk_dev; A.ddq_out = ddq_dev; A.lam_out = lambda_dev;
-    A.iters = b->dyn_ints; A.status = status_dev ? status_dev : b->dyn_ints + b->batch;
+    A.iters = b->dyn_ints.get(); A.status = status_dev ? status_dev : b->dyn_ints.get() + b->batch;
     return launch(b, A);
 }
 
 static int lagrangian_host(tg_batch *b, const double *q_host, const double *dq_host, const int32_t *seed1_host, const int32_t *seed2_host, double *first_host, double *second_host) {
     if (!b || !q_host || !dq_host || !first_host || !second_host) return fail(TG_ERR_INVALID, "null argument");
-    const tg::DevProg &P = b->P;
     HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch, nq = P.nq;
-    const size_t in_total = B * (2 * nq + P.nu + P.nk + P.nd + P.nc), out_total = B * nq * (2 + 3 * nq);
-    if (!b->dyn) HIP_TRY(hipMalloc(&b->dyn, (in_total ? in_total : 1) * sizeof(double)));
-    if (!b->dyn_ints) HIP_TRY(hipMalloc(&b->dyn_ints, 2 * B * sizeof(int)));
-    if (!b->lag) HIP_TRY(hipMalloc(&b->lag, (out_total ? out_total : 1) * sizeof(double)));
-    double *q = b->dyn, *dq = q + B * nq, *o1 = b->lag, *o2 = o1 + 2 * B * nq;
-    HIP_TRY(hipMemcpyAsync(q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(dq, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemsetAsync(b->lag, 0, out_total * sizeof(double), b->stream));     // the kernel accumulates
+    const size_t B = (size_t)b->batch, nq = b->P.nq, out_total = B * nq * (2 + 3 * nq);
+    DynStage s;
+    if (int rc = stage_dynamics(b, q_host, dq_host, nullptr, nullptr, s)) return rc;
+    HIP_TRY(b->lag.ensure(out_total));
+    double *o1 = b->lag.get(), *o2 = o1 + 2 * B * nq;
+    HIP_TRY(hipMemsetAsync(o1, 0, out_total * sizeof(double), b->stream));     // the kernel accumulates
     tg::RunArgs A = base_args(b, tg::MODE_LAGRANGIAN);
-    A.q1 = A.q2 = q; A.dq_in = dq; A.lag1_out = o1; A.lag2_out = o2;
-    A.iters = b->dyn_ints; A.status = b->dyn_ints + b->batch;
+    A.q1 = A.q2 = s.q; A.dq_in = s.dq; A.lag1_out = o1; A.lag2_out = o2;
+    A.iters = b->dyn_ints.get(); A.status = b->dyn_ints.get() + b->batch;
     if (seed1_host) {
         if (int rc = stage_seeds(b, seed1_host, seed2_host)) return rc;
-        A.seed1 = b->seeds; A.seed2 = seed2_host ? b->seeds + B : nullptr;
+        A.seed1 = b->seeds.get(); A.seed2 = seed2_host ? b->seeds.get() + B : nullptr;
         if (int rc = launch_forward(b, A, seed2_host ? 2 : 1)) return rc;
     } else if (int rc = launch(b, A)) return rc;
     HIP_TRY(hipMemcpyAsync(first_host, o1, 2 * B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
@@ -985,21 +940,16 @@ int tg_batch_set_predictor(tg_batch *b, int32_t mode) {
 
 int tg_batch_energy(tg_batch *b, const double *q_host, const double *dq_host, double *energy_host) {
     if (!b || !q_host || !dq_host || !energy_host) return fail(TG_ERR_INVALID, "null argument");
-    const tg::DevProg &P = b->P;
     HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch, nq = P.nq;
-    const size_t in_total = B * (2 * nq + P.nu + P.nk + P.nd + P.nc);   // the staging block of the dynamics calls (>= 2 B nq + 2 B)
-    if (!b->dyn) HIP_TRY(hipMalloc(&b->dyn, (in_total ? in_total : 1) * sizeof(double)));
-    if (!b->dyn_ints) HIP_TRY(hipMalloc(&b->dyn_ints, 2 * B * sizeof(int)));
-    if (!b->energy) HIP_TRY(hipMalloc(&b->energy, 2 * B * sizeof(double)));
-    double *q = b->dyn, *dq = q + B * nq;
-    HIP_TRY(hipMemcpyAsync(q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(dq, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    const size_t B = (size_t)b->batch;
+    DynStage s;
+    if (int rc = stage_dynamics(b, q_host, dq_host, nullptr, nullptr, s)) return rc;
+    HIP_TRY(b->energy.ensure(2 * B));
     tg::RunArgs A = base_args(b, tg::MODE_ENERGY);
-    A.q1 = A.q2 = q; A.dq_in = dq; A.energy_out = b->energy;
-    A.iters = b->dyn_ints; A.status = b->dyn_ints + b->batch;
+    A.q1 = A.q2 = s.q; A.dq_in = s.dq; A.energy_out = b->energy.get();
+    A.iters = b->dyn_ints.get(); A.status = b->dyn_ints.get() + b->batch;
     if (int rc = launch(b, A)) return rc;
-    HIP_TRY(hipMemcpyAsync(energy_host, b->energy, 2 * B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(energy_host, b->energy.get(), 2 * B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -1010,13 +960,13 @@ static int dyn_deriv1_device(tg_batch *b, const double *q_dev, const double *dq_
     const tg::DevProg &P = b->P;
     if ((P.nu && !u_dev) || (P.nk && !ddqk_dev)) return fail(TG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    if (!b->dyn_ints) HIP_TRY(hipMalloc(&b->dyn_ints, 2 * (size_t)b->batch * sizeof(int)));
+    HIP_TRY(b->dyn_ints.ensure(2 * (size_t)b->batch));
     tg::RunArgs A = base_args(b, tg::MODE_DYN_DERIV1);
     A.q1 = A.q2 = const_cast<double *>(q_dev);
-    A.u1 = const_cast<double *>(u_dev ? u_dev : b->u1);
+    A.u1 = const_cast<double *>(u_dev ? u_dev : b->u1.get());
     A.dq_in = dq_dev; A.ddqk_in = ddqk_dev; A.ddq_out = nullptr; A.lam_out = nullptr;
     for (int g = 0; g < 8; g++) A.g1[g] = out_dev[g];
-    A.iters = b->dyn_ints; A.status = status_dev ? status_dev : b->dyn_ints + b->batch;
+    A.iters = b->dyn_ints.get(); A.status = status_dev ? status_dev : b->dyn_ints.get() + b->batch;
     if (seed_dev) { A.seed1 = seed_dev; return launch_forward(b, A, 1); }
     return launch(b, A);
 }
@@ -1033,30 +983,20 @@ static int dyn_deriv1_host(tg_batch *b, const double *q_host, const double *dq_h
     if ((P.nu && !u_host) || (P.nk && !ddqk_host)) return fail(TG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
     const size_t B = (size_t)b->batch, nq = P.nq, nd = P.nd, nk = P.nk, nu = P.nu, nc = P.nc;
-    const size_t in_total = B * (2 * nq + nu + nk + nd + nc);
-    if (!b->dyn) HIP_TRY(hipMalloc(&b->dyn, (in_total ? in_total : 1) * sizeof(double)));
+    DynStage s;
+    if (int rc = stage_dynamics(b, q_host, dq_host, u_host, ddqk_host, s)) return rc;
     const size_t rows[4] = {nq, nq, nk, nu};
-    size_t out_total = 0;
-    for (int g = 0; g < 8; g++) out_total += B * rows[g & 3] * (g < 4 ? nd : nc);
-    if (!b->dyn_d1) HIP_TRY(hipMalloc(&b->dyn_d1, (out_total ? out_total : 1) * sizeof(double)));
-    double *q = b->dyn, *dq = q + B * nq, *u = dq + B * nq, *ddk = u + B * nu;
-    HIP_TRY(hipMemcpyAsync(q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(dq, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (nu) HIP_TRY(hipMemcpyAsync(u, u_host, B * nu * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (nk) HIP_TRY(hipMemcpyAsync(ddk, ddqk_host, B * nk * sizeof(double), hipMemcpyHostToDevice, b->stream));
     double *host[8] = {f_dq, f_ddq, f_dddk, f_du, lambda_dq, lambda_ddq, lambda_dddk, lambda_du};
-    double *dev[8];
-    size_t off = 0, cnt[8];
-    for (int g = 0; g < 8; g++) {
-        cnt[g] = B * rows[g & 3] * (g < 4 ? nd : nc);
-        dev[g] = (host[g] && cnt[g]) ? b->dyn_d1 + off : nullptr;
-        off += cnt[g];
-    }
+    size_t cnt[8], out_total = 0;
+    for (int g = 0; g < 8; g++) out_total += cnt[g] = B * rows[g & 3] * (g < 4 ? nd : nc);
+    HIP_TRY(b->dyn_d1.ensure(out_total));
+    double *dev[8], *next = b->dyn_d1.get();
+    for (int g = 0; g < 8; g++) { dev[g] = (host[g] && cnt[g]) ? next : nullptr; next += cnt[g]; }
     if (seed_host) { if (int rc = stage_seeds(b, seed_host, nullptr)) return rc; }
-    if (int rc = dyn_deriv1_device(b, q, dq, nu ? u : nullptr, nk ? ddk : nullptr, seed_host ? b->seeds : nullptr, dev, nullptr)) return rc;
+    if (int rc = dyn_deriv1_device(b, s.q, s.dq, nu ? s.u : nullptr, nk ? s.ddk : nullptr, seed_host ? b->seeds.get() : nullptr, dev, nullptr)) return rc;
     for (int g = 0; g < 8; g++)
         if (dev[g]) HIP_TRY(hipMemcpyAsync(host[g], dev[g], cnt[g] * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (status_host) HIP_TRY(hipMemcpyAsync(status_host, b->dyn_ints + B, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_host) HIP_TRY(hipMemcpyAsync(status_host, b->dyn_ints.get() + B, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
@@ -1078,42 +1018,37 @@ int tg_batch_dynamics(tg_batch *b, const double *q_host, const double *dq_host, 
     const tg::DevProg &P = b->P;
     if ((P.nu && !u_host) || (P.nk && !ddqk_host) || (P.nc && !lambda_host)) return fail(TG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch, nq = P.nq, nd = P.nd, nk = P.nk, nu = P.nu, nc = P.nc;
-    const size_t total = B * (2 * nq + nu + nk + nd + nc);
-    if (!b->dyn) HIP_TRY(hipMalloc(&b->dyn, (total ? total : 1) * sizeof(double)));
-    double *q = b->dyn, *dq = q + B * nq, *u = dq + B * nq, *ddk = u + B * nu, *ddq = ddk + B * nk, *lam = ddq + B * nd;
-    HIP_TRY(hipMemcpyAsync(q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(dq, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (nu) HIP_TRY(hipMemcpyAsync(u, u_host, B * nu * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (nk) HIP_TRY(hipMemcpyAsync(ddk, ddqk_host, B * nk * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (int rc = tg_batch_dynamics_device(b, q, dq, nu ? u : nullptr, nk ? ddk : nullptr, ddq, lam, nullptr)) return rc;
-    HIP_TRY(hipMemcpyAsync(ddq_host, ddq, B * nd * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (nc) HIP_TRY(hipMemcpyAsync(lambda_host, lam, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (status_host) HIP_TRY(hipMemcpyAsync(status_host, b->dyn_ints + B, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    const size_t B = (size_t)b->batch, nd = P.nd, nc = P.nc;
+    DynStage s;
+    if (int rc = stage_dynamics(b, q_host, dq_host, u_host, ddqk_host, s)) return rc;
+    if (int rc = tg_batch_dynamics_device(b, s.q, s.dq, P.nu ? s.u : nullptr, P.nk ? s.ddk : nullptr, s.ddq, s.lam, nullptr)) return rc;
+    HIP_TRY(hipMemcpyAsync(ddq_host, s.ddq, B * nd * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (nc) HIP_TRY(hipMemcpyAsync(lambda_host, s.lam, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (status_host) HIP_TRY(hipMemcpyAsync(status_host, b->dyn_ints.get() + B, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }
 
-int tg_batch_deriv2_contract_device(tg_batch *b, const double *z_dev, double *hz_dev) {
-    if (!b || !z_dev || !hz_dev) return fail(TG_ERR_INVALID, "null argument");
+// z and hz in device memory; horizon > 0: only steps k_begin .. k_end - 1 of every seed of a seeds x horizon batch
+static int deriv2_contract_device(tg_batch *b, const double *z_dev, double *hz_dev, int horizon, int k_begin, int k_end) {
     if (b->P.n_true_springs) return fail(TG_ERR_UNSUPPORTED, "V_dqdqdq() is undefined for LinearSpring (as in the reference): no second derivatives");
     if (b->t2 == b->t1) return fail(TG_ERR_STATE, "Integrator has not solved the next time step yet.");
     HIP_TRY(hipSetDevice(b->device));
     tg::RunArgs A = base_args(b, tg::MODE_DERIV2Z);
     A.z = z_dev; A.hz = hz_dev;
+    if (horizon > 0) { A.remap_len = k_end - k_begin; A.remap_stride = horizon; A.remap_off = k_begin; A.remap_count = (b->batch / horizon) * (k_end - k_begin); }
     return launch(b, A);
+}
+
+int tg_batch_deriv2_contract_device(tg_batch *b, const double *z_dev, double *hz_dev) {
+    if (!b || !z_dev || !hz_dev) return fail(TG_ERR_INVALID, "null argument");
+    return deriv2_contract_device(b, z_dev, hz_dev, 0, 0, 0);
 }
 
 int tg_batch_deriv2_contract_device_range(tg_batch *b, const double *z_dev, double *hz_dev, int32_t horizon, int32_t k_begin, int32_t k_end) {
     if (!b || !z_dev || !hz_dev) return fail(TG_ERR_INVALID, "null argument");
     if (horizon <= 0 || b->batch % horizon != 0 || k_begin < 0 || k_end > horizon || k_begin >= k_end) return fail(TG_ERR_INVALID, "bad step range");
-    if (b->P.n_true_springs) return fail(TG_ERR_UNSUPPORTED, "V_dqdqdq() is undefined for LinearSpring (as in the reference): no second derivatives");
-    if (b->t2 == b->t1) return fail(TG_ERR_STATE, "Integrator has not solved the next time step yet.");
-    HIP_TRY(hipSetDevice(b->device));
-    tg::RunArgs A = base_args(b, tg::MODE_DERIV2Z);
-    A.z = z_dev; A.hz = hz_dev;
-    A.remap_len = k_end - k_begin; A.remap_stride = horizon; A.remap_off = k_begin; A.remap_count = (b->batch / horizon) * (k_end - k_begin);
-    return launch(b, A);
+    return deriv2_contract_device(b, z_dev, hz_dev, horizon, k_begin, k_end);
 }
 
 int tg_batch_set_from_trajectories(tg_batch *b, int32_t seeds, int32_t horizon, double t0, double dt, const double *X_dev,
@@ -1124,15 +1059,11 @@ int tg_batch_set_from_trajectories(tg_batch *b, int32_t seeds, int32_t horizon, 
     const tg::DevProg &P = b->P;
     b->mirror_valid = false;
     hipLaunchKernelGGL(k_set_from_trajectories, dim3(b->batch), dim3(64), 0, b->stream, P, seeds, horizon, X_dev, U_dev,
-                       b->q1, b->q2, b->p1, b->p2, b->lam, b->stage_u, b->stage_k, b->stage_qh);
+                       b->q1.get(), b->q2.get(), b->p1.get(), b->p2.get(), b->lam.get(), b->stage_u.get(), b->stage_k.get(), b->stage_qh.get());
     HIP_TRY(hipGetLastError());
     b->t1 = t0; b->t2 = t0;
-    tg::RunArgs A = base_args(b, tg::MODE_ROLLOUT);
-    A.n_steps = 1; A.dt = dt; A.max_iterations = max_iterations;
-    if (!A.dt_period) A.dt_steps = nullptr;      // (as in tg_batch_step)
-    A.U = b->stage_u; A.K = b->stage_k; A.q2_hint = b->stage_qh;
-    int rc = launch(b, A);
-    if (rc) return rc;
+    tg::RunArgs A = step_args(b, dt, max_iterations, b->stage_u.get(), b->stage_k.get(), b->stage_qh.get(), nullptr);
+    if (int rc = launch(b, A)) return rc;
     b->t1 = t0; b->t2 = t0 + dt;
     return TG_SUCCESS;
 }
@@ -1141,8 +1072,8 @@ int tg_batch_initialize_from_state_device(tg_batch *b, double t, const double *X
     if (!b || !X_dev || row_stride_doubles < (uint64_t)(b->P.nq + b->P.nd)) return fail(TG_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(b->device));
     b->mirror_valid = false;
-    hipLaunchKernelGGL(k_init_from_X, dim3(b->batch), dim3(64), 0, b->stream, b->P, X_dev, (size_t)row_stride_doubles, b->q1, b->q2,
-                       b->p1, b->p2, b->lam);
+    hipLaunchKernelGGL(k_init_from_X, dim3(b->batch), dim3(64), 0, b->stream, b->P, X_dev, (size_t)row_stride_doubles, b->q1.get(), b->q2.get(),
+                       b->p1.get(), b->p2.get(), b->lam.get());
     HIP_TRY(hipGetLastError());
     b->t1 = t; b->t2 = t;
     return TG_SUCCESS;
@@ -1202,17 +1133,16 @@ int tg_debug_solve(int32_t device, int32_t n, int32_t exact, const double *A_aug
     if (n <= 0 || n > 32 || !A_aug_host || !x_host || !pivot_rows_host || !status_host) return fail(TG_ERR_INVALID, "bad arguments");
     if (exact == 2 && (n <= 16 || n >= 32)) return fail(TG_ERR_INVALID, "the panel solver takes 16 < n < 32");
     HIP_TRY(hipSetDevice(device));
-    double *dA = nullptr, *dx = nullptr; int *dp = nullptr, *ds = nullptr;
+    tg::DeviceBuffer<double> dA, dx;
+    tg::DeviceBuffer<int> dp, ds;
     const int ld = (n + 1) | 1;
-    HIP_TRY(hipMalloc(&dA, sizeof(double) * n * (n + 1))); HIP_TRY(hipMalloc(&dx, sizeof(double) * n));
-    HIP_TRY(hipMalloc(&dp, sizeof(int) * n)); HIP_TRY(hipMalloc(&ds, sizeof(int)));
-    HIP_TRY(hipMemcpy(dA, A_aug_host, sizeof(double) * n * (n + 1), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_debug_solve, dim3(1), dim3(64), sizeof(double) * (n * ld + 16 + 192), 0, n, ld, (int)exact, dA, dx, dp, ds);
+    HIP_TRY(dA.ensure((size_t)n * (n + 1))); HIP_TRY(dx.ensure(n)); HIP_TRY(dp.ensure(n)); HIP_TRY(ds.ensure(1));
+    HIP_TRY(hipMemcpy(dA.get(), A_aug_host, sizeof(double) * n * (n + 1), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_solve, dim3(1), dim3(64), sizeof(double) * (n * ld + 16 + 192), 0, n, ld, (int)exact, dA.get(), dx.get(), dp.get(), ds.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(x_host, dx, sizeof(double) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pivot_rows_host, dp, sizeof(int) * n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(status_host, ds, sizeof(int), hipMemcpyDeviceToHost));
-    hipFree(dA); hipFree(dx); hipFree(dp); hipFree(ds);
+    HIP_TRY(hipMemcpy(x_host, dx.get(), sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pivot_rows_host, dp.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(status_host, ds.get(), sizeof(int), hipMemcpyDeviceToHost));
     return TG_SUCCESS;
 }
 
@@ -1228,7 +1158,7 @@ std::string spec_header_text(const tg_system *sys) {
     std::string out;
     char line[160];
     std::snprintf(line, sizeof(line), "#define SPEC_TEAM %d\n#define SPEC_SPRINGS %s\n", sys->team,
-                  (sys->H.p.has_cs || sys->H.p.n_springs || sys->H.p.has_plane || sys->H.p.n_wrenches) ? "true" : "false");
+                  launch_springs(sys->H.p) ? "true" : "false");
     out += line;
     emit_spec_header(sys->H, out);
     return out;
@@ -1265,33 +1195,32 @@ uint64_t tg_system_spec_key(const tg_system *sys) {
 int tg_batch_load_specialized(tg_batch *b, const char *library_path) {
     if (!b || !library_path) return fail(TG_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(b->device));
-    void *h = dlopen(library_path, RTLD_NOW | RTLD_LOCAL);
-    if (!h) return fail(TG_ERR_INVALID, std::string("cannot load ") + library_path + ": " + (dlerror() ? dlerror() : "?"));
+    std::unique_ptr<void, int (*)(void *)> lib(dlopen(library_path, RTLD_NOW | RTLD_LOCAL), dlclose);     // closed again by every refusal
+    void *h = lib.get();
+    const char *why = h ? nullptr : dlerror();      // (one call: dlerror() clears the message it returns)
+    if (!h) return fail(TG_ERR_INVALID, std::string("cannot load ") + library_path + ": " + (why ? why : "?"));
     auto launch_fn = reinterpret_cast<int (*)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *)>(dlsym(h, "tg_spec_launch"));
     auto sizes_fn = reinterpret_cast<const int *(*)(void)>(dlsym(h, "tg_spec_sizes"));
     auto modes_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_modes"));
     auto key_fn = reinterpret_cast<uint64_t (*)(void)>(dlsym(h, "tg_spec_key"));
-    if (!launch_fn || !sizes_fn || !modes_fn || !key_fn) { dlclose(h); return fail(TG_ERR_INVALID, "not a specialised trep_amd kernel library"); }
+    if (!launch_fn || !sizes_fn || !modes_fn || !key_fn) return fail(TG_ERR_INVALID, "not a specialised trep_amd kernel library");
     const tg::DevProg &P = b->P;
     const int want[8] = {(int)sizeof(tg::DevProg), (int)sizeof(tg::RunArgs), P.nq, P.nd, P.nc, P.n_items, P.n_pairs, P.lds_per_team};
     const int *got = sizes_fn();
-    for (int i = 0; i < 8; i++) if (got[i] != want[i]) { dlclose(h); return fail(TG_ERR_INVALID, "specialised kernel was built for a different system or library version"); }
-    if (key_fn() != tg_system_spec_key(b->sys)) { dlclose(h); return fail(TG_ERR_INVALID, "specialised kernel was built from a different schedule (header hash mismatch)"); }
-    if (!b->d_args) {
-        bool ok = hipMalloc(&b->d_args, sizeof(tg::RunArgs) * tg_batch::ARG_SLOTS) == hipSuccess &&
-                  hipHostMalloc(&b->h_args, sizeof(tg::RunArgs) * tg_batch::ARG_SLOTS, hipHostMallocDefault) == hipSuccess;
-        int made = 0;
-        for (; made < tg_batch::ARG_SLOTS && ok; made++) ok = hipEventCreateWithFlags(&b->arg_done[made], hipEventDisableTiming) == hipSuccess;
-        if (!ok) {      // leave nothing half-made behind: a retry must find the batch as it was
-            for (int i = 0; i + 1 < made; i++) { hipEventDestroy(b->arg_done[i]); b->arg_done[i] = nullptr; }
-            if (b->h_args) { hipHostFree(b->h_args); b->h_args = nullptr; }
-            if (b->d_args) { hipFree(b->d_args); b->d_args = nullptr; }
-            dlclose(h);
-            return fail(TG_ERR_HIP, "allocation of the argument blocks failed");
-        }
+    for (int i = 0; i < 8; i++) if (got[i] != want[i]) return fail(TG_ERR_INVALID, "specialised kernel was built for a different system or library version");
+    if (key_fn() != tg_system_spec_key(b->sys)) return fail(TG_ERR_INVALID, "specialised kernel was built from a different schedule (header hash mismatch)");
+    if (!b->d_args) {      // built in locals and moved in when complete: a refused call leaves the batch as it was
+        tg::DeviceBuffer<tg::RunArgs> d_args;
+        tg::PinnedBuffer<tg::RunArgs> h_args;
+        tg::Event done[tg_batch::ARG_SLOTS];
+        bool ok = d_args.ensure(tg_batch::ARG_SLOTS) == hipSuccess && h_args.ensure(tg_batch::ARG_SLOTS, hipHostMallocDefault) == hipSuccess;
+        for (int i = 0; i < tg_batch::ARG_SLOTS && ok; i++) ok = done[i].create(hipEventDisableTiming) == hipSuccess;
+        if (!ok) return fail(TG_ERR_HIP, "allocation of the argument blocks failed");
+        b->d_args = std::move(d_args); b->h_args = std::move(h_args);
+        for (int i = 0; i < tg_batch::ARG_SLOTS; i++) b->arg_done[i] = std::move(done[i]);
     }
     if (b->spec_lib) { hipStreamSynchronize(b->stream); dlclose(b->spec_lib); }
-    b->spec_lib = h; b->spec_launch = launch_fn; b->spec_modes = modes_fn(); b->spec_path = library_path;
+    b->spec_lib = lib.release(); b->spec_launch = launch_fn; b->spec_modes = modes_fn(); b->spec_path = library_path;
     auto waves_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_waves"));
     b->spec_waves = waves_fn ? waves_fn() : 1;
     auto par_fn = reinterpret_cast<int (*)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *, const double *, int, int)>(dlsym(h, "tg_spec_launch_par"));
@@ -1326,22 +1255,17 @@ int tg_batch_debug_newton_solve(tg_batch *b, int32_t n_mats, int32_t skip_struct
     if (!fn) return fail(TG_ERR_INVALID, "the specialised library has no solve hook");
     const int nf = b->P.nf;
     HIP_TRY(hipSetDevice(b->device));
-    double *dA = nullptr, *dx = nullptr; int *dp = nullptr;
-    const size_t nA = sizeof(double) * (size_t)n_mats * nf * (nf + 1), nx = sizeof(double) * (size_t)n_mats * nf, np = sizeof(int) * (size_t)n_mats;
-    const char *what = nullptr;         /* one exit: whatever was allocated is freed on every path */
-    int rc = 0;
-    if (hipMalloc(&dA, nA) != hipSuccess || hipMalloc(&dx, nx) != hipSuccess || hipMalloc(&dp, np) != hipSuccess) what = "solve hook: device allocation failed";
-    if (!what && hipMemcpy(dA, A_aug_host, nA, hipMemcpyHostToDevice) != hipSuccess) what = "solve hook: upload failed";
-    if (!what) {
-        rc = fn(dA, dx, dp, n_mats, skip_structured);
-        if (hipDeviceSynchronize() != hipSuccess || rc != 0) what = "solve hook launch failed";
-    }
-    if (!what && (hipMemcpy(x_host, dx, nx, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(path_host, dp, np, hipMemcpyDeviceToHost) != hipSuccess))
-        what = "solve hook: download failed";
-    if (dA) hipFree(dA);
-    if (dx) hipFree(dx);
-    if (dp) hipFree(dp);
-    if (what) { (void)hipGetLastError(); return fail(TG_ERR_HIP, what); }
+    tg::DeviceBuffer<double> dA, dx;
+    tg::DeviceBuffer<int> dp;
+    const size_t cA = (size_t)n_mats * nf * (nf + 1), cx = (size_t)n_mats * nf, cp = (size_t)n_mats;
+    auto failed = [](const char *what) { (void)hipGetLastError(); return fail(TG_ERR_HIP, what); };
+    if (dA.ensure(cA) != hipSuccess || dx.ensure(cx) != hipSuccess || dp.ensure(cp) != hipSuccess) return failed("solve hook: device allocation failed");
+    if (hipMemcpy(dA.get(), A_aug_host, cA * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return failed("solve hook: upload failed");
+    const int rc = fn(dA.get(), dx.get(), dp.get(), n_mats, skip_structured);
+    if (hipDeviceSynchronize() != hipSuccess || rc != 0) return failed("solve hook launch failed");
+    if (hipMemcpy(x_host, dx.get(), cx * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(path_host, dp.get(), cp * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+        return failed("solve hook: download failed");
     return TG_SUCCESS;
 }
 
@@ -1351,8 +1275,7 @@ int tg_batch_debug_newton_solve(tg_batch *b, int32_t n_mats, int32_t skip_struct
 int tg_batch_info(const tg_batch *b, int32_t out[8]) {
     if (!b || !out) return fail(TG_ERR_INVALID, "null argument");
     out[0] = b->spec_launch ? b->spec_modes : 0;
-    out[1] = (int32_t)b->spec_launched_modes; out[2] = (int32_t)b->generic_launched_modes;
-    out[3] = (int32_t)std::min<long long>(b->spec_launches, 0x7fffffff); out[4] = (int32_t)std::min<long long>(b->generic_launches, 0x7fffffff);
+    for (int spec = 0; spec < 2; spec++) { out[2 - spec] = (int32_t)b->launched[0][spec].modes; out[4 - spec] = (int32_t)std::min<long long>(b->launched[0][spec].n, 0x7fffffff); }
     out[5] = b->exact_pivot; out[6] = b->sys->team; out[7] = b->spec_launch ? b->spec_waves : 1;
     return TG_SUCCESS;
 }
@@ -1363,8 +1286,7 @@ int tg_batch_info(const tg_batch *b, int32_t out[8]) {
 int tg_batch_par_info(const tg_batch *b, int32_t out[8]) {
     if (!b || !out) return fail(TG_ERR_INVALID, "null argument");
     out[0] = b->spec_launch_par ? b->spec_par_modes : 0;
-    out[1] = (int32_t)b->par_spec_launched_modes; out[2] = (int32_t)b->par_generic_launched_modes;
-    out[3] = (int32_t)std::min<long long>(b->par_spec_launches, 0x7fffffff); out[4] = (int32_t)std::min<long long>(b->par_generic_launches, 0x7fffffff);
+    for (int spec = 0; spec < 2; spec++) { out[2 - spec] = (int32_t)b->launched[1][spec].modes; out[4 - spec] = (int32_t)std::min<long long>(b->launched[1][spec].n, 0x7fffffff); }
     out[5] = b->par_rows; out[6] = b->par_rows ? b->par_group : 0; out[7] = 0;
     return TG_SUCCESS;
 }
@@ -1377,9 +1299,12 @@ int tg_system_parameters(const tg_system *sys, int32_t sizes_out[4], double *ine
     if (!sys) return fail(TG_ERR_INVALID, "null system");
     const tg::HostProgram &H = sys->H;
     if (sizes_out) { sizes_out[0] = H.p.n_bodies; sizes_out[1] = H.p.nd; sizes_out[2] = sys->has_gravity; sizes_out[3] = sys->has_damping; }
-    if (inertia) std::memcpy(inertia, H.b_inertia.data(), H.b_inertia.size() * sizeof(double));
-    if (gravity) for (int k = 0; k < 3; k++) gravity[k] = H.p.grav[k];
-    if (damping) for (int i = 0; i < H.p.nd; i++) damping[i] = H.damp.empty() ? 0.0 : H.damp[i];
+    const int nb = H.p.n_bodies, nd = H.p.nd;
+    std::vector<double> row(4 * (size_t)nb + 3 + nd);
+    base_parameter_row(H, row.data());
+    if (inertia) std::copy_n(row.begin(), 4 * nb, inertia);
+    if (gravity) std::copy_n(row.begin() + 4 * nb, 3, gravity);
+    if (damping) std::copy_n(row.begin() + 4 * nb + 3, nd, damping);
     return TG_SUCCESS;
 }
 
@@ -1402,19 +1327,19 @@ int tg_batch_set_parameters(tg_batch *b, int32_t rows, int32_t group, const doub
     std::vector<double> tab((size_t)rows * stride);
     for (int r = 0; r < rows; r++) {
         double *row = tab.data() + (size_t)r * stride;
-        for (int i = 0; i < 4 * nb; i++) row[i] = inertia_host ? inertia_host[(size_t)r * 4 * nb + i] : H.b_inertia[i];
-        for (int k = 0; k < 3; k++) row[4 * nb + k] = gravity_host ? gravity_host[3 * (size_t)r + k] : H.p.grav[k];
-        for (int i = 0; i < nd; i++) row[4 * nb + 3 + i] = damping_host ? damping_host[(size_t)r * nd + i] : (H.damp.empty() ? 0.0 : H.damp[i]);
+        base_parameter_row(H, row);
+        if (inertia_host) std::copy_n(inertia_host + (size_t)r * 4 * nb, 4 * nb, row);
+        if (gravity_host) std::copy_n(gravity_host + 3 * (size_t)r, 3, row + 4 * nb);
+        if (damping_host) std::copy_n(damping_host + (size_t)r * nd, nd, row + 4 * nb + 3);
     }
     for (double v : tab) if (!std::isfinite(v)) return fail(TG_ERR_INVALID, "parameter values must be finite");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->stream));          // a launch in flight keeps reading the old table until it has finished
-    if (tab.size() > b->par_cap) {
-        if (b->par_dev) { HIP_TRY(hipFree(b->par_dev)); b->par_dev = nullptr; b->par_cap = 0; b->par_rows = 0; }
-        HIP_TRY(hipMalloc(&b->par_dev, tab.size() * sizeof(double)));
-        b->par_cap = tab.size();
+    if (tab.size() > b->par_dev.count()) {
+        if (b->par_dev) { b->par_dev.reset(); b->par_rows = 0; }
+        HIP_TRY(b->par_dev.ensure(tab.size()));
     }
-    HIP_TRY(hipMemcpyAsync(b->par_dev, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(b->par_dev.get(), tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     b->par_rows = rows; b->par_group = rows == 1 ? b->batch : group; b->par_stride = stride;
     b->mirror_valid = false;
@@ -1440,13 +1365,13 @@ int tg_batch_timing(tg_batch *b, int32_t reset, int32_t *n_launches, double *tot
     double ms = b->folded_ms;
     for (auto &e : b->events) {
         float t = 0.f;
-        HIP_TRY(hipEventElapsedTime(&t, e.first, e.second));
+        HIP_TRY(hipEventElapsedTime(&t, e.first.get(), e.second.get()));
         ms += t;
     }
     if (n_launches) *n_launches = (int32_t)(b->events.size() + b->folded_n);
     if (total_ms) *total_ms = ms;
     if (reset) {
-        for (auto &e : b->events) { b->pool.push_back(e.first); b->pool.push_back(e.second); }
+        for (auto &e : b->events) { b->pool.push_back(std::move(e.first)); b->pool.push_back(std::move(e.second)); }
         b->events.clear();
         b->folded_ms = 0.0; b->folded_n = 0;
     }
