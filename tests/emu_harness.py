@@ -33,6 +33,7 @@ def lib():
         so = os.path.join(_HERE, "emu", "libtrepamd_emu.so")
         srcs = [os.path.join(_HERE, "emu", "emu.cpp"),
                 os.path.join(_ROOT, "trep_amd", "csrc", "mvi_core.hpp"),
+                os.path.join(_ROOT, "trep_amd", "csrc", "lanes.hpp"),
                 os.path.join(_ROOT, "trep_amd", "csrc", "program.hpp"),
                 os.path.join(_ROOT, "trep_amd", "csrc", "bbd.hpp"),
                 os.path.join(_ROOT, "trep_amd", "csrc", "dual.hpp")]

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(64, 2) void k_solve(int reps, const double *A_in, c
     for (int r = 0; r < reps; r++) {
         for (int e = lane; e < NF * LD; e += 64) lds[e] = pristine[e];
         __syncthreads();
-        if (VARIANT == 0) ok &= tg::Core<64>::gj_panel<28, false>(true, lds, NF, LD, lane, scratch, nullptr);
+        if (VARIANT == 0) ok &= tg::gj_panel<28, false>(true, lds, NF, LD, lane, scratch, nullptr);
         else ok &= tg::gj_bbd<NF, LD, BB_NG, BB_NB, BB_T>(lds, tg::bbd_rows<BB_NG + BB_NB>(tab, lane), scratch, lane, TVar{});
         __syncthreads();
     }

@@ -1,8 +1,8 @@
 // Micro-benchmark of the Newton-system solver of the rollout kernel in isolation: n x n system + one right-hand side per
 // wavefront, the occupancy of the real kernel (one 64-lane workgroup per trajectory, 19.5 KB of LDS each -> 8 per CU,
 // two waves per SIMD), `reps` solves per wave.  Variants:
-//   0  gj_rows<N>      (mvi_core.hpp: one row per lane, pivot row broadcast with v_readlane, 28 pivot steps)
-//   1  gj_panel<N>     (mvi_core.hpp: matrix in the v_mfma_f64_16x16x4 accumulator layout on all 64 lanes, panels of four
+//   0  gj_rows<N>      (gj_solve.hpp: one row per lane, pivot row broadcast with v_readlane, 28 pivot steps)
+//   1  gj_panel<N>     (gj_solve.hpp: matrix in the v_mfma_f64_16x16x4 accumulator layout on all 64 lanes, panels of four
 //                       columns factored one row per lane, trailing update on the matrix cores)
 // Prints ns per solve (wall, per wave slot), cycles at 2.4 GHz, and the residual / difference of the solutions.
 //   tools/micro/build.sh && tools/micro/bin/gj_bench [n] [reps]
@@ -40,8 +40,8 @@ __global__ __launch_bounds__(64, 2) void k_solve(int n_arg, int ld_arg, int reps
     for (int r = 0; r < reps; r++) {
         for (int e = lane; e < n * ld; e += 64) lds[e] = lds[n * ld + e];
         __syncthreads();
-        if (VARIANT == 0) ok &= tg::Core<64>::gj_rows<GJ_N, TRACE>(true, lds, n, ld, lane, trace);
-        else ok &= tg::Core<64>::gj_panel<GJ_N, TRACE>(true, lds, n, ld, lane, lds + 2 * n * ld + 32, trace);
+        if (VARIANT == 0) ok &= tg::gj_rows<64, GJ_N, TRACE>(true, lds, n, ld, lane, trace);
+        else ok &= tg::gj_panel<GJ_N, TRACE>(true, lds, n, ld, lane, lds + 2 * n * ld + 32, trace);
         __syncthreads();
     }
     const long long t1 = (long long)__builtin_amdgcn_s_memtime();

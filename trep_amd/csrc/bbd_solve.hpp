@@ -1,6 +1,7 @@
-// bbd_solve.hpp -- device part of the structured Newton solve (plan and rationale: bbd.hpp).  Included by mvi_core.hpp after
-// tg_rcp; device pass only.
+// bbd_solve.hpp -- device part of the structured Newton solve (plan and rationale: bbd.hpp).  Included by mvi_core.hpp; needs
+// lanes.hpp (tg_rcp) only; device pass only.
 #pragma once
+#include "lanes.hpp"
 #if defined(__HIPCC__) && defined(__HIP_DEVICE_COMPILE__)
 namespace tg {
 

@@ -22,6 +22,7 @@
 
 #include "program.hpp"
 #include "dual.hpp"
+#include "lanes.hpp"
 
 // Retired experiment switches: the A/B variants and timing mocks of rounds 3-5, measured, rejected and removed.  A build that still
 // passes one would be the default kernel under a variant's name, so it stops here.
@@ -35,34 +36,6 @@
 #error "a retired experiment switch is defined (TG_MOCK_*, TG_BBD_FUSED_UPDATE / _INLINE / _ASM, TG_WEV_*, TG_NO_* except TG_NO_WEV, GJR_ / GJP_*, TG_FRESH_*, or a former -D tunable): these variants were removed -- verdicts in docs/LOG.md, their source in commit 89f6ce0"
 #endif
 
-#if defined(__HIPCC__)
-#define TG_HD __host__ __device__ __forceinline__
-// Phase boundary.  Lanes of a team exchange data through LDS only, so the fence is restricted to the LDS address
-// space: a plain __syncthreads() also waits for every outstanding GLOBAL store (s_waitcnt vmcnt(0)), which puts
-// the HBM write latency of the result rows on the critical path of the next phase.
-// Helper waves (-DTG_HELPER_WAVES=n, system-specialised builds of full-wave teams): the second-derivative kernel runs n wavefronts per
-// trajectory.  Wave 0 owns every wave-scoped phase (sweeps, register solvers, DPP searches); the flat pair / tile loops -- which
-// only read LDS tables and accumulate with LDS atomics -- are shared by all n waves (TG_FORW) between workgroup barriers (TG_WSYNC).
-// A phase boundary INSIDE wave 0's part must then not be a workgroup barrier: TG_SYNC becomes a wave-local fence (in a one-wave
-// workgroup that is all s_barrier ever was).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define TG_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); \
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
-#if defined(TG_HELPER_WAVES)
-#define TG_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_wave_barrier(); \
-                       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
-#else
-#define TG_SYNC() TG_WSYNC()
-#endif
-#else
-#define TG_SYNC() ((void)0)
-#define TG_WSYNC() ((void)0)
-#endif
-#else
-#define TG_HD inline
-#define TG_SYNC() ((void)0)
-#define TG_WSYNC() ((void)0)
-#endif
 #if defined(TG_HELPER_WAVES)
 constexpr int TG_NW = TG_HELPER_WAVES;
 #else
@@ -119,12 +92,6 @@ constexpr int TG_LT_TRIPS = 4;
 // the same over all the waves of a trajectory (helper-wave kernels; `wave` is 0 and `nw` 1 everywhere else)
 #define TG_FORW(idx, n) for (int idx = tg_opaque(lane + TEAM * wave); idx < (n); idx += TEAM * nw)
 
-#if defined(__HIPCC__)
-// ROCm device-library wavefront reduction (DPP based); declared in hip/amd_detail only behind an opt-in macro
-extern "C" __device__ __attribute__((const)) unsigned long long __ockl_wfred_max_u64(unsigned long long);
-extern "C" __device__ __attribute__((const)) unsigned int __ockl_wfred_max_u32(unsigned int);
-#endif
-
 // Diagnostic build only (-DTG_PROFILE, `make prof`): per-phase cycle accumulation with s_memtime.
 // Never enabled in the product library; the stamps never feed an output value.
 #if defined(TG_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
@@ -136,30 +103,9 @@ extern "C" __device__ __attribute__((const)) unsigned int __ockl_wfred_max_u32(u
 #define TG_STAMP(id) ((void)0)
 #endif
 
-#if defined(__HIP_DEVICE_COMPILE__)
-// 1/p to full precision: hardware seed (4.6e-8 relative, tools/micro/rcp_f64_accuracy.hip) and ONE cubic refinement
-// r (1 + e + e^2), e = 1 - p r: three dependent fp64 operations instead of the four of two Newton steps (a dependent fp64
-// operation costs ~30 cycles on this part); the error is e^3 ~ 1e-22 plus rounding.
-__device__ __forceinline__ double tg_rcp(double p) {
-    const double r = __builtin_amdgcn_rcp(p);
-    const double e = fma(-p, r, 1.0);
-    return fma(r, fma(e, e, e), r);
-}
-// max over lanes 0..31 of a wavefront (the register solvers hold at most 32 rows): four row-shift steps leave each 16-lane
-// row's maximum in its last lane; the two row maxima are combined on the scalar unit.  Two DPP steps shorter than the
-// library's full-wave reduction, and this sits on the critical path of every pivot step.
-__device__ __forceinline__ unsigned int tg_max_u32_lanes32(unsigned int v) {
-    unsigned int t;
-    t = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); v = t > v ? t : v;   // row_shr:1
-    t = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true); v = t > v ? t : v;   // row_shr:2
-    t = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true); v = t > v ? t : v;   // row_shr:4
-    t = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true); v = t > v ? t : v;   // row_shr:8
-    const unsigned int a = (unsigned int)__builtin_amdgcn_readlane((int)v, 15), b = (unsigned int)__builtin_amdgcn_readlane((int)v, 31);
-    return a > b ? a : b;
-}
-#endif
 #include <type_traits>
 #include "bbd_solve.hpp"
+#include "gj_solve.hpp"
 
 namespace tg {
 // the structured Newton solve needs its plan as compile-time constants: system-specialised schedules (SpecProg: static members) only
@@ -168,24 +114,6 @@ template <class P> struct tg_static_bbd<P, typename std::enable_if<(P::bbd_ok >=
 // number of (own + border) columns of the plan (1 where there is no plan: the type of an unused variable)
 template <bool USE, class P, class = void> struct tg_static_bbd_cols { static constexpr int value = 1; };
 template <class P> struct tg_static_bbd_cols<true, P, typename std::enable_if<(P::bbd_ok > 0)>::type> { static constexpr int value = P::bbd_ng + P::bbd_nb; };
-// lane K of every quad (four neighbouring lanes) to the whole quad: two 32-bit DPP moves (quad_perm has no 64-bit form)
-#if defined(__HIP_DEVICE_COMPILE__)
-template <int CTRL> __device__ __forceinline__ double tg_dpp_f64(double x) {      // any DPP control on a double (lanes without a source read 0)
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double tg_readlane_f64(double x, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-template <int K> __device__ __forceinline__ double tg_quad_bcast(double x) {
-    int lo = __double2loint(x), hi = __double2hiint(x);
-    lo = __builtin_amdgcn_update_dpp(0, lo, K * 0x55, 0xF, 0xF, true);     // (bound_ctrl: no tied `old` operand, hence no copy ahead of the move)
-    hi = __builtin_amdgcn_update_dpp(0, hi, K * 0x55, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-#endif
 // any system-specialised schedule (sizes are static members)
 template <class P, class = void> struct tg_is_spec { static constexpr bool value = false; };
 template <class P> struct tg_is_spec<P, typename std::enable_if<(P::nq >= 0)>::type> { static constexpr bool value = true; };
@@ -374,29 +302,6 @@ TG_HD void gl_add(double *p, double v) {
 template <class RI, class RA, class RB> TG_HD auto inner6(const RI *I, const RA *a, const RB *b) -> decltype(I[0] * (a[0] * b[0])) {
     return I[0] * (a[0] * b[0] + a[1] * b[1] + a[2] * b[2]) + I[1] * (a[3] * b[3]) + I[2] * (a[4] * b[4]) +
            I[3] * (a[5] * b[5]);
-}
-
-// smallest c with 2^c >= cols, capped at log2(TEAM)
-template <int TEAM>
-TG_HD int tile_log2(int cols) {
-    int c = 0;
-    while ((1 << c) < cols && (1 << c) < TEAM) c++;
-    return c;
-}
-
-// arg-max over the team; ties resolve to the smaller index (first maximum, as a serial scan finds)
-template <int TEAM>
-TG_HD void team_argmax(double &v, int &i) {
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-    for (int m = TEAM / 2; m >= 1; m >>= 1) {
-        const double ov = __shfl_xor(v, m, TEAM);
-        const int oi = __shfl_xor(i, m, TEAM);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-#else
-    (void)v; (void)i;
-#endif
 }
 
 // SPRINGS: the spring potentials (ConfigSpring, LinearSpring) and the plane constraints are compiled in only for systems that have them, so
@@ -2250,636 +2155,6 @@ struct Core {
         return ok;
     }
 
-#if defined(__HIP_DEVICE_COMPILE__)
-    // ---- Gauss-Jordan with one matrix ROW PER LANE held in registers (n <= N <= TEAM) ---------------------
-    //      Same pivot rule as gauss_jordan() but pivoting "in place": rows never move, the lane that owns
-    //      the pivot row of step k broadcasts it (v_readlane for a full-wave team, ds_bpermute otherwise)
-    //      and every other lane eliminates in registers.  No LDS traffic inside the k loop.  N is the
-    //      matrix size rounded up to a multiple of 4 (identity padding), so every loop bound is a
-    //      compile-time constant and the body carries no guards.
-    //      Reads [A | rhs(1 column)] from LDS, leaves x in A[i*ld + n] like gauss_jordan().
-    // Slow path of the pivot search (out of line: the 28-times unrolled solver must stay small enough for the instruction
-    // cache): exact maximum of the candidates' doubles and, among the rows that attain it, the first in the reference's order.
-    static __device__ __noinline__ int pivot_exact(double cand64, bool cand_ok, int pos, int lane) {
-        unsigned long long best = cand_ok ? (unsigned long long)__double_as_longlong(cand64) : 0ull;   // non-negative doubles order like their bits
-        if (TEAM == 64) {
-            best = __ockl_wfred_max_u64(best);
-        } else {
-#pragma unroll
-            for (int m = TEAM / 2; m >= 1; m >>= 1) {
-                const unsigned long long o = __shfl_xor(best, m, TEAM);
-                best = o > best ? o : best;
-            }
-        }
-        const bool at_max = cand_ok && (unsigned long long)__double_as_longlong(cand64) == best;
-        unsigned int k2 = at_max ? ((unsigned int)(63 - pos) << 6) | (unsigned int)(lane & 63) : 0u;   // position first, lane to identify the row
-        if (TEAM == 64) {
-            k2 = __ockl_wfred_max_u32(k2);
-        } else {
-#pragma unroll
-            for (int m = TEAM / 2; m >= 1; m >>= 1) {
-                const unsigned int o = __shfl_xor(k2, m, TEAM);
-                k2 = o > k2 ? o : k2;
-            }
-        }
-        int piv = (int)(k2 & 0x3Fu);
-        if (TEAM != 64) piv = (piv & (TEAM - 1));
-        return piv;
-    }
-
-    template <int N, bool TRACE = false>
-    static __device__ __noinline__ bool gj_rows_exact(bool on, double *A_generic, int n, int ld, int lane, int *trace = nullptr) {
-        typedef __attribute__((address_space(3))) double lds_double;
-        lds_double *A = (lds_double *)A_generic;
-        double row[N], rhs = 0.0, scale = 0.0, diag = 1.0;
-        int mycol = -1;
-        // position of this lane's row in the reference's row order (math-code.c swaps rows physically; here rows never move):
-        // only needed to break EXACT ties the way the reference's strict `>` scan does -- first row in its current order
-        int pos = lane;
-        const bool mine = on && lane < N;
-        const int wl = (int)(threadIdx.x & 63u), team_base = wl - lane;
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            row[j] = (mine && lane < n && j < n) ? A[lane * ld + j] : ((mine && lane >= n && j == lane) ? 1.0 : 0.0);
-        if (mine) {
-            rhs = lane < n ? A[lane * ld + n] : 0.0;
-            double s = -1.0;
-#pragma unroll
-            for (int j = 0; j < N; j++) { const double a = fabs(row[j]); s = a > s ? a : s; }
-            scale = 1.0 / s;
-        }
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            // arg-max of |a_ik| * scale_i over the rows not yet used as pivots, ties to the row that comes first in the
-            // reference's (swapped) row order -- its scan uses a strict `>`.  The candidates are ranked by ONE 32-bit wave max
-            // of (single-precision magnitude with the 6 low mantissa bits replaced by 63 - position): cast and mask are
-            // monotonic, so the exact fp64 maximum is among the lanes that attain the truncated maximum, and among EXACTLY
-            // equal candidates (mirror-symmetric mechanisms produce them all the time) the key already prefers the smallest
-            // position.  Only if several lanes share the truncated maximum with DIFFERENT doubles (within 2^-17 relative, rare)
-            // the slow path compares the doubles exactly.
-            const bool cand_ok = mine && mycol < 0;
-            const double cand64 = cand_ok ? fabs(row[k] * scale) : 0.0;
-            // key = magnitude (22 bits) | 31 - position | lane: N <= 32, so position and lane take 5 bits each
-            const unsigned int tkey = __float_as_uint((float)cand64) & ~0x3FFu;
-            unsigned int key = tkey | ((unsigned int)(31 - (pos & 31)) << 5) | (unsigned int)(lane & 31);
-            if (TEAM == 64) {
-                key = __ockl_wfred_max_u32(key);
-            } else {
-#pragma unroll
-                for (int m = TEAM / 2; m >= 1; m >>= 1) {
-                    const unsigned int o = __shfl_xor(key, m, TEAM);
-                    key = o > key ? o : key;
-                }
-            }
-            const unsigned long long team_mask = TEAM == 64 ? ~0ull : (((1ull << TEAM) - 1ull) << team_base);
-            const bool at_tmax = cand_ok && tkey == (key & ~0x3FFu);
-            const unsigned long long tied = __ballot(at_tmax) & team_mask;
-            int piv = (int)(key & 31u);
-            if (TEAM < 32) piv &= (TEAM - 1);
-            if (__any((tied & (tied - 1ull)) != 0ull ? 1 : 0)) {   // some team has several lanes at the truncated maximum
-                const double w = TEAM == 64 ? __longlong_as_double(((long long)__builtin_amdgcn_readlane((int)(__double_as_longlong(cand64) >> 32), piv) << 32) |
-                                                                   (unsigned int)__builtin_amdgcn_readlane((int)(__double_as_longlong(cand64) & 0xFFFFFFFFLL), piv))
-                                            : __shfl(cand64, piv, TEAM);
-                if (__any((at_tmax && cand64 != w) ? 1 : 0))       // ... and they are not all exactly equal: exact comparison
-                    piv = pivot_exact(cand64, cand_ok, pos, lane);
-            }
-            // singular test (math-code.c:393: scaled pivot <= 1e-20): decided by the truncated maximum unless that lies within a
-            // factor of two of the threshold -- only then the winner's exact value is looked at
-            const int src = (TEAM == 64) ? __builtin_amdgcn_readfirstlane(piv) : piv;
-            const float best = __uint_as_float(key & ~0x3FFu);
-            if (__any((best < 2.0e-20f && best > 0.5e-20f) ? 1 : 0)) {
-                const unsigned long long big = __ballot(cand64 > 1.0e-20);
-                if (on && ok && !((big >> (team_base + src)) & 1ull)) ok = false;
-            } else if (on && ok && !(best > 1.0e-20f)) ok = false;
-            const bool go = on && ok;
-            // broadcast the pivot row (columns k..N-1 and the rhs)
-            auto bcast = [&](double v) -> double {
-                if (TEAM == 64) {
-                    const long long b = __double_as_longlong(v);
-                    const int lo = __builtin_amdgcn_readlane((int)(b & 0xFFFFFFFFLL), src);
-                    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-                    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-                }
-                return __shfl(v, src, TEAM);
-            };
-            const double pkk = bcast(row[k]);
-            const double prhs = bcast(rhs);
-            const bool is_piv = mine && (lane & (TEAM - 1)) == src;
-            // bookkeeping of the reference's row order: it swaps the pivot row with the row at position k
-            {
-                const int pos_p = (TEAM == 64) ? __builtin_amdgcn_readlane(pos, src) : __shfl(pos, src, TEAM);
-                if (__any(pos_p != k ? 1 : 0)) {     // (wave-uniform) almost never taken: the pivot usually is the row at position k
-                    if (pos == k) pos = pos_p;
-                    if (is_piv) pos = k;
-                }
-            }
-            if (TRACE && go && is_piv) trace[k] = lane;
-            // 1/pivot: hardware seed + two Newton steps (the multipliers need not be correctly rounded)
-            double rp = tg_rcp(pkk);
-            const double l = (go && mine && !is_piv) ? row[k] * rp : 0.0;
-#pragma unroll
-            for (int j = k + 1; j < N; j++) row[j] = fma(-l, bcast(row[j]), row[j]);
-            rhs = fma(-l, prhs, rhs);
-            if (go && is_piv) { mycol = k; diag = row[k]; }
-            // Keep the elimination pivot-major: left alone, the instruction selector linearises the fully
-            // unrolled body column by column (fma -> readlane of the same register -> fma ...): one long
-            // dependent chain padded with hazard s_nops.  Passing the updated row through ordered empty asm
-            // statements pins step k before step k+1; inside a step the broadcasts and fmas are independent.
-#pragma unroll
-            for (int j = k + 1; j < N; j += 8) {
-                if (j + 7 < N) asm volatile("" : "+v"(row[j]), "+v"(row[j + 1]), "+v"(row[j + 2]), "+v"(row[j + 3]),
-                                                 "+v"(row[j + 4]), "+v"(row[j + 5]), "+v"(row[j + 6]), "+v"(row[j + 7]));
-                else {
-#pragma unroll
-                    for (int jj = j; jj < N; jj++) asm volatile("" : "+v"(row[jj]));
-                }
-            }
-        }
-        if (mine && ok && mycol >= 0 && mycol < n) A[mycol * ld + n] = rhs / diag;
-        __syncthreads();
-        return ok;
-    }
-
-    // ---- the default solver: same elimination, pivot candidates ranked in single precision -------------------------------
-    //      One 32-bit wave max per step over (float bits of |a_ik| * scale_i with the 6 low mantissa bits replaced by
-    //      63 - lane) and no branch anywhere in the unrolled body.  Candidates closer than 2^-17 relative are taken in lane
-    //      (= original row) order.  That is NOT always the reference's choice: every row's largest entry scales to 1 +- 1 ulp,
-    //      so whenever two rows have their largest entry in the same column (two string constraints and a shared torso
-    //      config: 95 % of the puppet's Newton systems) the reference's strict `>` scan decides by that last ulp.  Either
-    //      row is an exact arg-max to 16 digits and the solutions agree to rounding (1e-13 relative on the test matrices), but
-    //      the pivot SEQUENCE can differ; gj_rows_exact() reproduces it exactly (RunArgs::exact_pivot, tg_batch_set_pivot_rule)
-    //      at +9 % rollout time -- each variant of an in-line exact test (position bookkeeping +2.3 %, tie block +3.4 %, exact
-    //      singular test +3.7 %; a branch-free "detect and redo" fires on 95 % of the solves) was measured and rejected.
-#if defined(TG_GJ_INLINE)
-#define TG_GJ_ATTR __forceinline__
-#else
-#define TG_GJ_ATTR __noinline__
-#endif
-    template <int N, bool TRACE = false>
-    static __device__ TG_GJ_ATTR bool gj_rows(bool on, double *A_generic, int n, int ld, int lane, int *trace = nullptr) {
-        typedef __attribute__((address_space(3))) double lds_double;
-        lds_double *A = (lds_double *)A_generic;
-        double row[N], rhs = 0.0, scale = 0.0, diag = 1.0;
-        int mycol = -1;
-        const bool mine = on && lane < N;
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            row[j] = (mine && lane < n && j < n) ? A[lane * ld + j] : ((mine && lane >= n && j == lane) ? 1.0 : 0.0);
-        if (mine) {
-            rhs = lane < n ? A[lane * ld + n] : 0.0;
-            double s = -1.0;
-#pragma unroll
-            for (int j = 0; j < N; j++) { const double a = fabs(row[j]); s = a > s ? a : s; }
-            scale = 1.0 / s;
-        }
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < N; k++) {
-            const float cand = (mine && mycol < 0) ? (float)fabs(row[k] * scale) : 0.0f;
-            unsigned int key = (__float_as_uint(cand) & ~0x3Fu) | (unsigned int)(63 - (lane & 63));
-            if (TEAM == 64) {
-                key = tg_max_u32_lanes32(key);       // N <= 32: only lanes 0..31 hold rows (the others carry key 0 | lane bits)
-            } else {
-#pragma unroll
-                for (int m = TEAM / 2; m >= 1; m >>= 1) {
-                    const unsigned int o = __shfl_xor(key, m, TEAM);
-                    key = o > key ? o : key;
-                }
-            }
-            int piv = 63 - (int)(key & 0x3Fu);
-            const float best = __uint_as_float(key & ~0x3Fu);
-            if (TEAM != 64) piv = (piv & (TEAM - 1));
-            if (on && ok && !(best > 1.0e-20f)) ok = false;
-            const bool go = on && ok;
-            // broadcast the pivot row (columns k..N-1 and the rhs)
-            const int src = (TEAM == 64) ? __builtin_amdgcn_readfirstlane(piv) : piv;
-            auto bcast = [&](double v) -> double {
-                if (TEAM == 64) {
-                    const long long b = __double_as_longlong(v);
-                    const int lo = __builtin_amdgcn_readlane((int)(b & 0xFFFFFFFFLL), src);
-                    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-                    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-                }
-                return __shfl(v, src, TEAM);
-            };
-            const double prhs = bcast(rhs);
-            const bool is_piv = mine && (lane & (TEAM - 1)) == src;
-            if (TRACE && go && is_piv) trace[k] = lane;
-            const double pkk = bcast(row[k]);
-            double rp = tg_rcp(pkk);          // 1/pivot (the multipliers need not be correctly rounded)
-            const double l = (go && mine && !is_piv) ? row[k] * rp : 0.0;
-            // two pivot-row entries are broadcast before their two FMAs: a v_readlane result cannot be consumed by the next VALU
-            // instruction (two wait states), so one broadcast-FMA pair at a time costs an s_nop per column (groups of four make
-            // the unroller give up on the row registers: 420 instead of 66 ms)
-#pragma unroll
-            for (int j = k + 1; j < N; j += 2) {
-                const double b0 = bcast(row[j]);
-                const double b1 = bcast(row[j + 1 < N ? j + 1 : j]);
-                row[j] = fma(-l, b0, row[j]);
-                if (j + 1 < N) row[j + 1] = fma(-l, b1, row[j + 1]);
-            }
-            rhs = fma(-l, prhs, rhs);
-            if (go && is_piv) { mycol = k; diag = row[k]; }
-            // keep the elimination pivot-major (see gj_rows_exact)
-#pragma unroll
-            for (int j = k + 1; j < N; j += 8) {
-                if (j + 7 < N) asm volatile("" : "+v"(row[j]), "+v"(row[j + 1]), "+v"(row[j + 2]), "+v"(row[j + 3]),
-                                                 "+v"(row[j + 4]), "+v"(row[j + 5]), "+v"(row[j + 6]), "+v"(row[j + 7]));
-                else {
-#pragma unroll
-                    for (int jj = j; jj < N; jj++) asm volatile("" : "+v"(row[jj]));
-                }
-            }
-        }
-        if (mine && ok && mycol >= 0 && mycol < n) A[mycol * ld + n] = rhs / diag;
-        __syncthreads();
-        return ok;
-    }
-
-    // ---- the full-wave solver (TEAM == 64, 16 < n < 32): panels of four columns + trailing update on the matrix cores ---------
-    //      gj_rows keeps one matrix row per lane (28 of 64 lanes busy) and pays two v_readlane per FMA for the pivot-row
-    //      broadcast: ~68 VALU instructions per pivot step, and the solver is bound by exactly that instruction stream.  Here the
-    //      [A | b] matrix (b = column n) stays in LDS in its [n][ld] layout AND lives in the accumulator layout of
-    //      v_mfma_f64_16x16x4_f64 on all 64 lanes: lane (g = lane >> 4, c = lane & 15), register v of tile (TR, TC) holds entry
-    //      [16 TR + 4 v + g][16 TC + c] -- 16 doubles per lane instead of 29.  Per panel of four columns:
-    //        1. lane i < n reads the four panel entries of row i from LDS (one row per lane);
-    //        2. the four columns are eliminated exactly like gj_rows does it (scaled partial pivoting, rows never move, same
-    //           single-precision ranking) -- but the broadcasts only cover the other panel columns and the columns of Z: 3 per step;
-    //        3. Z [32][4] accumulates what the four elementary row operations do to any OTHER column: after the panel,
-    //           A' = A + Z A[R, :] with R the four pivot rows as they were at the panel's start (block Gauss-Jordan; Z[:, t] is
-    //           column r_t of the accumulated row-operation matrix minus the identity: z_t <- l at step t, z_s += l z_s[r_t] for s < t);
-    //        4. Z goes through 1 KB of LDS into A-operand form, lane group t reads pivot row r_t straight from the LDS image as
-    //           its B operand, the rank-4 update of the four (later two) 16 x 16 tiles is one v_mfma_f64_16x16x4_f64 each, and the
-    //           live tiles are written back to the LDS image.
-    //      No branch, no run-time register index.  Same pivot rule as gj_rows (the default rule); the trailing columns see the block
-    //      update instead of four rank-1 updates, so results differ from gj_rows' by rounding only.  `scratch`: 128 doubles of LDS
-    //      outside [A | b] (the Z table).
-    //      Always an out-of-line function: inlined into the 20 k-instruction rollout kernel it shares that kernel's register
-    //      allocation and schedule (91 instead of 53 SGPR spills, every other phase ~10 % slower: 63.3 ms per benchmark launch);
-    //      as a call it keeps its own (61.7 ms; gj_rows: 65.1 ms).
-    template <int N, bool TRACE = false>
-    static __device__ __noinline__ bool gj_panel(bool on, double *A_generic, int n, int ld, int lane, double *scratch_generic, int *trace = nullptr) {
-        static_assert(N % 4 == 0 && N > 16 && N <= 32, "gj_panel: 16 < N <= 32");
-        typedef __attribute__((address_space(3))) double lds_double;
-        typedef double v4d __attribute__((ext_vector_type(4)));
-        lds_double *A = (lds_double *)A_generic, *WL = (lds_double *)scratch_generic;
-        const int g = (lane >> 4) & 3, c = lane & 15;
-        // TEAM == 64: the workgroup is ONE wavefront, whose LDS operations execute in program order -- a read issued after a write of
-        // the same wave sees it, so no fence / s_waitcnt stands between the phases below; the compiler only has to keep may-alias
-        // LDS accesses in program order, which it does (WL and A are both plain LDS pointers)
-        auto lds_fence = [] { asm volatile("" ::: "memory"); };
-        // rows 16 TR + 4 v + g of a register exist for every lane group / for none / for some (only when n is not a multiple of 4)
-        auto rows_all = [&](int TR, int v) { return 16 * TR + 4 * v + 3 < n; };
-        auto rows_none = [&](int TR, int v) { return 16 * TR + 4 * v >= n; };
-        const bool in1 = 16 + c <= n;             // this lane's column of tile column 1 exists (b is column n)
-        const int c1 = in1 ? 16 + c : 0;
-        // ---- the matrix into the accumulator layout, the rows' scale factors one row per lane
-        v4d T[2][2];
-#pragma unroll
-        for (int TR = 0; TR < 2; TR++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const int row = 16 * TR + 4 * v + g;
-                if (rows_none(TR, v)) { T[TR][0][v] = 0.0; T[TR][1][v] = 0.0; continue; }
-                const bool rin = rows_all(TR, v) || row < n;
-                const int ro = rin ? row * ld : 0;
-                const double a0 = A[ro + c], a1 = A[ro + c1];
-                T[TR][0][v] = rin ? a0 : 0.0;
-                T[TR][1][v] = (rin && in1) ? a1 : 0.0;
-            }
-        const bool mine = lane < n;
-        const int myrow = (mine ? lane : 0) * ld;     // lanes without a row mirror row 0: finite values that end up nowhere
-        double scale = 0.0;
-        {
-            double s = -1.0;
-#pragma unroll
-            for (int j = 0; j < N; j++) if (j < n) { const double a = fabs(A[myrow + j]); s = a > s ? a : s; }
-            scale = 1.0 / s;
-        }
-        bool ok = true;
-        if (!mine) scale = 0.0;
-        const unsigned int lanetag = (unsigned int)(63 - (lane & 63));
-        int mycol = -1;
-        double rdiag = 0.0;
-#pragma unroll
-        for (int p = 0; p < N / 4; p++) {
-            // 1. the panel's entries of this lane's row
-            double cp[4], z[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int t = 0; t < 4; t++) cp[t] = A[myrow + (4 * p + t < n ? 4 * p + t : 0)];
-            // 2. / 3. the four pivot steps
-            int srcs[4] = {0, 0, 0, 0};
-            double b0 = 0.0, b1 = 0.0;
-            const bool live0 = 4 * p + 4 < 16;
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int k = 4 * p + t;
-                if (k < n) {
-                    const double own_rp = tg_rcp(cp[t]);      // every lane inverts its own candidate while the search runs
-                    // rows already used as pivots (and lanes without a row) carry scale 0: their key is the bare lane tag
-                    const float cand = (float)(cp[t] * scale);
-                    unsigned int key = (__float_as_uint(cand) & 0x7FFFFFC0u) | lanetag;
-                    key = tg_max_u32_lanes32(key);
-                    if (!((key & ~0x3Fu) > 0x1E3CE508u)) ok = false;     // scaled pivot <= 1e-20 (compared as bits: non-negative floats)
-                    const int src = __builtin_amdgcn_readfirstlane(63 - (int)(key & 0x3Fu));
-                    auto bcast = [&](double v) -> double {
-                        const long long b = __double_as_longlong(v);
-                        const int lo = __builtin_amdgcn_readlane((int)(b & 0xFFFFFFFFLL), src);
-                        const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-                        return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-                    };
-                    const bool is_piv = lane == src;
-                    if (TRACE && on && ok && is_piv) trace[k] = lane;
-                    srcs[t] = src;
-                    if (t == 3 || k == n - 1) {
-                        // lane group t fetches pivot row r_t of the image (as of the panel's start) as its B operand: requested
-                        // here, as soon as the last pivot row is known, so that the loads travel under the last elimination step
-                        const int prow = (g == 0 ? srcs[0] : (g == 1 ? srcs[1] : (g == 2 ? srcs[2] : srcs[3]))) * ld;
-                        b1 = A[prow + c1];
-                        if (live0) b0 = A[prow + c];
-                    }
-                    const double rp = bcast(own_rp);
-                    // branch-free: a divergent if / else costs more (exec bookkeeping, two skipped-block branches) than three selects
-                    const double l = is_piv ? 0.0 : cp[t] * -rp;
-#pragma unroll
-                    for (int t2 = t + 1; t2 < 4; t2++) cp[t2] = fma(l, bcast(cp[t2]), cp[t2]);
-#pragma unroll
-                    for (int s = 0; s < t; s++) z[s] = fma(l, bcast(z[s]), z[s]);
-                    z[t] = l;
-                    mycol = is_piv ? k : mycol;
-                    rdiag = is_piv ? own_rp : rdiag;
-                    scale = is_piv ? 0.0 : scale;
-                }
-            }
-            // 4. Z -> A-operand form; pivot rows from the LDS image (as of the panel's start); trailing update; write back
-            //    (tile column 0 is dead once the panel has passed column 11)
-            if (lane < 32) {
-#pragma unroll
-                for (int t = 0; t < 4; t++) WL[lane * 4 + t] = z[t];
-            }
-            lds_fence();
-            const double a0 = WL[c * 4 + g], a1 = WL[(16 + c) * 4 + g];
-            if (!in1) b1 = 0.0;
-            if (live0) {
-                T[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, T[0][0], 0, 0, 0);
-                T[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, T[1][0], 0, 0, 0);
-            }
-            T[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, T[0][1], 0, 0, 0);
-            T[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, T[1][1], 0, 0, 0);
-            lds_fence();      // every lane has its operands before the image changes
-            auto write_back = [&](int TC) {
-#pragma unroll
-                for (int TR = 0; TR < 2; TR++)
-#pragma unroll
-                    for (int v = 0; v < 4; v++) {
-                        const int row = 16 * TR + 4 * v + g;
-                        if (!rows_none(TR, v) && (rows_all(TR, v) || row < n)) A[row * ld + 16 * TC + c] = T[TR][TC][v];
-                    }
-            };
-            if (live0) write_back(0);
-            if (in1) write_back(1);
-            lds_fence();
-        }
-        // x = b / pivot, row by row: the right-hand side is column n of the image
-        const double xr = A[myrow + n] * rdiag;
-        lds_fence();
-        if (on && mine && ok && mycol >= 0) A[mycol * ld + n] = xr;
-        __syncthreads();
-        return ok;
-    }
-    // ---- gj_panel for MANY right-hand sides (the derivative solves: n <= 31 rows, [A | B] with w <= 16 NTC columns) ------------
-    //      The same panels, pivot rule and block update as gj_panel, with NTC tile columns in the accumulator layout (two tile
-    //      rows x NTC tiles x 4 doubles per lane) instead of two: every right-hand side rides in the rank-4 matrix-core update
-    //      (2 NTC v_mfma_f64_16x16x4 per panel for ~110 columns, where gj_cols spends 28 x 56 lane-wide FMAs plus the pivot-column
-    //      traffic per PIVOT step).  The LDS image [n][ld] is refreshed after every panel (live tile columns only); at the end every
-    //      lane scales its entries by the reciprocal pivot of their row and stores them in the row of the variable that row solved:
-    //      A[i][n + j] = x_i of right-hand side j, like gauss_jordan() / gj_cols.  `scratch`: 128 + 64 doubles of LDS outside the image.
-    template <int N, int NTC>
-    static __device__ __noinline__ bool gj_panel_rhs(bool on, double *A_generic, int n, int w, int ld, int lane, double *scratch_generic) {
-        static_assert(N % 4 == 0 && N > 16 && N <= 32 && NTC >= 2 && NTC <= 8, "gj_panel_rhs: 16 < N <= 32, 32 .. 128 columns");
-        typedef __attribute__((address_space(3))) double lds_double;
-        typedef double v4d __attribute__((ext_vector_type(4)));
-        lds_double *A = (lds_double *)A_generic, *WL = (lds_double *)scratch_generic, *RD = WL + 128;
-        __attribute__((address_space(3))) int *MC = (__attribute__((address_space(3))) int *)(WL + 160);
-        const int g = (lane >> 4) & 3, c = lane & 15;
-        auto lds_fence = [] { asm volatile("" ::: "memory"); };
-        auto rows_all = [&](int TR, int v) { return 16 * TR + 4 * v + 3 < n; };
-        auto rows_none = [&](int TR, int v) { return 16 * TR + 4 * v >= n; };
-        // ---- [A | B] into the accumulator layout
-        v4d T[2][NTC];
-#pragma unroll
-        for (int TR = 0; TR < 2; TR++)
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                const int row = 16 * TR + 4 * v + g;
-                const bool rin = !rows_none(TR, v) && (rows_all(TR, v) || row < n);
-#pragma unroll
-                for (int TC = 0; TC < NTC; TC++) {
-                    const int col = 16 * TC + c;
-                    const bool in = rin && col < w;
-                    const double a = A[in ? row * ld + col : 0];
-                    T[TR][TC][v] = in ? a : 0.0;
-                }
-            }
-        const bool mine = lane < n;
-        const int myrow = (mine ? lane : 0) * ld;
-        double scale = 0.0;
-        {
-            double s = -1.0;
-#pragma unroll
-            for (int j = 0; j < N; j++) if (j < n) { const double a = fabs(A[myrow + j]); s = a > s ? a : s; }
-            scale = 1.0 / s;
-        }
-        bool ok = true;
-        if (!mine) scale = 0.0;
-        const unsigned int lanetag = (unsigned int)(63 - (lane & 63));
-        int mycol = -1;
-        double rdiag = 0.0;
-#pragma unroll
-        for (int p = 0; p < N / 4; p++) {
-            double cp[4], z[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int t = 0; t < 4; t++) cp[t] = A[myrow + (4 * p + t < n ? 4 * p + t : 0)];
-            int srcs[4] = {0, 0, 0, 0};
-            const int TC0 = (4 * p + 4) >> 4;        // first tile column with columns right of this panel
-            double bop[NTC];
-#pragma unroll
-            for (int TC = 0; TC < NTC; TC++) bop[TC] = 0.0;
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int k = 4 * p + t;
-                if (k < n) {
-                    const double own_rp = tg_rcp(cp[t]);
-                    const float cand = (float)(cp[t] * scale);
-                    unsigned int key = (__float_as_uint(cand) & 0x7FFFFFC0u) | lanetag;
-                    key = tg_max_u32_lanes32(key);
-                    if (!((key & ~0x3Fu) > 0x1E3CE508u)) ok = false;
-                    const int src = __builtin_amdgcn_readfirstlane(63 - (int)(key & 0x3Fu));
-                    auto bcast = [&](double v) -> double {
-                        const long long b = __double_as_longlong(v);
-                        const int lo = __builtin_amdgcn_readlane((int)(b & 0xFFFFFFFFLL), src);
-                        const int hi = __builtin_amdgcn_readlane((int)(b >> 32), src);
-                        return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-                    };
-                    const bool is_piv = lane == src;
-                    srcs[t] = src;
-                    if (t == 3 || k == n - 1) {   // B operands: lane group t takes pivot row r_t of the image as of the panel's start
-                        const int prow = (g == 0 ? srcs[0] : (g == 1 ? srcs[1] : (g == 2 ? srcs[2] : srcs[3]))) * ld;
-#pragma unroll
-                        for (int TC = 0; TC < NTC; TC++) if (TC >= TC0) { const int col = 16 * TC + c; bop[TC] = A[prow + (col < w ? col : 0)]; }
-                    }
-                    const double rp = bcast(own_rp);
-                    const double l = is_piv ? 0.0 : cp[t] * -rp;
-#pragma unroll
-                    for (int t2 = t + 1; t2 < 4; t2++) cp[t2] = fma(l, bcast(cp[t2]), cp[t2]);
-#pragma unroll
-                    for (int s = 0; s < t; s++) z[s] = fma(l, bcast(z[s]), z[s]);
-                    z[t] = l;
-                    mycol = is_piv ? k : mycol;
-                    rdiag = is_piv ? own_rp : rdiag;
-                    scale = is_piv ? 0.0 : scale;
-                }
-            }
-            if (lane < 32) {
-#pragma unroll
-                for (int t = 0; t < 4; t++) WL[lane * 4 + t] = z[t];
-            }
-            lds_fence();
-            const double a0 = WL[c * 4 + g], a1 = WL[(16 + c) * 4 + g];
-#pragma unroll
-            for (int TC = 0; TC < NTC; TC++) if (TC >= TC0) {
-                const double b = 16 * TC + c < w ? bop[TC] : 0.0;
-                T[0][TC] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b, T[0][TC], 0, 0, 0);
-                T[1][TC] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b, T[1][TC], 0, 0, 0);
-            }
-            lds_fence();
-            if (p + 1 < N / 4) {        // refresh the image (the last panel's result leaves through the scaled store below)
-#pragma unroll
-                for (int TC = 0; TC < NTC; TC++) if (TC >= TC0 && 16 * TC + c < w) {
-#pragma unroll
-                    for (int TR = 0; TR < 2; TR++)
-#pragma unroll
-                        for (int v = 0; v < 4; v++) {
-                            const int row = 16 * TR + 4 * v + g;
-                            if (!rows_none(TR, v) && (rows_all(TR, v) || row < n)) A[row * ld + 16 * TC + c] = T[TR][TC][v];
-                        }
-                }
-            }
-            lds_fence();
-        }
-        // x = B / pivot, row by row, into the row of the variable each row solved
-        if (mine) { RD[lane] = rdiag; MC[lane] = mycol; }
-        lds_fence();
-        if (on && ok) {
-#pragma unroll
-            for (int TR = 0; TR < 2; TR++)
-#pragma unroll
-                for (int v = 0; v < 4; v++) {
-                    const int row = 16 * TR + 4 * v + g;
-                    if (rows_none(TR, v) || !(rows_all(TR, v) || row < n)) continue;
-                    const double rd = RD[row];
-                    const int mc = MC[row];
-#pragma unroll
-                    for (int TC = 0; TC < NTC; TC++) {
-                        const int col = 16 * TC + c;
-                        if (col >= n && col < w && mc >= 0) A[mc * ld + col] = T[TR][TC][v] * rd;
-                    }
-                }
-        }
-        TG_SYNC();
-        return ok;
-    }
-#endif
-
-#if defined(__HIP_DEVICE_COMPILE__)
-    // ---- Gauss-Jordan with two matrix COLUMNS PER LANE in registers: few rows, many right-hand sides --------------
-    //      (the derivative solves: n <= NR <= 32 rows, up to 128 columns [A | rhs]).  Lane c holds columns c and
-    //      c + 64 of every row.  Per pivot column k: lane k publishes its column in LDS (NR doubles); lane i < NR
-    //      scales entry i and one 32-bit wave max picks the pivot row r; every lane reads the multipliers back with
-    //      uniform (broadcast) LDS reads.  Rows never move and r is only known at run time, so a lane picks its
-    //      pivot-row entries with a 0/1-weighted FMA sum over its rows instead of an indexed register read.  The
-    //      matrix itself never touches LDS during the elimination.  Leaves x_i in A[i*ld + n + rhs] like
-    //      gauss_jordan().  `scal` is 4*NR doubles of scratch (scale factors, pivot reciprocals, row -> variable
-    //      map, current column).
-    template <int NR>
-    static __device__ TG_GJ_ATTR bool gj_cols(bool on, double *A_generic, int n, int w, int ld, double *scal_generic, int lane) {
-        typedef __attribute__((address_space(3))) double lds_double;
-        lds_double *A = (lds_double *)A_generic, *scal = (lds_double *)scal_generic;
-        lds_double *dinv = scal + NR;                      // pivot reciprocal of physical row i
-        double a0[NR], a1[NR];
-        const bool c0 = on && lane < w, c1 = on && lane + 64 < w;
-        // implicit scaling factors 1 / max_j |a_ij| over the matrix columns: lane i < n owns row i
-        if (on && lane < NR) {
-            double s = -1.0;
-            if (lane < n) for (int j = 0; j < n; j++) { const double v = fabs(A[lane * ld + j]); s = v > s ? v : s; }
-            scal[lane] = lane < n ? 1.0 / s : 0.0;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-#pragma unroll
-        for (int i = 0; i < NR; i++) {
-            a0[i] = (c0 && i < n) ? A[i * ld + lane] : 0.0;
-            a1[i] = (c1 && i < n) ? A[i * ld + lane + 64] : 0.0;
-        }
-        bool ok = true;
-        unsigned int used = 0u;
-        lds_double *colbuf = scal + 3 * NR;                // column k of the current step, published by its lane
-        for (int k = 0; k < n; k++) {
-            if (lane == k) {
-#pragma unroll
-                for (int i = 0; i < NR; i++) colbuf[i] = a0[i];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-            // scaled pivot search, one row per lane: the magnitude only ranks candidates, so single precision with the
-            // lane in the low mantissa bits and one 32-bit wave max (scal is 0 for padding rows)
-            float mf = 0.0f;
-            if (lane < NR && !((used >> lane) & 1u)) mf = (float)(fabs(colbuf[lane]) * scal[lane]);
-            const unsigned int key = __ockl_wfred_max_u32((__float_as_uint(mf) & ~0x3Fu) | (unsigned int)(63 - lane));
-            const int r = __builtin_amdgcn_readfirstlane(63 - (int)(key & 0x3Fu));
-            if (on && ok && !(__uint_as_float(key & ~0x3Fu) > 1.0e-20f)) ok = false;
-            used |= 1u << r;
-            // the pivot column in registers first (wave-uniform addresses: LDS broadcasts, all in flight together): a load inside
-            // a `(i == r) ? .. : ..` arm turns into a scalar branch with its own s_waitcnt per row
-            double cb[NR];
-#pragma unroll
-            for (int i = 0; i < NR; i++) cb[i] = colbuf[i];
-            // this lane's pivot-row entries and the pivot: r is wave-uniform but not a compile-time register index, so a chain of
-            // uniform branches picks them (a 0/1-weighted FMA sum is NR dependent fp64 FMAs at ~30 cycles each)
-            double p0 = 0.0, p1 = 0.0, piv = 1.0;
-#pragma unroll
-            for (int i = 0; i < NR; i++) if (i == r) { p0 = a0[i]; p1 = a1[i]; piv = cb[i]; }
-            double inv = tg_rcp(piv);
-            if (lane == 0 && on) { ((__attribute__((address_space(3))) int *)(scal + 2 * NR))[r] = k; dinv[r] = 1.0 / piv; }
-            const double ginv = (on && ok) ? inv : 0.0;
-#pragma unroll
-            for (int i = 0; i < NR; i++) {
-                const double l = cb[i] * ((i == r) ? 0.0 : ginv);
-                a0[i] = fma(-l, p0, a0[i]); a1[i] = fma(-l, p1, a1[i]);
-            }
-            // the next step overwrites colbuf: its reads above are ordered before those writes (same wavefront, in-order LDS)
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        // physical row i solved variable var_i; write x = a / pivot into the row of the variable (right-hand sides only)
-        if (on && ok) {
-            const __attribute__((address_space(3))) int *var = (const __attribute__((address_space(3))) int *)(scal + 2 * NR);
-#pragma unroll
-            for (int i = 0; i < NR; i++) {
-                if (i < n) {
-                    const int v = var[i];
-                    const double d = dinv[i];
-                    if (c0 && lane >= n) A[v * ld + lane] = a0[i] * d;
-                    if (c1) A[v * ld + lane + 64] = a1[i] * d;
-                }
-            }
-        }
-        TG_SYNC();
-        return ok;
-    }
-#endif
-
     // =====================================================================================================
     // First derivatives of the step map (reference MidpointVI_calc_deriv1, midpointvi.c:749-1120).
     // The reference factors M2 and the projected matrix -Dh2 M2^-1 Dh1T separately and solves each
@@ -3133,8 +2408,8 @@ struct Core {
             if constexpr (TEAM == 64 && NF > 16 && NF <= 31 && W1 <= 128) {
                 constexpr int NP = ((NF + 3) >> 2) << 2;
                 double *sc = S + (cpt ? P.o_J : P.o_G);   // the joint poses (compact slice, where T12 sits there: the Jacobians) are dead during the solve
-                if (extra) return Core<64, SPRINGS, PROG>::template gj_panel_rhs<NP, (W1 + 15) / 16>(on, AUG, NF, W1, ld, lane, sc);
-                return Core<64, SPRINGS, PROG>::template gj_panel_rhs<NP, (W0 + 15) / 16>(on, AUG, NF, W0, ld, lane, sc);
+                if (extra) return gj_panel_rhs<NP, (W1 + 15) / 16>(on, AUG, NF, W1, ld, lane, sc);
+                return gj_panel_rhs<NP, (W0 + 15) / 16>(on, AUG, NF, W0, ld, lane, sc);
             }
         }
 #endif
@@ -3144,14 +2419,14 @@ struct Core {
             if (TEAM == 64 && w <= 128 && nb4 <= 8 && P.gjc_ok) {
                 double *sc = S + (cpt ? P.o_J : P.o_G);   // the joint poses / the Jacobians are dead during the solve
                 switch (nb4) {
-                case 1: return Core<TEAM>::template gj_cols<4>(on, AUG, nf, w, ld, sc, lane);
-                case 2: return Core<TEAM>::template gj_cols<8>(on, AUG, nf, w, ld, sc, lane);
-                case 3: return Core<TEAM>::template gj_cols<12>(on, AUG, nf, w, ld, sc, lane);
-                case 4: return Core<TEAM>::template gj_cols<16>(on, AUG, nf, w, ld, sc, lane);
-                case 5: return Core<TEAM>::template gj_cols<20>(on, AUG, nf, w, ld, sc, lane);
-                case 6: return Core<TEAM>::template gj_cols<24>(on, AUG, nf, w, ld, sc, lane);
-                case 7: return Core<TEAM>::template gj_cols<28>(on, AUG, nf, w, ld, sc, lane);
-                default: return Core<TEAM>::template gj_cols<32>(on, AUG, nf, w, ld, sc, lane);
+                case 1: return gj_cols<TEAM, 4>(on, AUG, nf, w, ld, sc, lane);
+                case 2: return gj_cols<TEAM, 8>(on, AUG, nf, w, ld, sc, lane);
+                case 3: return gj_cols<TEAM, 12>(on, AUG, nf, w, ld, sc, lane);
+                case 4: return gj_cols<TEAM, 16>(on, AUG, nf, w, ld, sc, lane);
+                case 5: return gj_cols<TEAM, 20>(on, AUG, nf, w, ld, sc, lane);
+                case 6: return gj_cols<TEAM, 24>(on, AUG, nf, w, ld, sc, lane);
+                case 7: return gj_cols<TEAM, 28>(on, AUG, nf, w, ld, sc, lane);
+                default: return gj_cols<TEAM, 32>(on, AUG, nf, w, ld, sc, lane);
                 }
             }
         }
@@ -4466,14 +3741,14 @@ struct Core {
         if constexpr (std::is_same<Real, double>::value) if (TEAM >= 4 && 4 * nb4 <= TEAM && nb4 <= 8) {
             double *Ad = S + P.o_Df;
             switch (nb4) {
-            case 1: return Core<TEAM>::template gj_rows<4>(on, Ad, P.nf, P.df_ld, lane);
-            case 2: return Core<TEAM>::template gj_rows<(TEAM >= 8 ? 8 : 4)>(on, Ad, P.nf, P.df_ld, lane);
-            case 3: return Core<TEAM>::template gj_rows<(TEAM >= 12 ? 12 : 4)>(on, Ad, P.nf, P.df_ld, lane);
-            case 4: return Core<TEAM>::template gj_rows<(TEAM >= 16 ? 16 : 4)>(on, Ad, P.nf, P.df_ld, lane);
-            case 5: return Core<TEAM>::template gj_rows<(TEAM >= 20 ? 20 : 4)>(on, Ad, P.nf, P.df_ld, lane);
-            case 6: return Core<TEAM>::template gj_rows<(TEAM >= 24 ? 24 : 4)>(on, Ad, P.nf, P.df_ld, lane);
-            case 7: return Core<TEAM>::template gj_rows<(TEAM >= 28 ? 28 : 4)>(on, Ad, P.nf, P.df_ld, lane);
-            default: return Core<TEAM>::template gj_rows<(TEAM >= 32 ? 32 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            case 1: return gj_rows<TEAM, 4>(on, Ad, P.nf, P.df_ld, lane);
+            case 2: return gj_rows<TEAM, (TEAM >= 8 ? 8 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            case 3: return gj_rows<TEAM, (TEAM >= 12 ? 12 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            case 4: return gj_rows<TEAM, (TEAM >= 16 ? 16 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            case 5: return gj_rows<TEAM, (TEAM >= 20 ? 20 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            case 6: return gj_rows<TEAM, (TEAM >= 24 ? 24 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            case 7: return gj_rows<TEAM, (TEAM >= 28 ? 28 : 4)>(on, Ad, P.nf, P.df_ld, lane);
+            default: return gj_rows<TEAM, (TEAM >= 32 ? 32 : 4)>(on, Ad, P.nf, P.df_ld, lane);
             }
         }
 #endif
@@ -4914,23 +4189,23 @@ struct Core {
             // plus the pivot-column traffic per pivot step on the same system)
             Real *sc = S + P.o_G;   // the joint poses are dead during the solve
             switch (nb4) {
-            case 5: ok = Core<64, SPRINGS, PROG>::template gj_panel_rhs<20, 8>(on, AUG, nf, w, ld, lane, sc); break;
-            case 6: ok = Core<64, SPRINGS, PROG>::template gj_panel_rhs<24, 8>(on, AUG, nf, w, ld, lane, sc); break;
-            case 7: ok = Core<64, SPRINGS, PROG>::template gj_panel_rhs<28, 8>(on, AUG, nf, w, ld, lane, sc); break;
-            default: ok = Core<64, SPRINGS, PROG>::template gj_panel_rhs<32, 8>(on, AUG, nf, w, ld, lane, sc); break;
+            case 5: ok = gj_panel_rhs<20, 8>(on, AUG, nf, w, ld, lane, sc); break;
+            case 6: ok = gj_panel_rhs<24, 8>(on, AUG, nf, w, ld, lane, sc); break;
+            case 7: ok = gj_panel_rhs<28, 8>(on, AUG, nf, w, ld, lane, sc); break;
+            default: ok = gj_panel_rhs<32, 8>(on, AUG, nf, w, ld, lane, sc); break;
             }
         } else
         if (TEAM == 64 && w <= 128 && nb4 <= 8 && P.gjc_ok) {
             Real *sc = S + P.o_G;   // the joint poses are dead during the solve
             switch (nb4) {
-            case 1: ok = Core<TEAM>::template gj_cols<4>(on, AUG, nf, w, ld, sc, lane); break;
-            case 2: ok = Core<TEAM>::template gj_cols<8>(on, AUG, nf, w, ld, sc, lane); break;
-            case 3: ok = Core<TEAM>::template gj_cols<12>(on, AUG, nf, w, ld, sc, lane); break;
-            case 4: ok = Core<TEAM>::template gj_cols<16>(on, AUG, nf, w, ld, sc, lane); break;
-            case 5: ok = Core<TEAM>::template gj_cols<20>(on, AUG, nf, w, ld, sc, lane); break;
-            case 6: ok = Core<TEAM>::template gj_cols<24>(on, AUG, nf, w, ld, sc, lane); break;
-            case 7: ok = Core<TEAM>::template gj_cols<28>(on, AUG, nf, w, ld, sc, lane); break;
-            default: ok = Core<TEAM>::template gj_cols<32>(on, AUG, nf, w, ld, sc, lane); break;
+            case 1: ok = gj_cols<TEAM, 4>(on, AUG, nf, w, ld, sc, lane); break;
+            case 2: ok = gj_cols<TEAM, 8>(on, AUG, nf, w, ld, sc, lane); break;
+            case 3: ok = gj_cols<TEAM, 12>(on, AUG, nf, w, ld, sc, lane); break;
+            case 4: ok = gj_cols<TEAM, 16>(on, AUG, nf, w, ld, sc, lane); break;
+            case 5: ok = gj_cols<TEAM, 20>(on, AUG, nf, w, ld, sc, lane); break;
+            case 6: ok = gj_cols<TEAM, 24>(on, AUG, nf, w, ld, sc, lane); break;
+            case 7: ok = gj_cols<TEAM, 28>(on, AUG, nf, w, ld, sc, lane); break;
+            default: ok = gj_cols<TEAM, 32>(on, AUG, nf, w, ld, sc, lane); break;
             }
         } else
 #endif
@@ -5329,14 +4604,14 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 double *Ad = S + P.o_Df;
                 if (PIVOT < 0 ? A.exact_pivot != 0 : PIVOT == 1) {
                 switch (nb4) {
-                case 1: ok = Core<TEAM>::template gj_rows_exact<4>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 2: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 8 ? 8 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 3: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 12 ? 12 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 4: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 16 ? 16 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 5: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 20 ? 20 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 6: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 24 ? 24 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 7: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 28 ? 28 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                default: ok = Core<TEAM>::template gj_rows_exact<(TEAM >= 32 ? 32 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 1: ok = gj_rows_exact<TEAM, 4>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 2: ok = gj_rows_exact<TEAM, (TEAM >= 8 ? 8 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 3: ok = gj_rows_exact<TEAM, (TEAM >= 12 ? 12 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 4: ok = gj_rows_exact<TEAM, (TEAM >= 16 ? 16 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 5: ok = gj_rows_exact<TEAM, (TEAM >= 20 ? 20 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 6: ok = gj_rows_exact<TEAM, (TEAM >= 24 ? 24 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 7: ok = gj_rows_exact<TEAM, (TEAM >= 28 ? 28 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                default: ok = gj_rows_exact<TEAM, (TEAM >= 32 ? 32 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
                 }
                 } else
 #if defined(TG_GJ_PANEL_DEFAULT)
@@ -5347,22 +4622,22 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 if (TEAM == 64 && nb4 >= 5 && P.nf <= 31 && 12 * P.n_items >= 128) {
                     double *scr = S + P.o_J;
                     switch (nb4) {
-                    case 5: ok = Core<64>::template gj_panel<20>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
-                    case 6: ok = Core<64>::template gj_panel<24>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
-                    case 7: ok = Core<64>::template gj_panel<28>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
-                    default: ok = Core<64>::template gj_panel<32>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
+                    case 5: ok = gj_panel<20>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
+                    case 6: ok = gj_panel<24>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
+                    case 7: ok = gj_panel<28>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
+                    default: ok = gj_panel<32>(!done, Ad, P.nf, P.df_ld, lane, scr); break;
                     }
                 } else
 #endif
                 switch (nb4) {
-                case 1: ok = Core<TEAM>::template gj_rows<4>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 2: ok = Core<TEAM>::template gj_rows<(TEAM >= 8 ? 8 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 3: ok = Core<TEAM>::template gj_rows<(TEAM >= 12 ? 12 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 4: ok = Core<TEAM>::template gj_rows<(TEAM >= 16 ? 16 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 5: ok = Core<TEAM>::template gj_rows<(TEAM >= 20 ? 20 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 6: ok = Core<TEAM>::template gj_rows<(TEAM >= 24 ? 24 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                case 7: ok = Core<TEAM>::template gj_rows<(TEAM >= 28 ? 28 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
-                default: ok = Core<TEAM>::template gj_rows<(TEAM >= 32 ? 32 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 1: ok = gj_rows<TEAM, 4>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 2: ok = gj_rows<TEAM, (TEAM >= 8 ? 8 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 3: ok = gj_rows<TEAM, (TEAM >= 12 ? 12 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 4: ok = gj_rows<TEAM, (TEAM >= 16 ? 16 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 5: ok = gj_rows<TEAM, (TEAM >= 20 ? 20 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 6: ok = gj_rows<TEAM, (TEAM >= 24 ? 24 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                case 7: ok = gj_rows<TEAM, (TEAM >= 28 ? 28 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
+                default: ok = gj_rows<TEAM, (TEAM >= 32 ? 32 : 4)>(!done, Ad, P.nf, P.df_ld, lane); break;
                 }
             } else
 #endif

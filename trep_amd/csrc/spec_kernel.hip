@@ -11,7 +11,7 @@
 
 #include <type_traits>
 
-#define TG_GJ_PANEL_DEFAULT 1      // 17..31 unknowns, full-wave team: the Newton systems go through gj_panel (mvi_core.hpp)
+#define TG_GJ_PANEL_DEFAULT 1      // 17..31 unknowns, full-wave team: the Newton systems go through gj_panel (gj_solve.hpp)
 #include "mvi_core.hpp"
 #include TG_SPEC_HEADER
 
@@ -110,8 +110,8 @@ __global__ __launch_bounds__(64, 2) void k_spec_debug_solve(const double *A_in, 
     } else load_dense();
     __syncthreads();
     if (!ok) {
-        if constexpr (SPEC_TEAM == 64 && nb4 >= 5 && nf <= 31 && 12 * SpecProg::n_items >= 128) ok = tg::Core<64>::gj_panel<4 * nb4>(true, S + P.o_Df, nf, ld, lane, S + P.o_J);
-        else if constexpr (SPEC_TEAM == 64 && nb4 <= 8) ok = tg::Core<64>::gj_rows<4 * nb4>(true, S + P.o_Df, nf, ld, lane);
+        if constexpr (SPEC_TEAM == 64 && nb4 >= 5 && nf <= 31 && 12 * SpecProg::n_items >= 128) ok = tg::gj_panel<4 * nb4>(true, S + P.o_Df, nf, ld, lane, S + P.o_J);
+        else if constexpr (SPEC_TEAM == 64 && nb4 <= 8) ok = tg::gj_rows<64, 4 * nb4>(true, S + P.o_Df, nf, ld, lane);
         path = ok ? 2 : -1;
     }
     __syncthreads();

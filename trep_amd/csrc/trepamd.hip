@@ -447,33 +447,33 @@ __global__ void k_debug_solve(int n, int ld, int exact, const double *A_in, doub
     __syncthreads();
     bool ok = true;
     if (exact == 1) switch ((n + 3) >> 2) {
-    case 1: ok = tg::Core<64>::gj_rows_exact<4, true>(true, lds, n, ld, lane, trace); break;
-    case 2: ok = tg::Core<64>::gj_rows_exact<8, true>(true, lds, n, ld, lane, trace); break;
-    case 3: ok = tg::Core<64>::gj_rows_exact<12, true>(true, lds, n, ld, lane, trace); break;
-    case 4: ok = tg::Core<64>::gj_rows_exact<16, true>(true, lds, n, ld, lane, trace); break;
-    case 5: ok = tg::Core<64>::gj_rows_exact<20, true>(true, lds, n, ld, lane, trace); break;
-    case 6: ok = tg::Core<64>::gj_rows_exact<24, true>(true, lds, n, ld, lane, trace); break;
-    case 7: ok = tg::Core<64>::gj_rows_exact<28, true>(true, lds, n, ld, lane, trace); break;
-    default: ok = tg::Core<64>::gj_rows_exact<32, true>(true, lds, n, ld, lane, trace); break;
+    case 1: ok = tg::gj_rows_exact<64, 4, true>(true, lds, n, ld, lane, trace); break;
+    case 2: ok = tg::gj_rows_exact<64, 8, true>(true, lds, n, ld, lane, trace); break;
+    case 3: ok = tg::gj_rows_exact<64, 12, true>(true, lds, n, ld, lane, trace); break;
+    case 4: ok = tg::gj_rows_exact<64, 16, true>(true, lds, n, ld, lane, trace); break;
+    case 5: ok = tg::gj_rows_exact<64, 20, true>(true, lds, n, ld, lane, trace); break;
+    case 6: ok = tg::gj_rows_exact<64, 24, true>(true, lds, n, ld, lane, trace); break;
+    case 7: ok = tg::gj_rows_exact<64, 28, true>(true, lds, n, ld, lane, trace); break;
+    default: ok = tg::gj_rows_exact<64, 32, true>(true, lds, n, ld, lane, trace); break;
     }
     else if (exact == 2) {     // the full-wave panel solver (default pivot rule), 16 < n < 32; scratch behind the trace words
         double *scr = lds + n * ld + 16;
         switch ((n + 3) >> 2) {
-        case 5: ok = tg::Core<64>::gj_panel<20, true>(true, lds, n, ld, lane, scr, trace); break;
-        case 6: ok = tg::Core<64>::gj_panel<24, true>(true, lds, n, ld, lane, scr, trace); break;
-        case 7: ok = tg::Core<64>::gj_panel<28, true>(true, lds, n, ld, lane, scr, trace); break;
-        default: ok = tg::Core<64>::gj_panel<32, true>(true, lds, n, ld, lane, scr, trace); break;
+        case 5: ok = tg::gj_panel<20, true>(true, lds, n, ld, lane, scr, trace); break;
+        case 6: ok = tg::gj_panel<24, true>(true, lds, n, ld, lane, scr, trace); break;
+        case 7: ok = tg::gj_panel<28, true>(true, lds, n, ld, lane, scr, trace); break;
+        default: ok = tg::gj_panel<32, true>(true, lds, n, ld, lane, scr, trace); break;
         }
     }
     else switch ((n + 3) >> 2) {
-    case 1: ok = tg::Core<64>::gj_rows<4, true>(true, lds, n, ld, lane, trace); break;
-    case 2: ok = tg::Core<64>::gj_rows<8, true>(true, lds, n, ld, lane, trace); break;
-    case 3: ok = tg::Core<64>::gj_rows<12, true>(true, lds, n, ld, lane, trace); break;
-    case 4: ok = tg::Core<64>::gj_rows<16, true>(true, lds, n, ld, lane, trace); break;
-    case 5: ok = tg::Core<64>::gj_rows<20, true>(true, lds, n, ld, lane, trace); break;
-    case 6: ok = tg::Core<64>::gj_rows<24, true>(true, lds, n, ld, lane, trace); break;
-    case 7: ok = tg::Core<64>::gj_rows<28, true>(true, lds, n, ld, lane, trace); break;
-    default: ok = tg::Core<64>::gj_rows<32, true>(true, lds, n, ld, lane, trace); break;
+    case 1: ok = tg::gj_rows<64, 4, true>(true, lds, n, ld, lane, trace); break;
+    case 2: ok = tg::gj_rows<64, 8, true>(true, lds, n, ld, lane, trace); break;
+    case 3: ok = tg::gj_rows<64, 12, true>(true, lds, n, ld, lane, trace); break;
+    case 4: ok = tg::gj_rows<64, 16, true>(true, lds, n, ld, lane, trace); break;
+    case 5: ok = tg::gj_rows<64, 20, true>(true, lds, n, ld, lane, trace); break;
+    case 6: ok = tg::gj_rows<64, 24, true>(true, lds, n, ld, lane, trace); break;
+    case 7: ok = tg::gj_rows<64, 28, true>(true, lds, n, ld, lane, trace); break;
+    default: ok = tg::gj_rows<64, 32, true>(true, lds, n, ld, lane, trace); break;
     }
     __syncthreads();
     if (lane < n) { x_out[lane] = lds[lane * ld + n]; piv_out[lane] = trace[lane]; }
