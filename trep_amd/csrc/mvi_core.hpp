@@ -142,6 +142,10 @@ template <class P, class = void> struct tg_static_pk { static constexpr bool val
 template <class P> struct tg_static_pk<P, typename std::enable_if<(P::bbd_pk_ok >= 0)>::type> { static constexpr bool value = P::bbd_pk_ok != 0 && tg_static_wev<P>::value && tg_static_bbd<P>::value; };
 #endif
 
+// ... and the closed forms of a floating base's translational prefix in it (program.hpp, fb_*)
+template <class P, class = void> struct tg_static_fb { static constexpr bool value = false; };
+template <class P> struct tg_static_fb<P, typename std::enable_if<(P::fb_on >= 0)>::type> { static constexpr bool value = P::fb_on != 0 && tg_static_wev<P>::value; };
+
 enum { MODE_ROLLOUT = 0, MODE_CALC_P2 = 1, MODE_CALC_F = 2, MODE_DERIV1 = 3, MODE_DERIV2Z = 4, MODE_DYNAMICS = 5, MODE_DYN_DERIV1 = 6, MODE_ENERGY = 7, MODE_LAGRANGIAN = 8 };
 
 struct RunArgs {
@@ -375,6 +379,7 @@ struct Core {
     // world-frame evaluation (eval_world): the lane's row of P.wev_lane and its config-pair records, constants of the lane for the whole
     // kernel; w_k = [V_k^-, s_k] of the lane's config between the evaluation and the Newton matrix
     int wvl[4] = {0, 0, 0, 0}, wpair[4] = {0, 0, 0, 0};
+    int wfb[2] = {0, 0};      // translational prefix (program.hpp, fb_abx): how many prefix configs lie above the lane's config, the places of those entries in the packed image
     int wdhx[2] = {0, 0}, wrhs = 0, wone = -1;      // packed Newton image: the lane's two Dh items (n | two addresses), its right-hand-side entry, its identity entry
     double wev_w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     bool pk_image = false;    // the Newton matrix goes to the packed image (the kernel solves it with the structured solve: default pivot rule only)
@@ -485,12 +490,24 @@ struct Core {
                 if (rollout) {
 #pragma unroll
                     for (int i = 0; i < 4; i++) wvl[i] = P.wev_lane[4 * lane + i];
+                    // (with a translational prefix: the shorter lists and pair list, and the lane's closed-form entries)
+                    constexpr bool FB = tg_static_fb<SP>::value;
+                    constexpr int NP = FB ? SP::fb_npairs : SP::n_cmpairs;
+                    const int *pairs = FB ? P.fb_pair : P.cmp_pair, *pairsx = FB ? P.fb_pairx : P.wev_pairx;
+                    if constexpr (FB) {
 #pragma unroll
-                    for (int u = 0; u < 4; u++) wpair[u] = P.cmp_pair[lane + u * TEAM < SP::n_cmpairs ? lane + u * TEAM : 0];
+                        for (int i = 0; i < 3; i++) wvl[i] = P.fb_lane[4 * lane + i];
+#pragma unroll
+                        for (int i = 0; i < 2; i++) wfb[i] = P.fb_abx[2 * (lane < SP::nd ? lane : 0) + i];
+                        if (lane >= SP::nd) wfb[0] = 0;
+                    }
+                    constexpr int TP = FB ? (NP + TEAM - 1) / TEAM : 4;      // (with the prefix: only the trips phase D makes)
+#pragma unroll
+                    for (int u = 0; u < TP; u++) wpair[u] = pairs[lane + u * TEAM < NP ? lane + u * TEAM : 0];
                     if constexpr (tg_static_pk<SP>::value) {
                         // the config pairs with their two places in the packed image: a | b << 6 | address (a, b) << 12 | address (b, a) << 22
 #pragma unroll
-                        for (int u = 0; u < 4; u++) wpair[u] = P.wev_pairx[lane + u * TEAM < SP::n_cmpairs ? lane + u * TEAM : 0];
+                        for (int u = 0; u < TP; u++) wpair[u] = pairsx[lane + u * TEAM < NP ? lane + u * TEAM : 0];
 #pragma unroll
                         for (int u = 0; u < 2; u++) wdhx[u] = P.wev_dhx[lane + u * TEAM < SP::n_dhr ? lane + u * TEAM : 0];
                         wrhs = P.bbd_map[(lane < SP::nf ? lane : 0) * (SP::nf + 1) + SP::nf];
@@ -1254,8 +1271,10 @@ struct Core {
     }
     TG_HD void eval_world(bool on) {
         typedef typename std::remove_cv<PROG>::type SP;
-        constexpr int nd = SP::nd, NB = SP::n_bodies, NG = SP::n_cgroups, MAXD = SP::wev_depth;
+        constexpr bool FB = tg_static_fb<SP>::value;      // translational prefix: shared list record, closed-form matrix entries
+        constexpr int nd = SP::nd, NB = SP::n_bodies, NG = SP::n_cgroups, MAXD = FB ? SP::fb_depth : SP::wev_depth;
         static_assert(TEAM == 64 && nd + 3 * NB < 64, "eval_world: one lane per config and per (body, axis), and the last lane free");
+        static_assert(!FB || nd + 3 * NB < 63, "eval_world: the prefix record needs a second lane without a role");
         static_assert((SP::o_csw & 1) == 0 && (SP::o_I & 1) == 0 && (SP::o_cmp & 1) == 0 && (SP::o_G & 1) == 0, "eval_world: 16-byte LDS accesses");
         // table rows of E3, requested ahead of the pose sweep: the end point's anchor row (as fetch_attach), the body lane's constant offset
         const int l0 = tg_opaque(lane);
@@ -1296,9 +1315,11 @@ struct Core {
                 const double val = g[0] * eo0 + g[1] * eo1 + g[2] * eo2 + g[3];
                 S[P.o_pE + lane] = eanc < 0 ? eor : val;
             }
-            if (lane < nd || lane == TEAM - 1) {       // (the last lane, which has no other role, writes the all-zero record the padded list entries point at)
+            // (the last lane, which has no other role, writes the all-zero record the padded list entries point at; with a translational
+            // prefix the lane before it writes record nd + 1: the rates of the prefix configs by axis, what the u halves of the prefix sum to)
+            if (lane < nd || lane == TEAM - 1 || (FB && lane == TEAM - 2)) {
                 const bool real = lane < nd;
-                const int rec = real ? lane : nd;
+                const int rec = real ? lane : (FB && lane == TEAM - 2 ? nd + 1 : nd);
                 const int oj = real ? wvl[3] & 0xFFFF : 0, kind = real ? (wvl[3] >> 16) & 0xFF : (int)TG_TX;
                 const bool prismatic = kind <= TG_TZ;
                 const int ax = prismatic ? kind - TG_TX : kind - TG_RX;
@@ -1312,6 +1333,10 @@ struct Core {
                 sv[3] = prismatic ? 0.0 : a0; sv[4] = prismatic ? 0.0 : a1; sv[5] = prismatic ? 0.0 : a2;
 #pragma unroll
                 for (int r = 0; r < 6; r++) { sv[r] = real ? sv[r] : 0.0; uv[r] = sv[r] * dqk; }
+                if constexpr (FB) {
+#pragma unroll
+                    for (int i = 0; i < SP::fb_n; i++) { const double dqa = S[P.o_dq + SP::fb_cfg[i]]; uv[SP::fb_axis[i]] = lane == TEAM - 2 ? dqa : uv[SP::fb_axis[i]]; }
+                }
                 st6<true>(SW + 12 * rec, sv);
                 st6<true>(SW + 12 * rec + 6, uv);
             } else if (blane) {
@@ -1379,7 +1404,9 @@ struct Core {
                     const int k = ct.rec[u][1], oj = ct.rec[u][2], w = ct.rec[u][3], oe1 = ct.rec[u][4], oe2 = ct.rec[u][5];
                     const int side = w & 0xFF, kind = (w >> 8) & 0xFF, type = (w >> 16) & 0xFF, comp = w >> 24;
                     const int ojc = oj < 0 ? 0 : oj;
-                    double d1[3], d2[3];
+                    // (what no record of this system has is decided here: a second side, a point constraint, a length config)
+                    constexpr bool ONE_SIDED = SP::dhr_sides == 1, DIST_ONLY = SP::dhr_types == (1 << TG_CONSTRAINT_DISTANCE), NO_LEN = !(SP::dhr_sides & 4);
+                    double d1[3], d2[3] = {0.0, 0.0, 0.0};
                     const double *gj = G2 + ojc;
                     const bool prismatic = kind <= TG_TZ;
                     const int ax = prismatic ? kind - TG_TX : kind - TG_RX;
@@ -1389,19 +1416,20 @@ struct Core {
                         const double dx = pe[0] - gj[3], dy = pe[1] - gj[7], dz = pe[2] - gj[11];
                         d1[0] = prismatic ? wx : wy * dz - wz * dy; d1[1] = prismatic ? wy : wz * dx - wx * dz; d1[2] = prismatic ? wz : wx * dy - wy * dx;
                     }
-                    {
+                    if constexpr (!ONE_SIDED) {
                         const double *pe = S + P.o_pE + oe2;
                         const double dx = pe[0] - gj[3], dy = pe[1] - gj[7], dz = pe[2] - gj[11];
                         d2[0] = prismatic ? wx : wy * dz - wz * dy; d2[1] = prismatic ? wy : wz * dx - wx * dz; d2[2] = prismatic ? wz : wx * dy - wy * dx;
                     }
                     const double s1 = (side & 1) ? 1.0 : 0.0, s2 = (side & 2) ? 1.0 : 0.0;
-                    const double dx = s1 * d1[0] - s2 * d2[0], dy = s1 * d1[1] - s2 * d2[1], dz = s1 * d1[2] - s2 * d2[2];
+                    // (one-sided: 1.0 * d1 - 0.0 * d2 is d1)
+                    const double dx = ONE_SIDED ? d1[0] : s1 * d1[0] - s2 * d2[0], dy = ONE_SIDED ? d1[1] : s1 * d1[1] - s2 * d2[1], dz = ONE_SIDED ? d1[2] : s1 * d1[2] - s2 * d2[2];
                     double val;
-                    if (type == TG_CONSTRAINT_POINT) val = comp == 0 ? dx : (comp == 1 ? dy : dz);
+                    if (!DIST_ONLY && type == TG_CONSTRAINT_POINT) val = comp == 0 ? dx : (comp == 1 ? dy : dz);
                     else {
                         const double *a = S + P.o_pE + oe1, *b = S + P.o_pE + oe2;
                         val = (a[0] - b[0]) * dx + (a[1] - b[1]) * dy + (a[2] - b[2]) * dz;
-                        if (side & 4) val -= S[P.o_q2 + k];
+                        if (!NO_LEN && (side & 4)) val -= S[P.o_q2 + k];
                         val *= 2.0;
                     }
                     S[P.o_Dh2 + n] = val;
@@ -1873,10 +1901,12 @@ struct Core {
     // registers, the composites in CMP -- so the two phases that re-derived them from the body-frame items (A, B) are gone.
     // PK: the image in the structured solve's own order (bbd.hpp, BbdPacked) -- every entry goes to its one place there, from the lane's
     // table rows; !PK: the dense image [nf][ld], which the pivoting fallback solves.  SKIPC: the per-config vectors are in place already
-    // (the dense re-assembly after a failed structured solve).
+    // (a dense re-assembly after a failed structured solve; it has no caller today -- the fallback unpacks the packed image through bbd_map --
+    // and refuses to compile with a translational prefix, whose closed-form entries phase C stores).
     template <bool PK, bool SKIPC = false> TG_HD void newton_matrix_world(bool on) {
         typedef typename std::remove_cv<PROG>::type SP;
-        constexpr int nd = SP::nd, nf = SP::nf, ld = SP::df_ld, NP = SP::n_cmpairs;
+        constexpr bool FB = tg_static_fb<SP>::value;      // translational prefix: its off-diagonal pairs are closed forms, written in phase C
+        constexpr int nd = SP::nd, nf = SP::nf, ld = SP::df_ld, NP = FB ? SP::fb_npairs : SP::n_cmpairs;
         constexpr int NCLEAR = PK ? SP::bbd_pk_size : nf * ld;
         constexpr int TP = (NP + TEAM - 1) / TEAM;
         double *A = S + P.o_Df, *SW = S + P.o_csw, *CZ = S + P.o_ccz;
@@ -1890,6 +1920,26 @@ struct Core {
             const tg_d2 z2 = {0.0, 0.0};
             if (on) TG_FOR(i, NCLEAR >> 1) A2[i] = z2;
         }
+        const double qdt = 0.25 * dt, rdt = inv_dt;
+        // the entries (a, b) and (b, a) of every prefix config a above the lane's config b: s_a = (e_x, 0) and w_a = 0 exactly, so of the four
+        // inner products of phase D  s_a . I s_b = (I s_b)[x],  s_a . Z_b = Z_b[x]  and the two with w_a are zero -- the same final expressions
+        // as there.  Behind the image clear (same wave, in order), like the identity entries of phase D.
+        auto closed_forms = [&](const double *Is, const double *Z) {
+            if constexpr (FB) {
+                const int m = (int)((unsigned)wfb[0] >> 30);
+#pragma unroll
+                for (int i = 0; i < SP::fb_n; i++) {
+                    if (i < m) {
+                        const double mab = Is[SP::fb_axis[i]], cab = Z[SP::fb_axis[i]];
+                        const double sym = qdt * 0.0 - rdt * mab, skew = 0.5 * (0.0 - cab);
+                        const int p_ab = i == 0 ? wfb[0] : (i == 1 ? wfb[0] >> 20 : wfb[1] >> 10), p_ba = i == 0 ? wfb[0] >> 10 : (i == 1 ? wfb[1] : wfb[1] >> 20);
+                        const int e_ab = PK ? p_ab & 0x3FF : SP::fb_cfg[i] * ld + lane, e_ba = PK ? p_ba & 0x3FF : lane * ld + SP::fb_cfg[i];
+                        A[e_ab] = sym + skew; A[e_ba] = sym - skew;
+                    }
+                }
+            }
+        };
+        static_assert(!(SKIPC && FB), "newton_matrix_world: SKIPC has no caller (the pivoting fallback unpacks the packed image through bbd_map); with a translational prefix it would have to store the closed-form entries from the per-config vectors in CZ");
         if (!SKIPC && on && lane < nd) {
             const double *c = S + P.o_cmp + 16 * ((wvl[3] >> 24) & 0x7F);
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3], Dxx = c[4], Dxy = c[5], Dxz = c[6], Dyy = c[7], Dyz = c[8], Dzz = c[9];
@@ -1918,6 +1968,7 @@ struct Core {
             for (int r = 0; r < 6; r++) { o[r] = Is[r]; o[6 + r] = Z[r]; }
             o[12] = Gy * gz - Gz * gy; o[13] = Gz * gx - Gx * gz; o[14] = Gx * gy - Gy * gx;
             st6<true>(SW + SWS * lane + 6, wev_w);
+            closed_forms(Is, Z);
         }
         TG_SYNC();
         TG_STAMP(7);
@@ -1933,7 +1984,6 @@ struct Core {
                 }
             }
         }
-        const double qdt = 0.25 * dt, rdt = inv_dt;
 #pragma unroll
         for (int u = 0; u < TP; u++) {
             if (on && lane + u * TEAM < NP) {

@@ -178,6 +178,21 @@ struct DevProg {
     // (config, constraint) << 8 | of (constraint, config) << 18;  the right-hand side of variable i at bbd_map[i * (nf + 1) + nf]
     int bbd_pk_ok, bbd_pk_nr, bbd_pk_nc2, bbd_pk_tb, bbd_pk_tc2, bbd_pk_xs, bbd_pk_size, bbd_pk_nones;
     const int *bbd_map, *bbd_ones, *wev_pairx, *wev_dhx;
+    // translational prefix of a floating base: fb_n (0..3) joints from the world down, each prismatic on a dynamic config
+    // (fb_cfg, axis index fb_axis), with an identity pre-transform and an axis of its own -- their world twists are (e_axis, 0) and their
+    // brackets w vanish, exactly.  fb_on: the world-frame evaluation uses it (wev_ok and room for one more twist record, index nd + 1,
+    // whose u half holds the prefix rates by axis) -- then the kernel reads, instead of cmp_pair / wev_pairx / wev_lane (which stay what
+    // they were: the composite form and the test hooks read them),
+    //   fb_pair / fb_pairx [fb_npairs]  the config pairs without the off-diagonal ones whose first config is in the prefix (layouts of
+    //                                   cmp_pair / wev_pairx); those entries are closed forms of I s_b and Z_b, stored by lane b itself:
+    //   fb_abx [2 nd]                   lane b's two words: packed address of (a_0, b) | of (b, a_0) << 10 | of (a_1, b) << 20 | m << 30 and
+    //                                   of (b, a_1) | of (a_2, b) << 10 | of (b, a_2) << 20, m = number of prefix configs above b
+    //   fb_lane [64][4]                 wev_lane with the whole prefix at the start of a list replaced by the record nd + 1; fb_depth: longest
+    // dhr_sides / dhr_types: OR of the side bits / of 1 << constraint type over the dhr_pack records
+    int fb_n, fb_on, fb_npairs, fb_depth, dhr_sides, dhr_types;
+    int fb_cfg[3];
+    int fb_axis[3];
+    const int *fb_pair, *fb_pairx, *fb_abx, *fb_lane;
     // COMPACT slice of the first-derivative kernel (MODE_DERIV1 only; a_ok): with the step layout's pose union [o_sc, end of the base region)
     // dead once the midpoint is evaluated, and the two D.D2L2 tables only filled by the (item, item) pair loop after that, the table T12 moves
     // INTO the pose union, the full-width constraint Jacobians Dh1 / Dh2 (dead after the KKT matrix's constant blocks) into the place T22 takes
@@ -202,6 +217,7 @@ struct HostProgram {
     std::vector<int> dh_c, dh_cfg, dh_joint, dh_side, dh_lookup, cu_off;
     std::vector<double> damp, cs_k, cs_kq0, cs_c0, s_k, s_x0, s_c, c_nloc, wr_const, wr_Rloc, ncs_mb, ncs_tab;
     std::vector<int> ncs_i, bbd_tab, cmp_rep, cmp_grp, cmp_goff, cmp_gbody, cmp_pair, wev_lane, bbd_map, bbd_ones, wev_pairx, wev_dhx;
+    std::vector<int> fb_pair, fb_pairx, fb_abx, fb_lane;
     std::vector<unsigned char> newton_pattern;   // [nf * nf] structural non-zeros of the Newton matrix (symmetrised), host side only
     std::vector<int> wr_in, wr_kind;
     std::vector<int> cf_cfg, cf_in;
@@ -862,6 +878,26 @@ inline HostProgram build_program(const tg_system_desc *d) {
         // and per (body, axis), lists of at most 12 entries, and the twists + the zero record inside the J area (the q2 poses of the
         // dual sweep sit in the W area while they are read)
         P.wev_ok = 0; P.wev_depth = 0; P.wev_rc_ident = 1;
+        {   // translational prefix (DevProg::fb_*): a property of the tree alone
+            P.fb_n = P.fb_on = P.fb_npairs = P.fb_depth = P.dhr_sides = P.dhr_types = 0;
+            for (int i = 0; i < 3; i++) P.fb_cfg[i] = P.fb_axis[i] = -1;
+            int prev = -1, axes = 0;
+            while (P.fb_n < 3) {
+                int next = -1;
+                for (int j = 0; j < nj && next < 0; j++) {
+                    const int kind = H.j_kind[j];
+                    if (H.j_parent[j] == prev && kind >= TG_TX && kind <= TG_TZ && H.j_cfg[j] < nd && H.j_pre_ident[j] && !((axes >> (kind - TG_TX)) & 1)) next = j;
+                }
+                if (next < 0) break;
+                P.fb_cfg[P.fb_n] = H.j_cfg[next]; P.fb_axis[P.fb_n] = H.j_kind[next] - TG_TX; P.fb_n++;
+                axes |= 1 << (H.j_kind[next] - TG_TX); prev = next;
+            }
+            for (size_t n = 0; n < H.dhr_pack.size() / 8; n++) {
+                P.dhr_sides |= H.dhr_pack[8 * n + 3] & 0xFF;
+                P.dhr_types |= 1 << ((H.dhr_pack[8 * n + 3] >> 16) & 0xFF);
+            }
+            H.fb_pair.assign(1, 0); H.fb_pairx.assign(1, 0); H.fb_abx.assign(1, 0); H.fb_lane.assign(1, 0);
+        }
         for (int b = 0; b < nb; b++) {
             const double *C = &H.b_C[12 * (size_t)b];
             for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) if (C[4 * i + j] != (i == j ? 1.0 : 0.0)) P.wev_rc_ident = 0;
@@ -903,6 +939,38 @@ inline HostProgram build_program(const tg_system_desc *d) {
             }
             P.wev_ok = 1;
             P.o_ccz = P.o_csw + 12 * (nd + 1);      // one more twist record: the all-zero one the padded list entries point at
+            // the prefix in use: one more record again (the same three room conditions with it), a second lane without a role to write it
+            const int rec2 = 16 * P.n_cgroups + 12 * (nd + 2);
+            if (P.fb_n > 0 && nd + 3 * nb < 63 && rec2 <= 6 * nitems && rec2 + 15 * nd <= 12 * nitems) {
+                P.fb_on = 1;
+                P.o_ccz = P.o_csw + 12 * (nd + 2);
+                auto in_prefix = [&](int c) { for (int i = 0; i < P.fb_n; i++) if (P.fb_cfg[i] == c) return true; return false; };
+                H.fb_pair.clear();
+                for (int w : H.cmp_pair) if ((w & 0xFFFF) == (w >> 16) || !in_prefix(w & 0xFFFF)) H.fb_pair.push_back(w);
+                P.fb_npairs = (int)H.fb_pair.size();
+                H.fb_lane = H.wev_lane;
+                for (int l = 0; l < 64; l++) {
+                    std::vector<int> s = lists[l];
+                    bool whole = (int)s.size() >= P.fb_n;
+                    for (int i = 0; i < P.fb_n && whole; i++) if (s[i] != P.fb_cfg[i]) whole = false;
+                    if (whole) { s.erase(s.begin(), s.begin() + P.fb_n); s.insert(s.begin(), nd + 1); }
+                    P.fb_depth = std::max(P.fb_depth, (int)s.size());
+                    int w[3] = {0, 0, 0};
+                    for (int e = 0; e < 12; e++) w[e >> 2] |= (e < (int)s.size() ? s[e] : nd) << (8 * (e & 3));
+                    for (int i = 0; i < 3; i++) H.fb_lane[4 * l + i] = w[i];
+                }
+                // lane b's closed-form entries: the prefix configs above b are the first m of the prefix (a chain from the world)
+                H.fb_abx.assign(2 * (size_t)nd, 0);
+                int closed = 0, listed = 0;
+                for (int b = 0; b < nd; b++) {
+                    int m = 0;
+                    while (m < P.fb_n && m < (int)lists[b].size() && lists[b][m] == P.fb_cfg[m]) m++;
+                    for (int c : lists[b]) if (in_prefix(c)) listed++;
+                    closed += m;
+                    H.fb_abx[2 * b] = (int)((unsigned)m << 30);
+                }
+                if ((int)H.cmp_pair.size() - P.fb_npairs != closed || listed != closed) throw std::runtime_error("floating-base prefix: pair bookkeeping error");
+            }
         }
     }
     {   // structured Newton solve: structural pattern of [[Df11, -Dh1^T], [Dh2, 0]] (newton_matrix in mvi_core.hpp writes exactly these
@@ -961,6 +1029,20 @@ inline HostProgram build_program(const tg_system_desc *d) {
                     P.bbd_pk_ok = 1; P.bbd_pk_nr = K.nr; P.bbd_pk_nc2 = K.nc2; P.bbd_pk_tb = K.tb; P.bbd_pk_tc2 = K.tc2; P.bbd_pk_xs = P.o_scal - P.o_Df; P.bbd_pk_size = K.size;      // (the solution vector: the dense solvers' scale vector, nf doubles, unused by these kernels)
                     P.bbd_pk_nones = K.ones[0] < 0 ? 0 : (int)K.ones.size();
                     H.bbd_map = K.map; H.bbd_ones = K.ones; H.wev_pairx = pairx.empty() ? std::vector<int>(1, 0) : pairx; H.wev_dhx = dhx.empty() ? std::vector<int>(1, 0) : dhx;
+                    if (P.fb_on) {      // the same records for the shorter pair list, and the places of every lane's closed-form entries
+                        H.fb_pairx.clear();
+                        for (int w : H.fb_pair) {
+                            const int a = w & 0xFFFF, b = w >> 16;
+                            H.fb_pairx.push_back((int)((unsigned)a | ((unsigned)b << 6) | ((unsigned)K.map[(size_t)a * (nf + 1) + b] << 12) | ((unsigned)K.map[(size_t)b * (nf + 1) + a] << 22)));
+                        }
+                        for (int b = 0; b < nd; b++) {
+                            const int m = (int)((unsigned)H.fb_abx[2 * b] >> 30);
+                            unsigned at[6] = {0, 0, 0, 0, 0, 0};
+                            for (int i = 0; i < m; i++) { at[2 * i] = (unsigned)K.map[(size_t)P.fb_cfg[i] * (nf + 1) + b]; at[2 * i + 1] = (unsigned)K.map[(size_t)b * (nf + 1) + P.fb_cfg[i]]; }
+                            H.fb_abx[2 * b] = (int)(at[0] | (at[1] << 10) | (at[2] << 20) | ((unsigned)m << 30));
+                            H.fb_abx[2 * b + 1] = (int)(at[3] | (at[4] << 10) | (at[5] << 20));
+                        }
+                    }
                 }
             }
         }
@@ -991,7 +1073,8 @@ inline void pool_append(std::vector<T> &pool, std::vector<size_t> &offs, const s
     X(it_joint) X(it_cfg) X(pair_a) X(pair_b) X(cfg_item_off) X(cfg_items) X(e_anchor) X(c_type) X(c_e1) X(c_e2) \
     X(c_cfg) X(c_comp) X(dh_c) X(dh_cfg) X(dh_joint) X(dh_side) X(cf_cfg) X(cf_in) X(dh_lookup) X(cu_off) X(it_slot) X(pair4) \
     X(tri4) X(cpair4) X(it_pack) X(dh_pack) X(cpath_off) X(cpath_items) X(dh_pos) X(tchunk) X(tri_off) X(wr_in) X(wr_kind) X(ncs_i) \
-    X(wp_a) X(wp_b) X(wt_a) X(wt_b) X(wt_split) X(wcp4) X(bbd_tab) X(cmp_rep) X(cmp_grp) X(cmp_goff) X(cmp_gbody) X(cmp_pair) X(dhr_pack) X(at_i) X(ae_i) X(sj_list) X(sj_full) X(wev_lane) X(bbd_map) X(bbd_ones) X(wev_pairx) X(wev_dhx)
+    X(wp_a) X(wp_b) X(wt_a) X(wt_b) X(wt_split) X(wcp4) X(bbd_tab) X(cmp_rep) X(cmp_grp) X(cmp_goff) X(cmp_gbody) X(cmp_pair) X(dhr_pack) X(at_i) X(ae_i) X(sj_list) X(sj_full) X(wev_lane) X(bbd_map) X(bbd_ones) X(wev_pairx) X(wev_dhx) \
+    X(fb_pair) X(fb_pairx) X(fb_abx) X(fb_lane)
 #define TG_DBL_TABLES(X) X(j_pre) X(jcoef) X(j_prm) X(at_d) X(ae_d) X(b_C) X(b_inertia) X(e_off) X(c_dist) X(c_tol) X(damp) X(cs_k) X(cs_kq0) X(cs_c0) X(s_k) X(s_x0) X(c_nloc) X(wr_const) X(s_c) X(wr_Rloc) X(ncs_mb) X(ncs_tab)
 
 inline void HostProgram::pack() {

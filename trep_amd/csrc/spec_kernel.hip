@@ -167,6 +167,9 @@ unsigned long long tg_spec_key(void) {
 }
 // wavefronts per trajectory in the derivative kernels of this library (helper waves, mvi_core.hpp)
 int tg_spec_waves(void) { return spec_waves<tg::MODE_DERIV2Z>(); }
+// joints of the floating base's translational prefix whose terms THIS library's rollout kernel takes in closed form (mvi_core.hpp,
+// tg_static_fb: the plan's prefix, 0 when the world-frame evaluation was compiled out)
+int tg_spec_fb_n(void) { return tg::tg_static_fb<SpecProg>::value ? SpecProg::fb_n : 0; }
 // bit m set: kernel mode m (tg::MODE_*) has a specialised instantiation in this library
 int tg_spec_modes(void) {
     int m = 1 << tg::MODE_ROLLOUT;
