@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The marionette of the reference's examples/puppet-basic.py through the drop-in API: build the system, make
 the starting guess consistent with the six string constraints, integrate with the single-trajectory
-MidpointVI (B = 1 shell over the batched HIP engine), then run 4096 perturbed copies as one device-resident rollout.
+MidpointVI (B = 1 shell over the batched HIP engine), then make 4096 differently perturbed poses consistent in one launch
+(BatchMidpointVI.satisfy_constraints) and run them as one device-resident rollout.
 
     python examples/puppet_basic.py
 """
@@ -34,11 +35,14 @@ print("single trajectory: %d steps in %.2f s, TorsoZ %.4f -> %.4f" %
 # the same system, 4096 perturbed poses, one kernel launch
 B, N = 4096, int(tf / dt)
 rng = np.random.default_rng(0)
-Q0 = np.repeat(q0[None], B, axis=0)
-for b in range(1, 8):                      # a few distinct consistent poses, tiled over the batch
-    system.q = q0 + rng.uniform(-0.03, 0.03, system.nQ) * (np.arange(system.nQ) >= 3)
-    Q0[b::8] = system.satisfy_constraints()
 batch = trep.BatchMidpointVI(system, B)
+guess = q0 + rng.uniform(-0.03, 0.03, (B, system.nQ)) * (np.arange(system.nQ) >= 3)      # B distinct poses off the strings ...
+guess[0] = q0
+t0 = time.perf_counter()
+proj = batch.satisfy_constraints(guess)    # ... each moved to the nearest pose on them, in one launch
+Q0 = proj.Q
+print("projection: %d poses in %.3f s (incl. transfers), failed: %d, Newton steps at most %d" %
+      (B, time.perf_counter() - t0, int((proj.status != 0).sum()), int(proj.iterations.max())))
 batch.initialize_from_configs(0.0, Q0, dt, Q0)
 t0 = time.perf_counter()
 X = batch.rollout(N, dt)                   # [B][N+1][nX]

@@ -412,6 +412,36 @@ int tg_batch_set_predictor(tg_batch *b, int32_t mode);
  * (System_L / System_total_energy, system.c:78-127).  q, dq [B][nq]; energy [B][2]. */
 int tg_batch_energy(tg_batch *b, const double *q_host, const double *dq_host, double *energy_host);
 
+/* ---- batched constraint projection ---------------------------------------------------------------------------------
+ * System.satisfy_constraints (reference trep/system.py:158-214) for every trajectory of the batch at once, in one launch:
+ * per trajectory, minimise 1/2 |q - q0|^2 over the FREE configs subject to h(q) = 0, the other configs held at their input
+ * values.  free [nq]: non-zero = free, the same set for the whole batch (NULL: every config; the reference's keep_kinematic
+ * is the dynamic configs, its constant_q_list everything outside the list).  Newton on the KKT conditions with the constraint
+ * curvature: from q = q0, mu = 0, with D = Dh(q)[:, F] and g = (q - q0)_F + D' mu, each step solves
+ *   [[I + sum_c mu_c h_c,qq (F x F), D'], [D, 0]] (dq_F, dmu) = -(g, h).
+ * A trajectory is converged when max |h| <= tolerance and max |g| <= tolerance at the current iterate, tested before stepping.
+ * status [B]: TG_OK converged; TG_NOT_CONVERGED max_iterations steps were taken, q is the last iterate; TG_SINGULAR the solver
+ * rejected the KKT matrix, q is the iterate before that solve.  With an empty free set or nc == 0 nothing is solved: TG_OK if the
+ * input passes the test (always for nc == 0), else TG_SINGULAR, q unchanged.  No damping or globalisation: a perturbation too
+ * large for plain Newton reports a status.  iterations [B]: steps taken.  q, dq [B][nq]; mu [B][nc] the multipliers.
+ * Velocity part (dq not NULL; dq_out then required): for converged trajectories dq_out = dq with dq_F -= D' nu,
+ * D D' nu = Dh(q) dq at the converged pose -- the nearest rates tangent to the constraints, Dh(q) dq_out = 0, the fixed rates
+ * kept; dq is returned unchanged for the others (and a rejected velocity solve also reports TG_SINGULAR).
+ * mu_out, iterations_out, status_out may be NULL.  Outputs may alias inputs.  Generic kernel of its own (mode 9 in
+ * tg_batch_info) whatever library or parameter table the batch has: constraints do not depend on inertia, gravity or damping.
+ * The integrator state of the batch (q1, q2, p, lambda1, status, iterations) is not touched.  TG_ERR_INVALID for tolerance <= 0,
+ * max_iterations < 0, a null q or q_out, or dq_out without dq; TG_ERR_UNSUPPORTED if the workgroup's LDS -- per team the rollout
+ * slice plus (n + 1) n + n + nq + nq / 2 doubles, n = nq + nc -- exceeds 160 KiB (tg_system_projection_lds: out = team size,
+ * doubles per team, bytes per workgroup, 0; the same refusal, computed without a device).
+ * The _device variant takes device pointers, launches on the batch's stream and does not synchronise. */
+int tg_system_projection_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_project_constraints(tg_batch *b, const double *q_host, const double *dq_host, const int32_t *free_host,
+                                 double tolerance, int32_t max_iterations, double *q_out, double *dq_out, double *mu_out,
+                                 int32_t *iterations_out, int32_t *status_out);
+int tg_batch_project_constraints_device(tg_batch *b, const double *q_dev, const double *dq_dev, const int32_t *free_dev,
+                                        double tolerance, int32_t max_iterations, double *q_out_dev, double *dq_out_dev,
+                                        double *mu_out_dev, int32_t *iterations_out_dev, int32_t *status_out_dev);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

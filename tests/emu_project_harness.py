@@ -1,0 +1,81 @@
+"""ctypes driver for the host emulation of the constraint-projection kernel (tests/emu_project/emu_project.cpp, compiled on demand
+with g++ from trep_amd/csrc/mvi_project.hpp, TEAM = 1).  project() answers what BatchMidpointVI.satisfy_constraints answers on the
+device.  Test infrastructure only."""
+import collections
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+import emu_harness
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(_HERE)
+_LIB = None
+
+Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        so = os.path.join(_HERE, "emu_project", "libtrepamd_emu_project.so")
+        csrc = os.path.join(_ROOT, "trep_amd", "csrc")
+        srcs = [os.path.join(_HERE, "emu_project", "emu_project.cpp")] + [os.path.join(csrc, f) for f in (
+            "mvi_project.hpp", "mvi_core.hpp", "lanes.hpp", "program.hpp", "bbd.hpp", "dual.hpp")]
+        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, srcs[0]], check=True)
+        L = ctypes.CDLL(so)
+        L.emu_create.restype = ctypes.c_void_p
+        L.emu_create.argtypes = [ctypes.c_void_p]
+        L.emu_destroy.argtypes = [ctypes.c_void_p]
+        L.emu_sizeof_run_args.restype = ctypes.c_int
+        L.emu_project_lds.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.emu_project.argtypes = [ctypes.c_void_p] * 8
+        _LIB = L
+    return _LIB
+
+
+def sizeof_run_args():
+    """sizeof(tg::RunArgs) in the kernels' own translation unit."""
+    return int(lib().emu_sizeof_run_args())
+
+
+class EmuProjection(object):
+    def __init__(self, desc):
+        self.L = lib()
+        self.h = self.L.emu_create(ctypes.addressof(desc.struct))
+        assert self.h
+        self.desc = desc
+        self.nq, self.nc = int(desc.n_configs), int(desc.n_constraints)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.emu_destroy(self.h)
+            self.h = None
+
+    def lds_doubles(self):
+        """(doubles of LDS per team of the projection kernel, of the rollout slice)."""
+        out = np.zeros(2, dtype=np.int32)
+        self.L.emu_project_lds(self.h, out.ctypes.data)
+        return int(out[0]), int(out[1])
+
+    def project(self, Q, dQ=None, free=None, tolerance=1e-10, max_iterations=50):
+        """free: boolean / int mask [nq] or None (every config)."""
+        Q = np.ascontiguousarray(Q, dtype=float)
+        B = Q.shape[0]
+        assert Q.shape == (B, self.nq)
+        dQ = None if dQ is None else np.ascontiguousarray(dQ, dtype=float)
+        mask = None if free is None else np.ascontiguousarray(np.asarray(free) != 0, dtype=np.int32)
+        q, mu = np.zeros((B, self.nq)), np.zeros((B, self.nc))
+        dq = None if dQ is None else np.zeros((B, self.nq))
+        iters, status = np.full(B, -1, dtype=np.int32), np.full(B, -1, dtype=np.int32)
+        a = emu_harness.RunArgs()
+        a.batch, a.mode, a.max_iterations, a.tolerance = B, 9, int(max_iterations), float(tolerance)
+        a.group_size = 1
+        a.iters = iters.ctypes.data_as(emu_harness._I)
+        a.status = status.ctypes.data_as(emu_harness._I)
+        p = lambda x: None if x is None or x.size == 0 else x.ctypes.data
+        self.L.emu_project(self.h, ctypes.addressof(a), p(mask), p(Q), p(dQ), p(q), p(dq), p(mu))
+        return Projection(q, dq, mu, iters, status)

@@ -143,6 +143,14 @@ _SIGNATURES = {
     "tg_comm_barrier": (ctypes.c_int, [_vp]),
 }
 
+# Batched constraint projection.  A table of its own: _SIGNATURES is the set of entry points whose first refusal was recorded before
+# the host layer was rewritten (tests/test_abi_refusals_cpu.py pins it); these are bound and exported exactly like the others.
+_PROJECTION_SIGNATURES = {
+    "tg_system_projection_lds": (ctypes.c_int, [_vp, _c_ip]),
+    "tg_batch_project_constraints": (ctypes.c_int, [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_project_constraints_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class LibraryError(RuntimeError):
     pass
@@ -162,7 +170,7 @@ def lib():
         # and it must be in the environment before the HIP runtime initialises, i.e. before the library that links it is loaded.
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _SIGNATURES.items():
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -171,7 +179,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(_SIGNATURES)
+    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES))
 
 
 def check(rc):

@@ -17,6 +17,7 @@
 
 #include "device_buffer.hpp"
 #include "mvi_core.hpp"
+#include "mvi_project.hpp"
 #include "spec_emit.inc"
 #include <dlfcn.h>
 
@@ -24,6 +25,8 @@ namespace tg_detail {
 int fail(int code, const std::string &msg);
 // the generic per-trajectory-parameter kernels (trepamd_par.hip: their own object, compiled beside this one)
 int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+// the constraint-projection kernel (trepamd_project.hip, likewise)
+int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ProjectArgs &J, int grid, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -119,6 +122,8 @@ struct tg_batch {
     tg::DeviceBuffer<double> energy;  // [batch][2] output of tg_batch_energy
     tg::DeviceBuffer<double> lag;     // outputs of tg_batch_lagrangian
     tg::DeviceBuffer<int> dyn_ints;   // its status / iteration words (the integrator's own stay untouched)
+    tg::DeviceBuffer<double> proj;    // staging of the host-facing constraint projection: q0, dq0 in, q, dq, mu out
+    tg::DeviceBuffer<int> proj_ints;  // its free mask [nq], iteration [batch] and status [batch] words
     tg::DeviceBuffer<int> seeds;      // [2][batch] direction variables of the forward-mode calls
     tg::DeviceBuffer<double> d1[12];
     bool have_d1 = false;
@@ -1025,6 +1030,77 @@ int tg_batch_dynamics(tg_batch *b, const double *q_host, const double *dq_host, 
     HIP_TRY(hipMemcpyAsync(ddq_host, s.ddq, B * nd * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (nc) HIP_TRY(hipMemcpyAsync(lambda_host, s.lam, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (status_host) HIP_TRY(hipMemcpyAsync(status_host, b->dyn_ints.get() + B, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return TG_SUCCESS;
+}
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the projection kernel for this system (out[0..2]; out[3] 0):
+ * the rollout slice plus the KKT image, q0, the solver's row scales and the free configs' places (mvi_project.hpp).
+ * TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a workgroup can have. */
+int tg_system_projection_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::ProjectArgs J{};
+    tg::project_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nc, J);
+    const long long bytes = (long long)(64 / sys->team) * J.lds_per_team * (long long)sizeof(double);
+    out[0] = sys->team; out[1] = J.lds_per_team; out[2] = (int32_t)std::min<long long>(bytes, 0x7fffffff); out[3] = 0;
+    if (bytes > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident projection kernel");
+    return TG_SUCCESS;
+}
+
+int tg_batch_project_constraints_device(tg_batch *b, const double *q_dev, const double *dq_dev, const int32_t *free_dev, double tolerance,
+                                        int32_t max_iterations, double *q_out_dev, double *dq_out_dev, double *mu_out_dev,
+                                        int32_t *iterations_out_dev, int32_t *status_out_dev) {
+    if (!b || !q_dev || !q_out_dev) return fail(TG_ERR_INVALID, "null argument");
+    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
+    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    if (dq_out_dev && !dq_dev) return fail(TG_ERR_INVALID, "dq_out without dq");
+    if (dq_dev && !dq_out_dev) return fail(TG_ERR_INVALID, "dq without dq_out");
+    int32_t geo[4];
+    if (int rc = tg_system_projection_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch;
+    HIP_TRY(b->proj_ints.ensure(b->P.nq + 2 * B));
+    // the state is an argument of this call: nothing of the integrator (q1, q2, p, lambda1, status) is read or written, and neither a
+    // loaded specialised library nor a parameter table has a say (constraints do not depend on inertia, gravity or damping)
+    tg::RunArgs A = base_args(b, tg::MODE_PROJECT);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.tolerance = tolerance; A.max_iterations = max_iterations;
+    A.iters = iterations_out_dev ? iterations_out_dev : b->proj_ints.get() + b->P.nq;
+    A.status = status_out_dev ? status_out_dev : b->proj_ints.get() + b->P.nq + B;
+    tg::ProjectArgs J{};
+    tg::project_layout(b->P.lds_per_team, b->P.nq, b->P.nc, J);
+    J.free_mask = free_dev; J.q0 = q_dev; J.dq0 = dq_dev; J.q = q_out_dev; J.dq = dq_out_dev; J.mu = mu_out_dev;
+    const int per_block = 64 / b->sys->team, grid = (b->batch + per_block - 1) / per_block;
+    b->launched[0][0].add(tg::MODE_PROJECT);
+    int rc = tg_detail::launch_project(b->sys->team, launch_springs(b), b->d_prog.get(), A, J, grid, (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    return rc;
+}
+
+int tg_batch_project_constraints(tg_batch *b, const double *q_host, const double *dq_host, const int32_t *free_host, double tolerance,
+                                 int32_t max_iterations, double *q_out, double *dq_out, double *mu_out, int32_t *iterations_out, int32_t *status_out) {
+    if (!b || !q_host || !q_out) return fail(TG_ERR_INVALID, "null argument");
+    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
+    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    if (dq_out && !dq_host) return fail(TG_ERR_INVALID, "dq_out without dq");
+    int32_t geo[4];
+    if (int rc = tg_system_projection_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc;
+    HIP_TRY(b->proj.ensure(B * (4 * nq + nc)));
+    HIP_TRY(b->proj_ints.ensure(nq + 2 * B));
+    double *q0 = b->proj.get(), *dq0 = q0 + B * nq, *q = dq0 + B * nq, *dq = q + B * nq, *mu = dq + B * nq;
+    int *mask = b->proj_ints.get(), *iters = mask + nq, *status = iters + B;
+    HIP_TRY(hipMemcpyAsync(q0, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (dq_host) HIP_TRY(hipMemcpyAsync(dq0, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (free_host && nq) HIP_TRY(hipMemcpyAsync(mask, free_host, nq * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (int rc = tg_batch_project_constraints_device(b, q0, dq_host ? dq0 : nullptr, free_host ? mask : nullptr, tolerance, max_iterations,
+                                                     q, dq_host ? dq : nullptr, mu, iters, status)) return rc;
+    HIP_TRY(hipMemcpyAsync(q_out, q, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (dq_out) HIP_TRY(hipMemcpyAsync(dq_out, dq, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, iters, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;
 }

@@ -11,6 +11,7 @@ include/trep_amd.h.  State lives in device memory; the properties copy it
 in/out.  There is no CPU execution path: without the library or without a GPU
 every call raises.
 """
+import collections
 import os
 
 import numpy as np
@@ -18,6 +19,8 @@ import numpy as np
 from . import _lib
 from .descriptor import flatten
 from .errors import ConvergenceError
+
+Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")      # BatchMidpointVI.satisfy_constraints
 
 
 class BatchMidpointVI(object):
@@ -483,6 +486,38 @@ class BatchMidpointVI(object):
         _lib.check(self._L.tg_batch_dynamics(self._h, _lib.ptr(Q), _lib.ptr(dQ), _lib.ptr(U), _lib.ptr(K),
                                              _lib.ptr(ddq), _lib.ptr(lam), status.ctypes.data))
         return ddq, lam, status
+
+    def free_mask(self, keep_kinematic=False, constant_q_list=None):
+        """int32 [nq], 1 = free: the configs System.satisfy_constraints would move (reference trep/system.py:176-186) -- everything
+        outside constant_q_list (names or Config objects) if one is given, else the dynamic configs with keep_kinematic, else all."""
+        configs = self._system.configs
+        if constant_q_list:
+            fixed = set(self._system.get_config(c).name for c in constant_q_list)
+            return np.array([0 if c.name in fixed else 1 for c in configs], dtype=np.int32)
+        if keep_kinematic:
+            return np.array([0 if c.kinematic else 1 for c in configs], dtype=np.int32)
+        return np.ones(len(configs), dtype=np.int32)
+
+    def satisfy_constraints(self, Q, dQ=None, tolerance=1e-10, keep_kinematic=False, constant_q_list=None, max_iterations=50):
+        """System.satisfy_constraints (reference trep/system.py:158-214) for B poses in one launch: every Q[b] moves to the nearest
+        pose (least squares over the free configs; the others keep their values) with h(q) = 0, by Newton on the KKT conditions
+        (include/trep_amd.h, tg_batch_project_constraints).  Q [B][nq]; dQ [B][nq], optional: rates made tangent to the constraints
+        at the new pose, the fixed configs' rates kept.  Returns the namedtuple (Q, dQ, mu, iterations, status): [B][nq], [B][nq] or
+        None, [B][nc] multipliers, [B] Newton steps, [B] TG_OK / TG_NOT_CONVERGED (q = the last iterate) / TG_SINGULAR (q = the
+        iterate before the rejected solve).  Nothing is raised for a trajectory that fails: look at status.  The system's own
+        configuration and the integrator state of the batch are left alone."""
+        self.refresh()
+        B = self._batch
+        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
+        dQ = None if dQ is None else _lib.as_f64(np.broadcast_to(np.asarray(dQ, dtype=float), (B, self.nq)), (B, self.nq))
+        free = None if not (keep_kinematic or constant_q_list) else self.free_mask(keep_kinematic, constant_q_list)
+        q, mu = np.zeros((B, self.nq)), np.zeros((B, self.nc))
+        dq = None if dQ is None else np.zeros((B, self.nq))
+        iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        _lib.check(self._L.tg_batch_project_constraints(self._h, _lib.ptr(Q), _lib.ptr(dQ), None if free is None else free.ctypes.data,
+                                                        float(tolerance), int(max_iterations), _lib.ptr(q), _lib.ptr(dq), _lib.ptr(mu),
+                                                        iters.ctypes.data, status.ctypes.data))
+        return Projection(q, dq, mu, iters, status)
 
     def _seeds(self, seeds, most):
         """(seed1,) or (seed1, seed2) -> contiguous int32 [B] arrays: the input variable each trajectory's direction follows, numbered
