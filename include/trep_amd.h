@@ -310,7 +310,9 @@ int tg_batch_debug_newton_solve(tg_batch *b, int32_t n_mats, int32_t skip_struct
  * went through a specialised / generic kernel since the batch was created; out[3] / out[4] = number of such launches;
  * out[5] pivot rule; out[6] team size; out[7] bits 0-7 wavefronts per trajectory in the loaded library's derivative kernels (1, or 2
  * with helper waves), bits 8-15 fb_n: the joints of the floating base's translational prefix whose terms the loaded rollout kernel
- * takes in closed form, as that library reports it (0: none, compiled out, or no specialised library).  (Modes: 0 rollout/step, 1 calc_p2, 2 calc_f, 3 deriv1, 4 deriv2z, 5.. dynamics.) */
+ * takes in closed form, as that library reports it (0: none, compiled out, or no specialised library), bits 16-23
+ * tr_n: the joints of translation runs whose world poses the loaded rollout kernel stores directly instead of sweeping them, as that
+ * library reports it (0 likewise).  (Modes: 0 rollout/step, 1 calc_p2, 2 calc_f, 3 deriv1, 4 deriv2z, 5.. dynamics.) */
 int64_t tg_system_spec_header(const tg_system *sys, char *buf, uint64_t capacity);
 uint64_t tg_system_spec_key(const tg_system *sys);
 int tg_batch_load_specialized(tg_batch *b, const char *library_path);

@@ -146,6 +146,10 @@ template <class P> struct tg_static_pk<P, typename std::enable_if<(P::bbd_pk_ok 
 template <class P, class = void> struct tg_static_fb { static constexpr bool value = false; };
 template <class P> struct tg_static_fb<P, typename std::enable_if<(P::fb_on >= 0)>::type> { static constexpr bool value = P::fb_on != 0 && tg_static_wev<P>::value; };
 
+// ... and the translation runs of the rollout's dual pose sweep (program.hpp, tr_*)
+template <class P, class = void> struct tg_static_tr { static constexpr bool value = false; };
+template <class P> struct tg_static_tr<P, typename std::enable_if<(P::tr_on >= 0)>::type> { static constexpr bool value = P::tr_on != 0 && tg_static_sweep<P>::value && P::tab_ok != 0; };
+
 enum { MODE_ROLLOUT = 0, MODE_CALC_P2 = 1, MODE_CALC_F = 2, MODE_DERIV1 = 3, MODE_DERIV2Z = 4, MODE_DYNAMICS = 5, MODE_DYN_DERIV1 = 6, MODE_ENERGY = 7, MODE_LAGRANGIAN = 8 };
 
 struct RunArgs {
@@ -470,7 +474,7 @@ struct Core {
                     const int q = swact ? l / 12 : 4, rc = swact ? l - 12 * q : 0;
                     swr = rc >> 2; swcol = rc & 3;
 #pragma unroll
-                    for (int i = 0; i < 16; i++) swc[i] = (i & 3) < SP::sw_np[i >> 2] ? sw_code<SP>(i * 5, q) : 15;
+                    for (int i = 0; i < 16; i++) swc[i] = (i & 3) < SwPlan<SP>::np(i >> 2) ? sw_code<SP>(i * 5, q) : 15;
                 }
             }
 #pragma unroll
@@ -529,6 +533,12 @@ struct Core {
             }
             sched[2 * idx] = w0; sched[2 * idx + 1] = w1;
         }
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (tg_static_tr<typename std::remove_cv<PROG>::type>::value) {
+            // the chain schedule of the rollout's second sweep plan (program.hpp, tr_sched): the chains without their translation runs
+            if (rollout) { int *sched2 = (int *)(S + P.o_sched2); TG_FOR(i, 32 * P.n_rounds) sched2[i] = P.tr_sched[i]; }
+        }
+#endif
         TG_SYNC();
     }
 
@@ -642,8 +652,13 @@ struct Core {
         // quad-lane chain rounds (chain_round_quads): the lane's instance of every pass of the first round, requested a phase ahead
         SwDesc sw0;
         if constexpr (tg_static_sweep<typename std::remove_cv<PROG>::type>::value) {
-            if (rollout_lists) sw0 = sw_fetch<typename std::remove_cv<PROG>::type, 0>((const int *)(S + P.o_sched));
+            if (rollout_lists) sw0 = sw_fetch<typename std::remove_cv<PROG>::type, 0>((const int *)(S + SwPlan<typename std::remove_cv<PROG>::type>::o_sched()));
         }
+        // translation runs (program.hpp, tr_*): in the rollout's lists the lane of a run joint stores the joint's WORLD pose -- the rotation
+        // its local transform already has (the identity), and on every row either the row's constant (tr_prm, through the same fma: its
+        // factor is an exact 0, or an exact 1 on the row of the joint's own config) or a copy of the config another joint of the run
+        // puts there (tr_sj: config << 8 r, bit 24 + r) -- and the chain rounds follow the plan without those joints
+        constexpr bool TR = tg_static_tr<typename std::remove_cv<PROG>::type>::value;
         if (P.tab_ok) {
             // One lane per (pose set, joint): sin / cos of the joint coordinate AND the joint's local transform pre_j lg(q) in the same
             // phase.  With the pre-transform's columns in the order (axis a, b = a + 1, c = a + 2, translation) -- rows (A, B, C, D) of
@@ -654,11 +669,13 @@ struct Core {
             // twelve evaluations A + B cos + C sin and a trip through LDS for the sin / cos values entry by entry (13 wavefront trips for
             // the puppet's 2 x 34 joints, the rows from global memory batch after batch).  Same numbers.
             double pr[2][12];
+            int trw[2] = {0, 0};
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                const double *src = P.j_prm + 12 * (size_t)((jck[u] >> 16) & 0xFFF);
+                const double *src = (TR && rollout_lists ? P.tr_prm : P.j_prm) + 12 * (size_t)((jck[u] >> 16) & 0xFFF);
 #pragma unroll
                 for (int e = 0; e < 12; e++) pr[u][e] = src[e];
+                if constexpr (TR) { if (rollout_lists) trw[u] = P.tr_sj[lane + u * TEAM < sjn ? lane + u * TEAM : 0]; }
             }
             if (on) {
 #pragma unroll
@@ -671,6 +688,13 @@ struct Core {
                         const bool rotary = kind >= TG_RX;
                         const int a = rotary ? kind - TG_RX : kind - TG_TX, b = a == 2 ? 0 : a + 1, c = a == 0 ? 2 : a - 1;
                         double *g = (second ? G2 : G) + 12 * j;
+                        // translation column of row l: v, or for a run joint's copied row the config itself (one instruction stream: selects)
+                        auto row_t = [&](int l, double v) {
+                            if constexpr (TR) {
+                                if (rollout_lists) { const double e = qval(second ? dsB : dsA, (trw[u] >> (8 * l)) & 0xFF); return (trw[u] >> (24 + l)) & 1 ? e : v; }
+                            }
+                            return v;
+                        };
                         if (u * TEAM < sc_rot2) {          // (wave-uniform) a trip with rotary joints in it
                             double sn = 0.0, cs = 1.0;
                             if (rotary) tg_sincos(x, &sn, &cs);
@@ -681,14 +705,14 @@ struct Core {
                                 g[4 * l + a] = A_;
                                 g[4 * l + b] = rotary ? fma(C_, sn, B_ * cs) : B_;
                                 g[4 * l + c] = rotary ? fma(-B_, sn, C_ * cs) : C_;
-                                g[4 * l + 3] = fma(A_, tq, D_);
+                                g[4 * l + 3] = row_t(l, fma(A_, tq, D_));
                             }
                         } else {
 #pragma unroll
                             for (int l = 0; l < 3; l++) {
                                 const double A_ = pr[u][4 * l], B_ = pr[u][4 * l + 1], C_ = pr[u][4 * l + 2], D_ = pr[u][4 * l + 3];
                                 g[4 * l + a] = A_; g[4 * l + b] = B_; g[4 * l + c] = C_;
-                                g[4 * l + 3] = fma(A_, x, D_);
+                                g[4 * l + 3] = row_t(l, fma(A_, x, D_));
                             }
                         }
                     }
@@ -746,7 +770,7 @@ struct Core {
             if (rollout_lists) {     // (the instance plan lists the chains the ROLLOUT reads; the derivative kernels sweep every chain below)
                 typedef typename std::remove_cv<PROG>::type SP;
                 __builtin_amdgcn_s_setprio(TG_CHAIN_PRIO);
-                chain_round_quads<SP, 0>(on, sched, sw0);
+                chain_round_quads<SP, 0>(on, (const int *)(S + SwPlan<SP>::o_sched()), sw0);
                 __builtin_amdgcn_s_setprio(0);
                 return;
             }
@@ -844,8 +868,24 @@ struct Core {
     struct SwDesc { int w0[4], par[4]; };      // per pass: 12 * first joint | chain length << 16, 12 * parent joint (or -1) of the lane's instance
     // instance q (the lane's, 0 .. 4) of the pass whose five plan words start at `base`: chain slot | pose set << 8; a lane without an
     // instance gets slot 15, which the schedule leaves empty (length 0).  The plan words are compile-time constants: four selects.
+    // the plan the quad-lane rounds follow: the rollout's second one (program.hpp, tr_*: the chains without their translation runs, their
+    // schedule at o_sched2) where the kernel has it, sw_* otherwise -- the rounds only ever run on the rollout's lists
+    template <class SP, bool TR = tg_static_tr<SP>::value> struct SwPlan {
+        TG_HD static constexpr int np(int r) { return SP::sw_np[r]; }
+        TG_HD static constexpr int len(int i) { return SP::sw_len[i]; }
+        TG_HD static constexpr int inst(int i) { return SP::sw_inst[i]; }
+        TG_HD static constexpr int maxlen() { return SP::sw_maxlen; }
+        TG_HD static constexpr int o_sched() { return SP::o_sched; }
+    };
+    template <class SP> struct SwPlan<SP, true> {
+        TG_HD static constexpr int np(int r) { return SP::tr_np[r]; }
+        TG_HD static constexpr int len(int i) { return SP::tr_len[i]; }
+        TG_HD static constexpr int inst(int i) { return SP::tr_inst[i]; }
+        TG_HD static constexpr int maxlen() { return SP::tr_maxlen; }
+        TG_HD static constexpr int o_sched() { return SP::o_sched2; }
+    };
     template <class SP> TG_HD static int sw_code(int base, int q) {
-        auto w = [&](int i) { const int c = SP::sw_inst[base + i]; return c ? (c & 0x1FF) : 15; };
+        auto w = [&](int i) { const int c = SwPlan<SP>::inst(base + i); return c ? (c & 0x1FF) : 15; };
         return q == 0 ? w(0) : q == 1 ? w(1) : q == 2 ? w(2) : q == 3 ? w(3) : w(4);
     }
     template <class SP, int RD> TG_HD SwDesc sw_fetch(const int *sched) const {
@@ -853,7 +893,7 @@ struct Core {
 #pragma unroll
         for (int ps = 0; ps < 4; ps++) {
             d.w0[ps] = 0; d.par[ps] = -1;
-            if (ps < SP::sw_np[RD < 4 ? RD : 0]) {
+            if (ps < SwPlan<SP>::np(RD < 4 ? RD : 0)) {
                 const int slot = swc[4 * (RD < 4 ? RD : 0) + ps] & 0xFF;
                 d.w0[ps] = sched[2 * (16 * RD + slot)]; d.par[ps] = sched[2 * (16 * RD + slot) + 1];
             }
@@ -864,7 +904,7 @@ struct Core {
     // round's are requested before this round's columns: no LDS round trip between "which chain" and "its transforms")
     template <class SP, int RD> TG_HD void chain_round_quads(bool on, const int *sched, const SwDesc &d) {
         if constexpr (RD < SP::n_rounds) {
-            constexpr int NP = SP::sw_np[RD], ML = SP::sw_maxlen;
+            constexpr int NP = SwPlan<SP>::np(RD), ML = SwPlan<SP>::maxlen() > 0 ? SwPlan<SP>::maxlen() : 1;
             SwDesc nxt = d;
             if constexpr (RD + 1 < SP::n_rounds) nxt = sw_fetch<SP, RD + 1>(sched);
             const int r = swr, c = swcol;
@@ -883,7 +923,7 @@ struct Core {
                         p[ps] = opar >= 0 ? pv : (r == c ? 1.0 : 0.0);
 #pragma unroll
                         for (int s = 0; s < ML; s++) {
-                            if (s < SP::sw_len[4 * RD + ps]) {
+                            if (s < SwPlan<SP>::len(4 * RD + ps)) {
                                 // (past the end of a shorter chain of the pass: whatever follows it in LDS -- never stored)
                                 const int o = base[ps] + 12 * s + c;
                                 m[ps][s][0] = S[o]; m[ps][s][1] = S[o + 4]; m[ps][s][2] = S[o + 8];
@@ -895,7 +935,7 @@ struct Core {
                 for (int s = 0; s < ML; s++) {
 #pragma unroll
                     for (int ps = 0; ps < 4; ps++) {
-                        if (ps < NP && s < SP::sw_len[4 * RD + ps]) {
+                        if (ps < NP && s < SwPlan<SP>::len(4 * RD + ps)) {
                             const double b0 = tg_quad_bcast<0>(p[ps]), b1 = tg_quad_bcast<1>(p[ps]), b2 = tg_quad_bcast<2>(p[ps]);
                             const double last = c == 3 ? p[ps] : 0.0;
                             const double v = fma(b2, m[ps][s][2], fma(b1, m[ps][s][1], fma(b0, m[ps][s][0], last)));

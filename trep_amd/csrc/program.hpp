@@ -200,6 +200,26 @@ struct DevProg {
     // three resident workgroups per CU instead of two (measured with timing mocks first: -28 % kernel time).  The tables are cleared late
     // (after the constant blocks) in this layout; the second-derivative kernel keeps the d_* / e_* layout.
     int a_ok, a_o_T12, a_o_AUG, a_aug_ld, a_o_T22, a_lds_per_team;
+    // translation runs: the tr_n prismatic joints (tr_joint, parents first; dynamic or kinematic config) that hang off the
+    // world or off another run joint with a pre-transform whose rotation is exactly the identity, and along whose path from the world
+    // every component of the position has at most ONE non-zero contributor (the constant pre-translations, the config of the joint on
+    // that axis).  Their world pose is exactly [1 | p] with p[r] a copy of that contributor: tr_src[3 i + r] its config, or -1 for the
+    // constant tr_const[3 i + r].  tr_on: the rollout's dual sweep uses it (sw_ok, and the world-frame kernels only) -- the
+    // local-transform pass stores the run joints' WORLD poses and the chain rounds follow a second plan without them, next to the first
+    // (which the derivative kernels and the other sweep forms keep reading):
+    //   tr_np / tr_len / tr_inst / tr_maxlen   sw_np / sw_len / sw_inst / sw_maxlen of the trimmed chains: a chain of run joints alone is
+    //                                          gone, a chain that begins with run joints starts behind them
+    //   tr_sched [32 n_rounds]                 the chain schedule of those rounds (words as init_sweep_schedule writes them for the full
+    //                                          chains: a trimmed chain's parent is its last run joint), staged in LDS at o_sched2
+    //   tr_prm [12 n_joints]                   j_prm with a run joint's translation column replaced by its world constants
+    //   tr_sj [n_sj]                           per item of sj_list: (config + 1) << 10 r of the OTHER joints' configs a run joint's
+    //                                          component r copies (0: none -- the constant, or the joint's own config times its axis)
+    int tr_n, tr_on, tr_maxlen, o_sched2;
+    int tr_np[4];
+    int tr_len[16];
+    int tr_inst[80];
+    const int *tr_joint, *tr_src, *tr_sj, *tr_sched;
+    const double *tr_const, *tr_prm;
 };
 
 struct HostProgram {
@@ -218,6 +238,8 @@ struct HostProgram {
     std::vector<double> damp, cs_k, cs_kq0, cs_c0, s_k, s_x0, s_c, c_nloc, wr_const, wr_Rloc, ncs_mb, ncs_tab;
     std::vector<int> ncs_i, bbd_tab, cmp_rep, cmp_grp, cmp_goff, cmp_gbody, cmp_pair, wev_lane, bbd_map, bbd_ones, wev_pairx, wev_dhx;
     std::vector<int> fb_pair, fb_pairx, fb_abx, fb_lane;
+    std::vector<int> tr_joint, tr_src, tr_sj, tr_sched;      // translation runs (DevProg::tr_*)
+    std::vector<double> tr_const, tr_prm;
     std::vector<unsigned char> newton_pattern;   // [nf * nf] structural non-zeros of the Newton matrix (symmetrised), host side only
     std::vector<int> wr_in, wr_kind;
     std::vector<int> cf_cfg, cf_in;
@@ -1052,6 +1074,81 @@ inline HostProgram build_program(const tg_system_desc *d) {
             P.lds_per_team = (P.lds_per_team + 1) & ~1;
         }
     }
+    {   // translation runs (DevProg::tr_*): the joints are a property of the tree alone, the second sweep plan is for the rollout kernels
+        P.tr_n = P.tr_on = P.tr_maxlen = P.o_sched2 = 0;
+        for (int i = 0; i < 4; i++) P.tr_np[i] = 0;
+        for (int i = 0; i < 16; i++) P.tr_len[i] = 0;
+        for (int i = 0; i < 80; i++) P.tr_inst[i] = 0;
+        std::vector<int> run_of(nj, -1);
+        for (int j = 0; j < nj; j++) {      // (parents come first in the joint order)
+            const int kind = H.j_kind[j], par = H.j_parent[j];
+            if (kind < TG_TX || kind > TG_TZ || (par >= 0 && run_of[par] < 0)) continue;
+            const double *pre = &H.j_pre[12 * (size_t)j];
+            bool ok = true;
+            for (int l = 0; l < 3; l++) for (int c = 0; c < 3; c++) if (pre[4 * l + c] != (l == c ? 1.0 : 0.0)) ok = false;
+            int src[3];
+            double cst[3];
+            for (int r = 0; r < 3; r++) {
+                src[r] = par >= 0 ? H.tr_src[3 * (size_t)run_of[par] + r] : -1;
+                cst[r] = par >= 0 ? H.tr_const[3 * (size_t)run_of[par] + r] : 0.0;
+                const double D = pre[4 * r + 3];
+                if (D != 0.0) { if (src[r] >= 0 || cst[r] != 0.0) ok = false; else cst[r] = D; }      // (the copy rule: a second contributor ends the run)
+            }
+            const int a = kind - TG_TX;
+            if (src[a] >= 0 || cst[a] != 0.0) ok = false;
+            if (!ok) continue;
+            src[a] = H.j_cfg[j]; cst[a] = 0.0;
+            run_of[j] = P.tr_n++;
+            H.tr_joint.push_back(j);
+            for (int r = 0; r < 3; r++) { H.tr_src.push_back(src[r]); H.tr_const.push_back(src[r] >= 0 ? 0.0 : cst[r]); }
+        }
+        H.tr_prm = H.j_prm;
+        for (int i = 0; i < P.tr_n; i++)
+            for (int l = 0; l < 3; l++) H.tr_prm[12 * (size_t)H.tr_joint[i] + 4 * l + 3] = H.tr_const[3 * (size_t)i + l];
+        H.tr_sj.assign(H.sj_list.size(), 0);
+        for (int n = 0; n < P.n_sj; n++) {
+            const int j = (H.sj_list[n] >> 16) & 0xFFF, i = run_of[j];
+            if (i < 0) continue;
+            for (int r = 0; r < 3; r++) {
+                const int c = H.tr_src[3 * (size_t)i + r];
+                if (c >= 0 && c != H.j_cfg[j]) H.tr_sj[n] |= ((c & 0xFF) << (8 * r)) | (1 << (24 + r));
+            }
+        }
+        // the second plan: every chain without its leading run joints, in its own round and slot
+        H.tr_sched.assign(32 * (size_t)std::max(P.n_rounds, 1), 0);
+        bool on = P.sw_ok && P.wev_ok && P.tr_n > 0 && nq <= 256;
+        for (int r = 0; r < P.n_rounds && on; r++) {
+            std::vector<int> inst;
+            for (int slot = 0; slot < 16; slot++) {
+                const int c = H.round_off[r] + slot;
+                int *w = &H.tr_sched[2 * (size_t)(16 * r + slot)];
+                w[0] = 0; w[1] = -1;
+                if (c >= H.round_off[r + 1]) continue;
+                int k = 0;
+                while (k < H.ch_len[c] && run_of[H.ch_first[c] + k] >= 0) k++;
+                const int first = H.ch_first[c] + k, len = H.ch_len[c] - k, parent = k ? first - 1 : H.ch_parent[c];
+                if (len == 0) continue;
+                w[0] = (12 * first) | (len << 16); w[1] = parent >= 0 ? 12 * parent : -1;
+                for (int set = 0; set < 2; set++) if (pose_need[first] >> set & 1) inst.push_back(slot | (set << 8) | (1 << 9));
+            }
+            P.tr_np[r] = ((int)inst.size() + 4) / 5;
+            for (int p = 0; p < P.tr_np[r]; p++) {
+                int len = 0;
+                for (int q = 0; q < 5 && 5 * p + q < (int)inst.size(); q++) {
+                    P.tr_inst[(4 * r + p) * 5 + q] = inst[5 * p + q];
+                    len = std::max(len, H.tr_sched[2 * (size_t)(16 * r + (inst[5 * p + q] & 0xFF))] >> 16);
+                }
+                P.tr_len[4 * r + p] = len;
+                P.tr_maxlen = std::max(P.tr_maxlen, len);
+            }
+        }
+        if (on) {
+            P.tr_on = 1;
+            P.o_sched2 = P.lds_per_team;      // behind the base region, like the solve's plan tables (rollout kernels only)
+            P.lds_per_team += 16 * P.n_rounds;
+        }
+        if (H.tr_joint.empty()) { H.tr_joint.push_back(0); H.tr_src.assign(3, -1); H.tr_const.assign(3, 0.0); }
+    }
     H.pack();
     return H;
 }
@@ -1074,8 +1171,8 @@ inline void pool_append(std::vector<T> &pool, std::vector<size_t> &offs, const s
     X(c_cfg) X(c_comp) X(dh_c) X(dh_cfg) X(dh_joint) X(dh_side) X(cf_cfg) X(cf_in) X(dh_lookup) X(cu_off) X(it_slot) X(pair4) \
     X(tri4) X(cpair4) X(it_pack) X(dh_pack) X(cpath_off) X(cpath_items) X(dh_pos) X(tchunk) X(tri_off) X(wr_in) X(wr_kind) X(ncs_i) \
     X(wp_a) X(wp_b) X(wt_a) X(wt_b) X(wt_split) X(wcp4) X(bbd_tab) X(cmp_rep) X(cmp_grp) X(cmp_goff) X(cmp_gbody) X(cmp_pair) X(dhr_pack) X(at_i) X(ae_i) X(sj_list) X(sj_full) X(wev_lane) X(bbd_map) X(bbd_ones) X(wev_pairx) X(wev_dhx) \
-    X(fb_pair) X(fb_pairx) X(fb_abx) X(fb_lane)
-#define TG_DBL_TABLES(X) X(j_pre) X(jcoef) X(j_prm) X(at_d) X(ae_d) X(b_C) X(b_inertia) X(e_off) X(c_dist) X(c_tol) X(damp) X(cs_k) X(cs_kq0) X(cs_c0) X(s_k) X(s_x0) X(c_nloc) X(wr_const) X(s_c) X(wr_Rloc) X(ncs_mb) X(ncs_tab)
+    X(fb_pair) X(fb_pairx) X(fb_abx) X(fb_lane) X(tr_joint) X(tr_src) X(tr_sj) X(tr_sched)
+#define TG_DBL_TABLES(X) X(j_pre) X(jcoef) X(j_prm) X(at_d) X(ae_d) X(b_C) X(b_inertia) X(e_off) X(c_dist) X(c_tol) X(damp) X(cs_k) X(cs_kq0) X(cs_c0) X(s_k) X(s_x0) X(c_nloc) X(wr_const) X(s_c) X(wr_Rloc) X(ncs_mb) X(ncs_tab) X(tr_const) X(tr_prm)
 
 inline void HostProgram::pack() {
     ipool.clear(); dpool.clear(); ioff.clear(); doff.clear();

@@ -170,6 +170,9 @@ int tg_spec_waves(void) { return spec_waves<tg::MODE_DERIV2Z>(); }
 // joints of the floating base's translational prefix whose terms THIS library's rollout kernel takes in closed form (mvi_core.hpp,
 // tg_static_fb: the plan's prefix, 0 when the world-frame evaluation was compiled out)
 int tg_spec_fb_n(void) { return tg::tg_static_fb<SpecProg>::value ? SpecProg::fb_n : 0; }
+// joints of translation runs whose world poses THIS library's rollout kernel stores directly instead of sweeping them (mvi_core.hpp,
+// tg_static_tr: the plan's run joints, 0 when the kernel follows the first sweep plan)
+int tg_spec_tr_n(void) { return tg::tg_static_tr<SpecProg>::value ? SpecProg::tr_n : 0; }
 // bit m set: kernel mode m (tg::MODE_*) has a specialised instantiation in this library
 int tg_spec_modes(void) {
     int m = 1 << tg::MODE_ROLLOUT;

@@ -187,6 +187,8 @@ class BatchMidpointVI(object):
         kout = np.zeros(8, dtype=np.int32)
         _lib.check(self._L.tg_batch_info(self._h, kout.ctypes.data_as(_lib._c_ip)))
         d["fb_n"] = (int(kout[7]) >> 8) & 0xFF
+        # joints of translation runs whose world poses the loaded rollout kernel stores directly (likewise)
+        d["tr_n"] = (int(kout[7]) >> 16) & 0xFF
         return d
 
     MODES = {"rollout": 0, "calc_p2": 1, "calc_f": 2, "deriv1": 3, "deriv2z": 4}
@@ -236,7 +238,7 @@ class BatchMidpointVI(object):
         """Which kernels this batch has launched (tg_batch_info): `spec_modes` = set of mode names with a specialised kernel
         loaded, `spec_launched` / `generic_launched` = mode names that have actually gone through a specialised / generic
         kernel, and the launch counts; `helper_waves` = wavefronts per trajectory in the loaded library's derivative kernels; `fb_n` = joints of the
-        translational prefix the loaded rollout kernel has closed forms for;
+        translational prefix the loaded rollout kernel has closed forms for; `tr_n` = joints of translation runs whose world poses it stores directly;
         `spec_library` the loaded file.  The par_* keys: the same for the per-trajectory parameter kernels (set_parameters),
         over all kernel modes (ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
         out = np.zeros(8, dtype=np.int32)
@@ -248,7 +250,7 @@ class BatchMidpointVI(object):
         return {"spec_modes": names(out[0]), "spec_launched": names(out[1]), "generic_launched": names(out[2]),
                 "spec_launch_mask": int(out[1]), "generic_launch_mask": int(out[2]),
                 "spec_launches": int(out[3]), "generic_launches": int(out[4]), "exact_pivot": bool(out[5]), "team": int(out[6]),
-                "helper_waves": int(out[7]) & 0xFF, "fb_n": (int(out[7]) >> 8) & 0xFF, "spec_library": self._specialized,
+                "helper_waves": int(out[7]) & 0xFF, "fb_n": (int(out[7]) >> 8) & 0xFF, "tr_n": (int(out[7]) >> 16) & 0xFF, "spec_library": self._specialized,
                 # per-trajectory parameter kernels (set_parameters); the keys above count the default kernels only
                 "par_spec_modes": every(par[0]), "par_spec_launched": every(par[1]), "par_generic_launched": every(par[2]),
                 "par_spec_launches": int(par[3]), "par_generic_launches": int(par[4]), "parameter_rows": int(par[5]),
