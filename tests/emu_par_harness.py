@@ -19,7 +19,7 @@ def lib():
     if _LIB is None:
         so = os.path.join(_HERE, "emu_par", "libtrepamd_emu_par.so")
         csrc = os.path.join(_ROOT, "trep_amd", "csrc")
-        srcs = [os.path.join(_HERE, "emu_par", "emu_par.cpp")] + [os.path.join(csrc, f) for f in ("mvi_core.hpp", "lanes.hpp", "program.hpp", "bbd.hpp", "dual.hpp")]
+        srcs = [os.path.join(_HERE, "emu_par", "emu_par.cpp")] + [os.path.join(csrc, f) for f in ("mvi_core.hpp", "lanes.hpp", "program.hpp", "devprog_fields.def", "schedule.hpp", "bbd.hpp", "dual.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, srcs[0]], check=True)
         L = ctypes.CDLL(so)

@@ -23,7 +23,7 @@ def lib():
         so = os.path.join(_HERE, "emu_project", "libtrepamd_emu_project.so")
         csrc = os.path.join(_ROOT, "trep_amd", "csrc")
         srcs = [os.path.join(_HERE, "emu_project", "emu_project.cpp")] + [os.path.join(csrc, f) for f in (
-            "mvi_project.hpp", "mvi_core.hpp", "lanes.hpp", "program.hpp", "bbd.hpp", "dual.hpp")]
+            "mvi_project.hpp", "mvi_core.hpp", "lanes.hpp", "program.hpp", "devprog_fields.def", "schedule.hpp", "bbd.hpp", "dual.hpp")]
         if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, srcs[0]], check=True)
         L = ctypes.CDLL(so)

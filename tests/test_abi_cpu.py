@@ -70,23 +70,35 @@ def test_product_never_imports_oracle():
                     assert b not in text, (f, b)
 
 
-def test_specialisation_emitter_is_in_sync_and_header_is_complete():
-    """csrc/spec_emit.inc is generated from struct DevProg (tools/gen_spec_emitter.py); the header it prints for a system
-    must define every field of the struct as a compile-time constant (host-only: no GPU involved)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    assert subprocess.run([sys.executable, os.path.join(root, "tools", "gen_spec_emitter.py"), "--check"]).returncode == 0, \
-        "trep_amd/csrc/spec_emit.inc is stale: run tools/gen_spec_emitter.py"
-    sys.path.insert(0, os.path.join(root, "tools"))
-    import gen_spec_emitter
+def test_specialisation_header_defines_exactly_the_declared_fields():
+    """csrc/devprog_fields.def is the one list of DevProg's members; the specialisation header printed for a system must define every
+    one of them as a compile-time constant -- every int, every element and the accessor of every array, every table pointer -- and
+    no member that the list does not name (host-only: no GPU involved)."""
     from trep_amd import specialize, systems
-    ints, dbl_arrays, pointers = gen_spec_emitter.parse_fields()
+    with open(os.path.join(ROOT, "trep_amd", "csrc", "devprog_fields.def")) as fh:
+        fields = re.sub(r"//[^\n]*", "", fh.read())
+    ints = re.findall(r"\bTG_F_INT\(\s*(\w+)\s*\)", fields)
+    arrays = re.findall(r"\bTG_F_ARRAY\(\s*(\w+)\s*,\s*(\w+)\s*,\s*(\d+)\s*\)", fields)
+    tables = re.findall(r"\bTG_F_TABLE\(\s*(\w+)\s*,\s*(\w+)\s*\)", fields)
+    assert len(ints) >= 163 and len(arrays) >= 11 and len(tables) >= 104
+    names = ints + [a[1] for a in arrays] + [t[1] for t in tables]
+    assert len(set(names)) == len(names), "a field is listed twice"
     text = specialize.header(systems.scissor_lift(4))
+    body = text[text.index("struct SpecProg {"):]
+    line = lambda pattern: re.search("^    " + pattern + "$", body, flags=re.M)
+    expected = set(names)
     for f in ints:
-        assert "static constexpr int %s = " % f in text, f
-    for ctype, name in pointers:
-        assert "static constexpr const %s *%s = " % (ctype, name) in text, name
+        assert line(r"static constexpr int %s = -?\d+;" % f), f
+    for ctype, name, n in arrays:
+        for i in range(int(n)):
+            assert line(r"static constexpr %s %s_%d = \S+;" % (ctype, name, i)), (name, i)
+            expected.add("%s_%d" % (name, i))
+        assert line(r"struct %s_t \{ __host__ __device__ constexpr %s operator\[\]\(int i\) const \{ return .*; \} \};" % (name, ctype)), name
+        assert line(r"static constexpr %s_t %s\{\};" % (name, name)), name
+    for ctype, name in tables:
+        assert line(r"static constexpr const %s \*%s = (spec_%spool \+ \d+|nullptr);" % (ctype, name, ctype[0])), name
+    defined = re.findall(r"^    static constexpr [^=;{]*?\*?(\w+)(?: = [^;]*|\{\});$", body, flags=re.M)
+    assert len(defined) == body.count("static constexpr") and sorted(defined) == sorted(expected), sorted(set(defined) ^ expected)
     assert "#define SPEC_TEAM 64" in text and "static constexpr int nc = 8;" in text
     # a different system gives a different header (and cache key)
     assert specialize.library_path(systems.pend_on_cart())[0] != specialize.library_path(systems.scissor_lift(4))[0]

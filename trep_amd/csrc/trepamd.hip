@@ -18,7 +18,7 @@
 #include "device_buffer.hpp"
 #include "mvi_core.hpp"
 #include "mvi_project.hpp"
-#include "spec_emit.inc"
+#include "schedule.hpp"
 #include <dlfcn.h>
 
 namespace tg_detail {
@@ -1236,7 +1236,7 @@ std::string spec_header_text(const tg_system *sys) {
     std::snprintf(line, sizeof(line), "#define SPEC_TEAM %d\n#define SPEC_SPRINGS %s\n", sys->team,
                   launch_springs(sys->H.p) ? "true" : "false");
     out += line;
-    emit_spec_header(sys->H, out);
+    tg::emit_spec_header(sys->H, out);
     return out;
 }
 uint64_t fnv1a64(const std::string &t) {
@@ -1247,7 +1247,7 @@ uint64_t fnv1a64(const std::string &t) {
 }  // namespace
 extern "C" {
 
-/* Text of the specialisation header of a system (spec_emit.inc); returns the length needed (incl. the terminator). */
+/* Text of the specialisation header of a system (schedule.hpp, emit_spec_header); returns the length needed (incl. the terminator). */
 int64_t tg_system_spec_header(const tg_system *sys, char *buf, uint64_t capacity) {
     if (!sys) { fail(TG_ERR_INVALID, "null system"); return -1; }
     const std::string out = spec_header_text(sys);
