@@ -444,6 +444,41 @@ int tg_batch_project_constraints_device(tg_batch *b, const double *q_dev, const 
                                         double tolerance, int32_t max_iterations, double *q_out_dev, double *dq_out_dev,
                                         double *mu_out_dev, int32_t *iterations_out_dev, int32_t *status_out_dev);
 
+/* ---- batched equilibrium search -----------------------------------------------------------------------------------
+ * System.minimize_potential_energy (reference trep/system.py:215-272) for every pose of the batch at once, in one launch: per
+ * pose, minimise V(q) over the FREE configs subject to h(q) = 0, the other configs held at their input values bit for bit.
+ * free [nq] as in tg_batch_project_constraints (NULL: every config).  A safeguarded Newton iteration on the KKT conditions
+ * (tests/equilibrium_reference.py is its specification).  At (q, mu): D = Dh(q)[:, F], g = V_q[F] + D' mu,
+ * W = V_qq[F, F] + sum_c mu_c h_c,qq[F, F].  From q = q0 with the least-squares multipliers of the start
+ * ([[I, D'], [D, 0]] (d, mu) = (-V_q[F], 0); zero where that matrix is rejected), tau = 0, rho = 0.  A pose is converged when
+ * max |h| <= tolerance and max |g| <= tolerance (a NaN fails the test).  Otherwise a trial, each of which counts toward
+ * max_iterations and is rejected if it fails any of: (1) W + tau I + sigma D'D has an unpivoted Cholesky factor, with
+ * sigma = 1e8 wmax / max diag(D'D), wmax = max |diag W|; (2) [[W + tau I, D'], [D, 0]] (d, dmu) = -(g, h) is solved and the
+ * step is finite; (3) at the trial point (q_F + d, mu + dmu), with rho+ = max(rho, 2 |mu + dmu|inf) and phi = V + rho+ |h|_1 on
+ * both sides, phi_trial <= phi + 64 eps max(1, |phi|) -- or, while tau <= 1e-3 wmax, the KKT residual max(|h|inf, |g|inf) of the
+ * trial point is at most half the current one.  Accepted: tau /= 4, and 0 once under 1e-6 wmax.  Rejected:
+ * tau = max(4 tau, 1e-3 wmax); tau > 1e9 wmax ends the search.
+ * status [B]: TG_OK converged (a minimum: (1) held at every accepted step); TG_NOT_CONVERGED max_iterations trials were made, q is
+ * the last accepted iterate; TG_SINGULAR tau ran out, or nothing is free and the input does not pass the test.  A system without
+ * constraints is a normal case.  iterations [B]: trials made.  q [B][nq]; mu [B][nc]; v_out [B][2]: V at the start and at the
+ * returned pose.  mu_out, v_out, iterations_out, status_out may be NULL.  q_out may alias q.
+ * Generic kernel of its own (mode 10 in tg_batch_info) whatever library the batch has; with a parameter table
+ * (tg_batch_set_parameters) its parameter twin runs (mode 10 in tg_batch_par_info) and every pose uses its row's masses, inertias
+ * and gravity -- damping plays no part.  The integrator state of the batch (q1, q2, p, lambda1, status, iterations) is not touched.
+ * TG_ERR_INVALID for tolerance <= 0, max_iterations < 0, a null q or q_out; TG_ERR_UNSUPPORTED for a system with a
+ * NonlinearConfigSpring (its V() is 0 in the reference while its force is not: there is no potential to minimise), for the
+ * profiling build, and if the workgroup's LDS -- per team the rollout slice plus (n + 1) n + 2 nq^2 + 2 n + 3 nq + 2 + nq / 2
+ * doubles, n = nq + nc -- exceeds 160 KiB (tg_system_equilibrium_lds: out = team size, doubles per team, bytes per workgroup, 0;
+ * the same refusals, computed without a device).
+ * The _device variant takes device pointers, launches on the batch's stream and does not synchronise. */
+int tg_system_equilibrium_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_minimize_potential(tg_batch *b, const double *q_host, const int32_t *free_host, double tolerance,
+                                int32_t max_iterations, double *q_out, double *mu_out, double *v_out, int32_t *iterations_out,
+                                int32_t *status_out);
+int tg_batch_minimize_potential_device(tg_batch *b, const double *q_dev, const int32_t *free_dev, double tolerance,
+                                       int32_t max_iterations, double *q_out_dev, double *mu_out_dev, double *v_out_dev,
+                                       int32_t *iterations_out_dev, int32_t *status_out_dev);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

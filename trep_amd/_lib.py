@@ -151,6 +151,13 @@ _PROJECTION_SIGNATURES = {
     "tg_batch_project_constraints_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# Batched equilibrium search: bound and exported like the others, from a table of its own for the same reason.
+_EQUILIBRIUM_SIGNATURES = {
+    "tg_system_equilibrium_lds": (ctypes.c_int, [_vp, _c_ip]),
+    "tg_batch_minimize_potential": (ctypes.c_int, [_vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_minimize_potential_device": (ctypes.c_int, [_vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class LibraryError(RuntimeError):
     pass
@@ -170,7 +177,7 @@ def lib():
         # and it must be in the environment before the HIP runtime initialises, i.e. before the library that links it is loaded.
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()):
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -179,7 +186,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES))
+    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES))
 
 
 def check(rc):

@@ -4038,6 +4038,69 @@ struct Core {
         }
     }
 
+    // The potential and its first two derivatives at the pose in q2, at rest, summed into LDS (MODE_EQUILIBRIUM): V[0] = the V half of
+    // energy(); Vq [nq] and Vqq = -L_dq and -L_dqdq of lagrangian() at dq = 0, where the velocity terms (v, W) vanish and only the
+    // gam, cs_eval, o_sV and o_sH terms are left.  Vqq is kept over the free configs alone: entry (idx[ka], idx[kb]) of an [ld][ld]
+    // image, a config with idx < 0 left out.  With constraints their h and sparse Dh (into Dh) come from the same sweep.
+    TG_HD void potential_lds(bool on, Real *Dh, Real *V, Real *Vq, Real *Vqq, int ld, const int *idx) {
+        const int nq = P.nq;
+        if (on) {
+            TG_FOR(i, nq) { S[P.o_dq + i] = 0.0; Vq[i] = 0.0; }
+            TG_FOR(i, ld * ld) Vqq[i] = 0.0;
+            if (lane == 0) V[0] = 0.0;
+        }
+        TG_SYNC();
+        pose_sweep(on, 2);
+        attach_points(on, true, P.nc > 0 || n_springs() > 0);
+        if (P.nc > 0) constraints(on, 2, true, Dh, 0);
+        spring_terms(on);
+        jacobians(on);
+        if (on) {
+            TG_FOR(b, P.n_bodies) {
+                const Real *I = S + P.o_I + 4 * b, *gb = S + P.o_gB + 12 * b;
+                lds_add(&V[0], -I[0] * (grav_of(P, 0) * gb[3] + grav_of(P, 1) * gb[7] + grav_of(P, 2) * gb[11]));
+            }
+            TG_FOR(sp, n_springs()) {
+                const int c = P.nc + sp;
+                const Real *a = S + P.o_pE + 3 * P.c_e1[c], *b = S + P.o_pE + 3 * P.c_e2[c];
+                const Real x = sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]));
+                lds_add(&V[0], 0.5 * P.s_k[sp] * (x - P.s_x0[sp]) * (x - P.s_x0[sp]));
+            }
+            TG_FOR(it, P.n_items) {
+                const int b = P.it_pack[4 * (size_t)it], cfg = P.it_pack[4 * (size_t)it + 3] & 0xFFFF;
+                const Real *I = S + P.o_I + 4 * b, *gam = S + P.o_gam + 3 * b, *J = S + P.o_J + 6 * it;
+                lds_add(&Vq[cfg], -(I[0] * (gam[0] * J[0] + gam[1] * J[1] + gam[2] * J[2])));
+            }
+            TG_FOR(pp, P.n_pairs) {
+                const int ia = P.pair_a[pp], ib = P.pair_b[pp];
+                const int b = P.it_pack[4 * (size_t)ia], ca = idx[P.it_pack[4 * (size_t)ia + 3] & 0xFFFF], cb = idx[P.it_pack[4 * (size_t)ib + 3] & 0xFFFF];
+                if (ca < 0 || cb < 0) continue;
+                const Real *I = S + P.o_I + 4 * b, *gam = S + P.o_gam + 3 * b, *Ja = S + P.o_J + 6 * ia, *Jb = S + P.o_J + 6 * ib;
+                const Real vqq = -(I[0] * (gam[0] * (Ja[4] * Jb[2] - Ja[5] * Jb[1]) + gam[1] * (Ja[5] * Jb[0] - Ja[3] * Jb[2]) +
+                                           gam[2] * (Ja[3] * Jb[1] - Ja[4] * Jb[0])));
+                lds_add(&Vqq[ca * ld + cb], vqq);
+                if (ia != ib) lds_add(&Vqq[cb * ld + ca], vqq);
+            }
+            if (has_cs()) TG_FOR(i, nq) {
+                const Real q = S[P.o_q2 + i];
+                Real d1_, d2_, d3_;
+                cs_eval(i, q, d1_, d2_, d3_);
+                lds_add(&V[0], 0.5 * P.cs_k[i] * q * q - P.cs_kq0[i] * q + P.cs_c0[i]);
+                lds_add(&Vq[i], d1_);
+                if (idx[i] >= 0) lds_add(&Vqq[idx[i] * ld + idx[i]], d2_);
+            }
+            if (n_springs()) TG_FOR(i, nq) lds_add(&Vq[i], S[P.o_sV + i]);
+            TG_FOR(pp, n_spair()) {
+                const int *pw = P.cpair4 + 4 * (size_t)(P.n_cpair + pp);
+                const int ka = idx[pw[3] & 0xFFFF], kb = idx[pw[3] >> 16];
+                if (ka < 0 || kb < 0) continue;
+                lds_add(&Vqq[ka * ld + kb], S[P.o_sH + pp]);
+                if (pw[1] != pw[2]) lds_add(&Vqq[kb * ld + ka], S[P.o_sH + pp]);
+            }
+        }
+        TG_SYNC();
+    }
+
     // =====================================================================================================
     // First derivatives of the continuous dynamics (reference calc_dynamics_deriv1, system.c:912-1299): d(ddq_d, lambda)
     // / d(q, dq, ddq_k, u).  With r = D - M ddq_d + Ad^T lambda = 0 and g = A ddq + dq^T H dq = 0 solved by `dynamics`,

@@ -18,6 +18,7 @@
 #include "device_buffer.hpp"
 #include "mvi_core.hpp"
 #include "mvi_project.hpp"
+#include "mvi_equilibrium.hpp"
 #include "schedule.hpp"
 #include <dlfcn.h>
 
@@ -27,6 +28,8 @@ int fail(int code, const std::string &msg);
 int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the constraint-projection kernel (trepamd_project.hip, likewise)
 int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ProjectArgs &J, int grid, size_t lds, hipStream_t stream);
+// the equilibrium-search kernel and its parameter-table twin (trepamd_equilibrium.hip, likewise)
+int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -124,6 +127,8 @@ struct tg_batch {
     tg::DeviceBuffer<int> dyn_ints;   // its status / iteration words (the integrator's own stay untouched)
     tg::DeviceBuffer<double> proj;    // staging of the host-facing constraint projection: q0, dq0 in, q, dq, mu out
     tg::DeviceBuffer<int> proj_ints;  // its free mask [nq], iteration [batch] and status [batch] words
+    tg::DeviceBuffer<double> equi;    // staging of the host-facing equilibrium search: q0 in, q, mu, V out
+    tg::DeviceBuffer<int> equi_ints;  // its free mask [nq], iteration [batch] and status [batch] words
     tg::DeviceBuffer<int> seeds;      // [2][batch] direction variables of the forward-mode calls
     tg::DeviceBuffer<double> d1[12];
     bool have_d1 = false;
@@ -1099,6 +1104,77 @@ int tg_batch_project_constraints(tg_batch *b, const double *q_host, const double
     HIP_TRY(hipMemcpyAsync(q_out, q, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (dq_out) HIP_TRY(hipMemcpyAsync(dq_out, dq, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, iters, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return TG_SUCCESS;
+}
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the equilibrium kernel for this system (out[0..2]; out[3] 0):
+ * the rollout slice plus the KKT image, W, the Cholesky work area, q0, the kept pose and multipliers, V_q, g, V, the solver's row
+ * scales and the free configs' places (mvi_equilibrium.hpp).  TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a workgroup can
+ * have, and for a system with a NonlinearConfigSpring (no potential to minimise). */
+int tg_system_equilibrium_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::EquilibriumArgs J{};
+    tg::equilibrium_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nc, J);
+    const long long bytes = (long long)(64 / sys->team) * J.lds_per_team * (long long)sizeof(double);
+    out[0] = sys->team; out[1] = J.lds_per_team; out[2] = (int32_t)std::min<long long>(bytes, 0x7fffffff); out[3] = 0;
+    if (sys->H.p.n_ncs > 0) return fail(TG_ERR_UNSUPPORTED, "a NonlinearConfigSpring has a force but no potential energy (as in the reference): nothing to minimise");
+    if (bytes > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident equilibrium kernel");
+    return TG_SUCCESS;
+}
+
+int tg_batch_minimize_potential_device(tg_batch *b, const double *q_dev, const int32_t *free_dev, double tolerance, int32_t max_iterations,
+                                       double *q_out_dev, double *mu_out_dev, double *v_out_dev, int32_t *iterations_out_dev,
+                                       int32_t *status_out_dev) {
+    if (!b || !q_dev || !q_out_dev) return fail(TG_ERR_INVALID, "null argument");
+    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
+    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    int32_t geo[4];
+    if (int rc = tg_system_equilibrium_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch;
+    HIP_TRY(b->equi_ints.ensure(b->P.nq + 2 * B));
+    // the pose is an argument of this call: nothing of the integrator (q1, q2, p, lambda1, status) is read or written.  A loaded
+    // specialised library has no say; a parameter table has (masses and gravity move an equilibrium; damping plays no part)
+    tg::RunArgs A = base_args(b, tg::MODE_EQUILIBRIUM);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.tolerance = tolerance; A.max_iterations = max_iterations;
+    A.iters = iterations_out_dev ? iterations_out_dev : b->equi_ints.get() + b->P.nq;
+    A.status = status_out_dev ? status_out_dev : b->equi_ints.get() + b->P.nq + B;
+    tg::EquilibriumArgs J{};
+    tg::equilibrium_layout(b->P.lds_per_team, b->P.nq, b->P.nc, J);
+    J.free_mask = free_dev; J.q0 = q_dev; J.q = q_out_dev; J.mu = mu_out_dev; J.v = v_out_dev;
+    const bool par = b->par_rows > 0;
+    const int per_block = 64 / b->sys->team, grid = (b->batch + per_block - 1) / per_block;
+    int rc = tg_detail::launch_equilibrium(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+                                           tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0}, grid,
+                                           (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[par][0].add(tg::MODE_EQUILIBRIUM);      // a refused launch (the profiling build) is not counted
+    return rc;
+}
+
+int tg_batch_minimize_potential(tg_batch *b, const double *q_host, const int32_t *free_host, double tolerance, int32_t max_iterations,
+                                double *q_out, double *mu_out, double *v_out, int32_t *iterations_out, int32_t *status_out) {
+    if (!b || !q_host || !q_out) return fail(TG_ERR_INVALID, "null argument");
+    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
+    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    int32_t geo[4];
+    if (int rc = tg_system_equilibrium_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc;
+    HIP_TRY(b->equi.ensure(B * (2 * nq + nc + 2)));
+    HIP_TRY(b->equi_ints.ensure(nq + 2 * B));
+    double *q0 = b->equi.get(), *q = q0 + B * nq, *mu = q + B * nq, *v = mu + B * nc;
+    int *mask = b->equi_ints.get(), *iters = mask + nq, *status = iters + B;
+    HIP_TRY(hipMemcpyAsync(q0, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (free_host && nq) HIP_TRY(hipMemcpyAsync(mask, free_host, nq * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (int rc = tg_batch_minimize_potential_device(b, q0, free_host ? mask : nullptr, tolerance, max_iterations, q, mu, v, iters, status)) return rc;
+    HIP_TRY(hipMemcpyAsync(q_out, q, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (v_out) HIP_TRY(hipMemcpyAsync(v_out, v, B * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, iters, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));

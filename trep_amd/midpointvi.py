@@ -21,6 +21,7 @@ from .descriptor import flatten
 from .errors import ConvergenceError
 
 Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")      # BatchMidpointVI.satisfy_constraints
+Equilibrium = collections.namedtuple("Equilibrium", "Q mu V iterations status")     # BatchMidpointVI.minimize_potential_energy
 
 
 class BatchMidpointVI(object):
@@ -240,7 +241,9 @@ class BatchMidpointVI(object):
         kernel, and the launch counts; `helper_waves` = wavefronts per trajectory in the loaded library's derivative kernels; `fb_n` = joints of the
         translational prefix the loaded rollout kernel has closed forms for; `tr_n` = joints of translation runs whose world poses it stores directly;
         `spec_library` the loaded file.  The par_* keys: the same for the per-trajectory parameter kernels (set_parameters),
-        over all kernel modes (ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
+        over all kernel modes (ALL_MODES), with `par_spec_launch_mask` / `par_generic_launch_mask` the raw mode bits as
+        `spec_launch_mask` / `generic_launch_mask` are for the default kernels (bit 9: the projection, bit 10: the equilibrium search,
+        which have no name in ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
         out = np.zeros(8, dtype=np.int32)
         _lib.check(self._L.tg_batch_info(self._h, out.ctypes.data_as(_lib._c_ip)))
         names = lambda bits: sorted(n for n, m in self.MODES.items() if (int(bits) >> m) & 1)
@@ -253,7 +256,7 @@ class BatchMidpointVI(object):
                 "helper_waves": int(out[7]) & 0xFF, "fb_n": (int(out[7]) >> 8) & 0xFF, "tr_n": (int(out[7]) >> 16) & 0xFF, "spec_library": self._specialized,
                 # per-trajectory parameter kernels (set_parameters); the keys above count the default kernels only
                 "par_spec_modes": every(par[0]), "par_spec_launched": every(par[1]), "par_generic_launched": every(par[2]),
-                "par_spec_launches": int(par[3]), "par_generic_launches": int(par[4]), "parameter_rows": int(par[5]),
+                "par_spec_launch_mask": int(par[1]), "par_generic_launch_mask": int(par[2]), "par_spec_launches": int(par[3]), "par_generic_launches": int(par[4]), "parameter_rows": int(par[5]),
                 "parameter_group": int(par[6])}
 
     @property
@@ -520,6 +523,26 @@ class BatchMidpointVI(object):
                                                         float(tolerance), int(max_iterations), _lib.ptr(q), _lib.ptr(dq), _lib.ptr(mu),
                                                         iters.ctypes.data, status.ctypes.data))
         return Projection(q, dq, mu, iters, status)
+
+    def minimize_potential_energy(self, Q, tolerance=1e-10, keep_kinematic=False, constant_q_list=None, max_iterations=100):
+        """System.minimize_potential_energy (reference trep/system.py:215-272) for B poses in one launch: every Q[b] moves to a
+        minimum of the potential energy over the free configs (the others keep their values bit for bit) with h(q) = 0, by a
+        safeguarded Newton iteration on the KKT conditions (include/trep_amd.h, tg_batch_minimize_potential).  With a parameter
+        table (set_parameters) each pose rests under its own row's masses, inertias and gravity.  Q [B][nq].  Returns the
+        namedtuple (Q, mu, V, iterations, status): [B][nq], [B][nc] multipliers, [B][2] the potential at the start and at the
+        returned pose, [B] trials, [B] TG_OK / TG_NOT_CONVERGED (q = the last accepted iterate) / TG_SINGULAR (the
+        regularisation ran out).  Nothing is raised for a pose that fails: look at status.  The system's own configuration and
+        the integrator state of the batch are left alone."""
+        self.refresh()
+        B = self._batch
+        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
+        free = None if not (keep_kinematic or constant_q_list) else self.free_mask(keep_kinematic, constant_q_list)
+        q, mu, v = np.zeros((B, self.nq)), np.zeros((B, self.nc)), np.zeros((B, 2))
+        iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        _lib.check(self._L.tg_batch_minimize_potential(self._h, _lib.ptr(Q), None if free is None else free.ctypes.data, float(tolerance),
+                                                       int(max_iterations), _lib.ptr(q), _lib.ptr(mu), _lib.ptr(v), iters.ctypes.data,
+                                                       status.ctypes.data))
+        return Equilibrium(q, mu, v, iters, status)
 
     def _seeds(self, seeds, most):
         """(seed1,) or (seed1, seed2) -> contiguous int32 [B] arrays: the input variable each trajectory's direction follows, numbered
