@@ -1,6 +1,6 @@
 """Batched equilibrium search without a device: the numpy reference (equilibrium_reference.py) on its case table with the certificate
 of a minimum that does not depend on the iteration, the failures of the undamped iteration, the mutations the table must catch, and
-the kernel itself (mvi_equilibrium.hpp) compiled for the host with TEAM = 1 (emu_equilibrium_harness.py) against the reference --
+the kernel itself (mvi_equilibrium.hpp) compiled for the host with TEAM = 1 (emu_pose_harness.py) against the reference --
 end points within the per-case bound, V within the energy parity figure, trial counts and status equal on every row whose decisions
 are firm -- with its parameter-table twin, the status cases, the refusals of the C entry points and the layout guards.
 
@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import common
-import emu_equilibrium_harness
+import emu_pose_harness
 import emu_harness
 import equilibrium_reference as er
 import projection_reference as pr
@@ -26,7 +26,7 @@ ERR_INVALID, ERR_UNSUPPORTED = -1, -3
 
 
 def _emu(name):
-    return emu_equilibrium_harness.EmuEquilibrium(common.build(name)[1])
+    return emu_pose_harness.EmuEquilibrium(common.build(name)[1])
 
 
 # ---- 1. the reference reaches certified minima on the table -------------------------------------------------------------------
@@ -208,7 +208,7 @@ def test_status_empty_free_set():
     assert list(got.status) == [er.OK, er.SINGULAR] and not got.iterations.any()      # nothing free: g is empty, the test is h alone
     assert np.array_equal(got.Q, np.array([rest, Q0[0]]))
     d = common.build("pendulum1")[1]
-    hang = emu_equilibrium_harness.EmuEquilibrium(d).minimize(np.array([[0.0], [0.3]]), np.zeros(1, dtype=bool))
+    hang = emu_pose_harness.EmuEquilibrium(d).minimize(np.array([[0.0], [0.3]]), np.zeros(1, dtype=bool))
     assert list(hang.status) == [er.OK, er.OK] and not hang.iterations.any()          # no constraint either: nothing to test
     assert np.array_equal(hang.Q, [[0.0], [0.3]])
 
@@ -284,7 +284,7 @@ def test_lds_of_a_workgroup_and_its_refusal(monkeypatch, name, team):
     monkeypatch.setenv("TREPAMD_TEAM", str(team))
     L = _lib.lib()
     d = common.build(name)[1]
-    slice_, rollout = emu_equilibrium_harness.EmuEquilibrium(d).lds_doubles()
+    slice_, rollout = emu_pose_harness.EmuEquilibrium(d).lds_doubles()
     assert rollout == emu_harness.lds_slices(d)["rollout"]
     assert slice_ == lds_doubles(rollout, int(d.n_configs), int(d.n_constraints))
     sys_h = L.tg_system_create(d.byref())
@@ -317,7 +317,7 @@ def test_both_sides_of_the_lds_limit_are_in_the_cells(monkeypatch):
 
 # ---- 6. layout guards -----------------------------------------------------------------------------------------------------------
 def test_run_args_layout_is_the_emulation_harness_mirror():
-    assert ctypes.sizeof(emu_harness.RunArgs) == emu_equilibrium_harness.sizeof_run_args()
+    assert ctypes.sizeof(emu_harness.RunArgs) == emu_pose_harness.sizeof_run_args()
 
 
 def test_the_new_entry_points_are_exported_and_declared():

@@ -1,6 +1,6 @@
 """Batched constraint projection without a device: the numpy reference (projection_reference.py) on its case table, the checks of an
 answer that do not depend on the iteration, the teeth of those checks, and the kernel itself (mvi_project.hpp) compiled for the host
-with TEAM = 1 (emu_project_harness.py) against the reference -- answers within the per-case bound, step counts within one, the
+with TEAM = 1 (emu_pose_harness.py) against the reference -- answers within the per-case bound, step counts within one, the
 status cases, the refusals of the C entry points and the layout guards.
 
 Per case, floor = max |q_ref(tolerance 1e-10) - q_ref(tolerance 1e-13)| and the bound on |q - q_ref| is 64 max(floor, 1e-13)
@@ -14,7 +14,7 @@ import pytest
 
 import common
 import emu_harness
-import emu_project_harness
+import emu_pose_harness
 import projection_reference as pr
 from trep_amd import _lib
 
@@ -23,7 +23,7 @@ ERR_INVALID, ERR_UNSUPPORTED = -1, -3
 
 
 def _emu(name):
-    return emu_project_harness.EmuProjection(common.build(name)[1])
+    return emu_pose_harness.EmuProjection(common.build(name)[1])
 
 
 # ---- 1. the reference iteration converges on the table ----------------------------------------------------------------------
@@ -175,7 +175,7 @@ def test_status_empty_free_set():
 
 def test_status_without_constraints():
     d = common.build("pendulum1")[1]
-    emu = emu_project_harness.EmuProjection(d)
+    emu = emu_pose_harness.EmuProjection(d)
     Q = np.array([[0.3], [-1.2], [4.0]])
     dQ = np.array([[1.0], [2.0], [3.0]])
     got = emu.project(Q, dQ)
@@ -224,7 +224,7 @@ def test_lds_of_a_workgroup_and_its_refusal(monkeypatch, name, team):
     d = common.build(name)[1]
     nq, nc = int(d.n_configs), int(d.n_constraints)
     n = nq + nc
-    slice_, rollout = emu_project_harness.EmuProjection(d).lds_doubles()
+    slice_, rollout = emu_pose_harness.EmuProjection(d).lds_doubles()
     assert rollout == emu_harness.lds_slices(d)["rollout"]
     even = lambda x: (x + 1) & ~1
     assert slice_ == even(even(even(rollout) + n * (n + 1) + nq + n) + (nq + 1) // 2)
@@ -258,7 +258,7 @@ def test_both_sides_of_the_lds_limit_are_in_the_cells(monkeypatch):
 
 # ---- 8. layout guards -------------------------------------------------------------------------------------------------------
 def test_run_args_layout_is_the_emulation_harness_mirror():
-    assert ctypes.sizeof(emu_harness.RunArgs) == emu_project_harness.sizeof_run_args()
+    assert ctypes.sizeof(emu_harness.RunArgs) == emu_pose_harness.sizeof_run_args()
 
 
 def test_the_new_entry_points_are_exported_and_declared():

@@ -39,7 +39,7 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import common
-    import emu_equilibrium_harness
+    import emu_pose_harness
     import equilibrium_reference as er
 
     def measured(got, ref):
@@ -59,7 +59,7 @@ def main():
                    reference_steps=[int(steps.min()), int(steps.max())], reference_margin=float(ref.margin.min()),
                    thin_rows=int((~er.firm_rows(ref)).sum()), draw=er.DRAW.get(case, 0),
                    certified=bool(er.certified(name, ref, free).all()))
-        emu = emu_equilibrium_harness.EmuEquilibrium(common.build(name)[1]).minimize(Q0, free, tolerance=er.TOL)
+        emu = emu_pose_harness.EmuEquilibrium(common.build(name)[1]).minimize(Q0, free, tolerance=er.TOL)
         row["emulation_error"], row["emulation_mu_error"], row["emulation_v_error"], row["emulation_steps"] = measured(emu, ref)
         row["device_error"] = row["device_mu_error"] = row["device_v_error"] = row["device_steps"] = None
         if not args.cpu_only:

@@ -32,7 +32,7 @@ def main():
     args = ap.parse_args()
     import numpy as np
     import common
-    import emu_project_harness
+    import emu_pose_harness
     import projection_reference as pr
 
     def measured(name, case, got, ref):
@@ -46,7 +46,7 @@ def main():
         ref = pr.case_reference(*case)
         row = dict(system=name, mask=mask, noise=noise, rows=len(Q0), floor=pr.case_floor(*case), bound=pr.case_bound(*case),
                    reference_steps=int(ref.iterations.max()))
-        emu = emu_project_harness.EmuProjection(common.build(name)[1]).project(Q0, dQ0, free, tolerance=pr.TOL)
+        emu = emu_pose_harness.EmuProjection(common.build(name)[1]).project(Q0, dQ0, free, tolerance=pr.TOL)
         row["emulation_error"], row["emulation_steps"], row["emulation_residual"] = measured(name, case, emu, ref)
         row["device_error"] = row["device_steps"] = row["device_residual"] = None
         if not args.cpu_only:

@@ -21,22 +21,21 @@
 // Every decision reads LDS words that the whole team sees, so it is team-uniform without a vote; the teams of a wavefront leave
 // together (__all) and a finished team idles through the phases.  A rejected trial puts q and mu back and evaluates the point
 // again: the same arithmetic on the same input, so the state is the one before the trial bit for bit.
-// LDS of a team: the rollout slice (sweeps, h, the sparse Dh; mu in its lambda area) and behind it, at offsets the host computes
-// (EquilibriumArgs): the KKT image [n][n + 1], n <= nq + nc; W [nF][nF]; the Cholesky work area [nF][nF]; q0 [nq]; the pose and
-// multipliers before the trial [nq + nc]; V_q [nq] and g [nq]; V (2 words); the solver's row scales [nq + nc]; the free configs'
-// places (int [nq]).
-// Compiled by hipcc (trepamd_equilibrium.hip: k_equilibrium) and, with TEAM = 1, by g++ for the CPU tests (tests/emu_equilibrium).
+// LDS of a team: the rollout slice (sweeps, h, the sparse Dh; mu in its lambda area) and behind it the frame's scratch (mvi_pose.hpp:
+// the KKT image, q0, the solver's row scales, the free configs' places) with the search's own regions in it: behind the image
+// W [nF][nF] and the Cholesky work area [nF][nF]; behind q0 the pose and multipliers before the trial [nq + nc], V_q [nq], g [nq]
+// and V (2 words).
+// Compiled by hipcc (trepamd_equilibrium.hip: k_equilibrium) and, with TEAM = 1, by g++ for the CPU tests (tests/emu_pose).
 #pragma once
 #include <cfloat>
 
-#include "mvi_core.hpp"
+#include "mvi_pose.hpp"
 
 namespace tg {
 
 constexpr int MODE_EQUILIBRIUM = 10;
 
-// Passed beside RunArgs (whose layout the host emulation mirrors), as ParTable is.  RunArgs supplies batch, tolerance, max_iterations,
-// the remap fields and the iteration / status words (the call's own, not the integrator's).
+// (the fields of the frame, mvi_pose.hpp, V and the search's own regions)
 struct EquilibriumArgs {
     const int *free_mask;        // [nq] device, non-zero = free; null: every config
     const double *q0;            // [batch][nq]
@@ -45,70 +44,32 @@ struct EquilibriumArgs {
     int lds_per_team;            // doubles per team: what the kernel strides its teams by
 };
 
-// the scratch layout of one team for a system of the given sizes (host; the same numbers for the device launch and the emulation)
 inline void equilibrium_layout(int rollout_lds_per_team, int nq, int nc, EquilibriumArgs &J) {
-    const int n = nq + nc;
-    int off = (rollout_lds_per_team + 1) & ~1;
-    J.o_kkt = off; off += n * (n + 1);
-    J.o_w = off; off += nq * nq;
-    J.o_chol = off; off += nq * nq;
-    J.o_q0 = off; off += nq;
-    J.o_keep = off; off += n;
-    J.o_vq = off; off += nq;
-    J.o_g = off; off += nq;
-    J.o_v = off; off += 2;
-    J.o_scal = off; off += n;
-    off = (off + 1) & ~1;
-    J.o_idx = off; off += (nq + 1) / 2;
-    J.lds_per_team = (off + 1) & ~1;
+    pose_layout(rollout_lds_per_team, nq, nc, J, {{&J.o_w, nq * nq}, {&J.o_chol, nq * nq}},
+                {{&J.o_keep, nq + nc}, {&J.o_vq, nq}, {&J.o_g, nq}, {&J.o_v, 2}});
 }
 
 template <int TEAM, bool SPRINGS, bool PAR, class PROG, class ARGS>
 TG_HD void run_equilibrium(PROG &P, ARGS &A, const EquilibriumArgs &J, const ParTable T, double *S, int lane, int traj) {
     const int nq = P.nq, nd = P.nd, nc = P.nc;
-    const bool live = traj < A.batch;
-    const size_t t = (size_t)(live ? traj : 0);
+    PoseFrame<TEAM, PROG, EquilibriumArgs> F(P, J, S, lane, traj, A.batch);
+    const bool live = F.live;
+    const size_t t = F.t;
     Core<TEAM, SPRINGS, PROG, double, PAR> core(P, S, lane, 1.0);
     if constexpr (PAR) core.par = T.rows + (t / (size_t)T.group) * (size_t)T.stride + 4 * P.n_bodies;
     else (void)T;
     core.init_sweep_schedule(false);
-    double *K = S + J.o_kkt, *W = S + J.o_w, *C = S + J.o_chol, *Q0 = S + J.o_q0, *keep = S + J.o_keep, *Vq = S + J.o_vq, *G = S + J.o_g;
-    double *Vs = S + J.o_v, *scal = S + J.o_scal;
-    int *idx = (int *)(S + J.o_idx);
-    // the free configs' places in the image, in config order; nF (every lane counts: uniform)
-    int nF = 0;
-    for (int k = 0; k < nq; k++) nF += (!J.free_mask || J.free_mask[k]) ? 1 : 0;
-    TG_FOR(k, nq) {
-        int at = 0;
-        for (int j = 0; j < k; j++) at += (!J.free_mask || J.free_mask[j]) ? 1 : 0;
-        idx[k] = (!J.free_mask || J.free_mask[k]) ? at : -1;
-    }
-    const int n = nF + nc, ld = n + 1;
-    if (live) {
-        TG_FOR(i, nq) { const double v = J.q0[t * nq + i]; Q0[i] = v; S[P.o_q1 + i] = v; S[P.o_q2 + i] = v; }
-        TG_FOR(c, nc) S[P.o_lam + c] = 0.0;
-        TG_FOR(i, P.n_dh) S[P.o_Dh2 + i] = 0.0;
-    }
-    TG_SYNC();
-
-#if defined(__HIP_DEVICE_COMPILE__)
-    auto any = [](bool f) { return __any(f ? 1 : 0) != 0; };     // a phase no team of the wavefront needs is skipped by all of them
-#else
-    auto any = [](bool f) { return f; };
-#endif
+    double *K = F.K, *W = S + J.o_w, *C = S + J.o_chol, *keep = S + J.o_keep, *Vq = S + J.o_vq, *G = S + J.o_g;
+    double *Vs = S + J.o_v, *scal = F.scal;
+    int *idx = F.idx;
+    const int nF = F.index_free(), n = nF + nc, ld = n + 1;
+    F.load_pose();
 
     // everything the iteration reads at (q2, lambda area): h, Dh, V, V_q, W with the multipliers' curvature, g
     auto evaluate = [&](bool on) {
-        if (!any(on)) return;
+        if (!pose_any(on)) return;
         core.potential_lds(on, S + P.o_Dh2, Vs, Vq, W, nF, idx);
-        if (on) for (int pp = tg_opaque(lane); pp < P.n_cpair; pp += TEAM) {     // (several constraints reach the same entry: LDS atomics)
-            const int *pw = P.cpair4 + 4 * (size_t)pp;
-            const int c = pw[0], na = pw[1], nb = pw[2], a = idx[pw[3] & 0xFFFF], b = idx[pw[3] >> 16];
-            if (a < 0 || b < 0) continue;
-            const double h = S[P.o_lam + c] * core.con_d2(c, na, nb);
-            lds_add(&W[b * nF + a], h);
-            if (na != nb) lds_add(&W[a * nF + b], h);
-        }
+        if (on) F.add_curvature(core, W, nF);
         if (on) TG_FOR(k, nq) {
             const int a = idx[k];
             if (a < 0) continue;
@@ -131,11 +92,7 @@ TG_HD void run_equilibrium(PROG &P, ARGS &A, const EquilibriumArgs &J, const Par
         if (on) TG_FOR(i, n * ld) K[i] = 0.0;
         TG_SYNC();
         if (on) {
-            TG_FOR(m, P.n_dh) {
-                const int c = P.dh_pack[8 * (size_t)m], k = P.dh_pack[8 * (size_t)m + 1], a = idx[k];
-                const double v = S[P.o_Dh2 + m];
-                if (a >= 0) { K[(nF + c) * ld + a] = v; K[a * ld + nF + c] = v; }
-            }
+            F.scatter_dh(nF, ld);
             TG_FOR(e, nF * nF) { const int a = e / nF, b = e % nF; K[a * ld + b] = identity ? (a == b ? 1.0 : 0.0) : W[e] + (a == b ? tau : 0.0); }
             TG_FOR(a, nF) K[a * ld + n] = -first[a];
             TG_FOR(c, nc) K[(nF + c) * ld + n] = second ? -S[P.o_f + nd + c] : 0.0;
@@ -197,11 +154,7 @@ TG_HD void run_equilibrium(PROG &P, ARGS &A, const EquilibriumArgs &J, const Par
             else if (iterations >= A.max_iterations) { done = true; status = TG_NOT_CONVERGED; }
             else if (tau > 1e9 * wmax) { done = true; status = TG_SINGULAR; }
         }
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (__all(done ? 1 : 0) != 0) break;       // the teams of a wavefront leave together: a finished one idles through the phases
-#else
-        if (done) break;
-#endif
+        if (pose_all(done)) break;       // the teams of a wavefront leave together: a finished one idles through the phases
         if (!done) iterations++;
         assemble(!done, false, tau, G, true);
         double dmax = 0.0;
@@ -248,14 +201,8 @@ TG_HD void run_equilibrium(PROG &P, ARGS &A, const EquilibriumArgs &J, const Par
             else tau = 4.0 * tau > 1e-3 * wmax ? 4.0 * tau : 1e-3 * wmax;
         }
     }
-    if (live) {
-        TG_FOR(i, nq) J.q[t * nq + i] = S[P.o_q2 + i];
-        if (J.mu) TG_FOR(c, nc) J.mu[t * nc + c] = S[P.o_lam + c];
-        if (lane == 0) {
-            if (J.v) { J.v[2 * t] = v_start; J.v[2 * t + 1] = Vs[0]; }
-            A.iters[t] = iterations; A.status[t] = status;
-        }
-    }
+    if (live && lane == 0 && J.v) { J.v[2 * t] = v_start; J.v[2 * t + 1] = Vs[0]; }
+    F.store(A, iterations, status);
 }
 
 }  // namespace tg

@@ -18,18 +18,17 @@
 // [[I, D'], [D, 0]] (d, nu) = (0, -Dh(q) dq0), dq_F = dq0_F + d -- through the same matrix image and solver.
 //
 // LDS of a team: the rollout slice (the sweeps and the constraint evaluation work in it; mu lives in its lambda area, the sparse Dh in
-// its Dh2 area) and behind it, at offsets the host computes (ProjectArgs): the KKT image [n][n + 1], n <= nq + nc; q0 [nq]; the
-// solver's row scales [nq + nc]; the free configs' places in the image (int [nq]).
-// Compiled by hipcc (trepamd_project.hip: k_project) and, with TEAM = 1, by g++ for the CPU tests (tests/emu_project).
+// its Dh2 area) and behind it the frame's scratch alone (mvi_pose.hpp): the KKT image, q0, the solver's row scales, the free configs'
+// places in the image.
+// Compiled by hipcc (trepamd_project.hip: k_project) and, with TEAM = 1, by g++ for the CPU tests (tests/emu_pose).
 #pragma once
-#include "mvi_core.hpp"
+#include "mvi_pose.hpp"
 
 namespace tg {
 
 constexpr int MODE_PROJECT = 9;
 
-// Passed beside RunArgs (whose layout the host emulation mirrors), as ParTable is.  RunArgs supplies batch, tolerance, max_iterations,
-// the remap fields and the iteration / status words (iters, status: the projection's own, not the integrator's).
+// (the fields of the frame, mvi_pose.hpp, and the rates)
 struct ProjectArgs {
     const int *free_mask;        // [nq] device, non-zero = free; null: every config
     const double *q0, *dq0;      // [batch][nq]; dq0 null: no velocity part
@@ -38,53 +37,27 @@ struct ProjectArgs {
     int lds_per_team;            // doubles per team: what the kernel strides its teams by
 };
 
-// the scratch layout of one team for a system of the given sizes (host; the same numbers for the device launch and the emulation)
-inline void project_layout(int rollout_lds_per_team, int nq, int nc, ProjectArgs &J) {
-    const int n = nq + nc;
-    int off = (rollout_lds_per_team + 1) & ~1;
-    J.o_kkt = off; off += n * (n + 1);
-    J.o_q0 = off; off += nq;
-    J.o_scal = off; off += n;
-    off = (off + 1) & ~1;
-    J.o_idx = off; off += (nq + 1) / 2;
-    J.lds_per_team = (off + 1) & ~1;
-}
+inline void project_layout(int rollout_lds_per_team, int nq, int nc, ProjectArgs &J) { pose_layout(rollout_lds_per_team, nq, nc, J); }
 
 template <int TEAM, bool SPRINGS, class PROG, class ARGS>
 TG_HD void run_project(PROG &P, ARGS &A, const ProjectArgs &J, double *S, int lane, int traj) {
     const int nq = P.nq, nd = P.nd, nc = P.nc;
-    const bool live = traj < A.batch;
-    const size_t t = (size_t)(live ? traj : 0);
     Core<TEAM, SPRINGS, PROG, double> core(P, S, lane, 1.0);
     core.init_sweep_schedule(false);
-    double *K = S + J.o_kkt, *Q0 = S + J.o_q0, *scal = S + J.o_scal;
-    int *idx = (int *)(S + J.o_idx);
-    // the free configs' places in the image, in config order; nF (every lane counts: uniform)
-    int nF = 0;
-    for (int k = 0; k < nq; k++) nF += (!J.free_mask || J.free_mask[k]) ? 1 : 0;
-    TG_FOR(k, nq) {
-        int at = 0;
-        for (int j = 0; j < k; j++) at += (!J.free_mask || J.free_mask[j]) ? 1 : 0;
-        idx[k] = (!J.free_mask || J.free_mask[k]) ? at : -1;
-    }
-    const int n = nF + nc, ld = n + 1;
-    if (live) {
-        TG_FOR(i, nq) { const double v = J.q0[t * nq + i]; Q0[i] = v; S[P.o_q1 + i] = v; S[P.o_q2 + i] = v; }
-        TG_FOR(c, nc) S[P.o_lam + c] = 0.0;
-        TG_FOR(i, P.n_dh) S[P.o_Dh2 + i] = 0.0;
-    }
-    TG_SYNC();
+    PoseFrame<TEAM, PROG, ProjectArgs> F(P, J, S, lane, traj, A.batch);
+    const bool live = F.live;
+    const size_t t = F.t;
+    double *K = F.K, *Q0 = F.Q0, *scal = F.scal;
+    int *idx = F.idx;
+    const int nF = F.index_free(), n = nF + nc, ld = n + 1;
+    F.load_pose();
 
     // the image without the curvature block: zeros, D and D' from the sparse Dh, the identity, the right-hand side -(g | h)
     auto assemble = [&](bool on, bool velocity) {
         if (on) TG_FOR(i, n * ld) K[i] = 0.0;
         TG_SYNC();
         if (on) {
-            TG_FOR(m, P.n_dh) {
-                const int c = P.dh_pack[8 * (size_t)m], k = P.dh_pack[8 * (size_t)m + 1], a = idx[k];
-                const double v = S[P.o_Dh2 + m];
-                if (a >= 0) { K[(nF + c) * ld + a] = v; K[a * ld + nF + c] = v; }
-            }
+            F.scatter_dh(nF, ld);
             TG_FOR(k, nq) { const int a = idx[k]; if (a >= 0) K[a * ld + a] = 1.0; }
         }
         TG_SYNC();
@@ -118,20 +91,8 @@ TG_HD void run_project(PROG &P, ARGS &A, const ProjectArgs &J, double *S, int la
             else if (nF == 0 || nc == 0) { done = true; status = TG_SINGULAR; }
             else if (iterations >= A.max_iterations) { done = true; status = TG_NOT_CONVERGED; }
         }
-#if defined(__HIP_DEVICE_COMPILE__)
-        if (__all(done ? 1 : 0) != 0) break;       // the teams of a wavefront leave together: a finished one idles through the phases
-#else
-        if (done) break;
-#endif
-        // curvature: sum_c mu_c h_c,qq(a, b) over the free configs (several constraints reach the same entry: LDS atomics)
-        if (!done) for (int pp = tg_opaque(lane); pp < P.n_cpair; pp += TEAM) {
-            const int *pw = P.cpair4 + 4 * (size_t)pp;
-            const int c = pw[0], na = pw[1], nb = pw[2], a = idx[pw[3] & 0xFFFF], b = idx[pw[3] >> 16];
-            if (a < 0 || b < 0) continue;
-            const double h = S[P.o_lam + c] * core.con_d2(c, na, nb);
-            lds_add(&K[b * ld + a], h);
-            if (na != nb) lds_add(&K[a * ld + b], h);
-        }
+        if (pose_all(done)) break;       // the teams of a wavefront leave together: a finished one idles through the phases
+        if (!done) F.add_curvature(core, K, ld);
         TG_SYNC();
         const bool ok = core.gauss_jordan(!done, K, n, 1, ld, scal);
         if (!done && !ok) { done = true; status = TG_SINGULAR; }
@@ -154,11 +115,7 @@ TG_HD void run_project(PROG &P, ARGS &A, const ProjectArgs &J, double *S, int la
             J.dq[t * nq + k] = (von && ok && a >= 0) ? v + K[a * ld + n] : v;
         }
     }
-    if (live) {
-        TG_FOR(i, nq) J.q[t * nq + i] = S[P.o_q2 + i];
-        if (J.mu) TG_FOR(c, nc) J.mu[t * nc + c] = S[P.o_lam + c];
-        if (lane == 0) { A.iters[t] = iterations; A.status[t] = status; }
-    }
+    F.store(A, iterations, status);
 }
 
 }  // namespace tg

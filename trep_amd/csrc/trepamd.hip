@@ -16,14 +16,13 @@
 #include <vector>
 
 #include "device_buffer.hpp"
-#include "mvi_core.hpp"
+#include "launch_generic.hpp"
 #include "mvi_project.hpp"
 #include "mvi_equilibrium.hpp"
 #include "schedule.hpp"
 #include <dlfcn.h>
 
 namespace tg_detail {
-int fail(int code, const std::string &msg);
 // the generic per-trajectory-parameter kernels (trepamd_par.hip: their own object, compiled beside this one)
 int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the constraint-projection kernel (trepamd_project.hip, likewise)
@@ -125,10 +124,9 @@ struct tg_batch {
     tg::DeviceBuffer<double> energy;  // [batch][2] output of tg_batch_energy
     tg::DeviceBuffer<double> lag;     // outputs of tg_batch_lagrangian
     tg::DeviceBuffer<int> dyn_ints;   // its status / iteration words (the integrator's own stay untouched)
-    tg::DeviceBuffer<double> proj;    // staging of the host-facing constraint projection: q0, dq0 in, q, dq, mu out
-    tg::DeviceBuffer<int> proj_ints;  // its free mask [nq], iteration [batch] and status [batch] words
-    tg::DeviceBuffer<double> equi;    // staging of the host-facing equilibrium search: q0 in, q, mu, V out
-    tg::DeviceBuffer<int> equi_ints;  // its free mask [nq], iteration [batch] and status [batch] words
+    tg::DeviceBuffer<double> pose;    // staging of the host-facing pose solvers (stream-ordered, one call at a time): q0 in, q, mu out, and
+                                      // the projection's dq0 in, dq out or the equilibrium search's V out
+    tg::DeviceBuffer<int> pose_ints;  // their free mask [nq], iteration [batch] and status [batch] words
     tg::DeviceBuffer<int> seeds;      // [2][batch] direction variables of the forward-mode calls
     tg::DeviceBuffer<double> d1[12];
     bool have_d1 = false;
@@ -204,14 +202,6 @@ void append(std::vector<T> &pool, const std::vector<T> &v, size_t &off) {
     while (pool.size() % 2) pool.push_back(T());
 }
 
-template <int TEAM, int MODE, bool SPRINGS>
-int launch_variant(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_run<TEAM, MODE, SPRINGS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_run<TEAM, MODE, SPRINGS>), dim3(grid), dim3(64), lds, b->stream, b->d_prog.get(), A);
-    return TG_SUCCESS;
-}
-
 bool launch_springs(const tg::DevProg &P) { return P.has_cs || P.n_springs || P.has_plane || P.n_wrenches; }
 bool launch_springs(const tg_batch *b) { return launch_springs(b->P); }
 // doubles of LDS that one team of a mode-`mode` kernel keeps (the slice k_run strides its teams by)
@@ -225,9 +215,9 @@ int launch_one(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
 #if defined(TG_PROFILE)   // the diagnostic build only instruments the plain kernels of full-wave teams (fewer instantiations)
     if (TEAM != 64 || launch_springs(b))
         return fail(TG_ERR_UNSUPPORTED, "the profiling build covers full-wave teams without spring / plane / wrench features");
-    return launch_variant<64, MODE, false>(b, A, grid, lds);
+    return tg_detail::launch_kernel(&k_run<64, MODE, false>, grid, lds, b->stream, b->d_prog.get(), A);
 #else
-    return launch_springs(b) ? launch_variant<TEAM, MODE, true>(b, A, grid, lds) : launch_variant<TEAM, MODE, false>(b, A, grid, lds);
+    return tg_detail::launch_kernel(launch_springs(b) ? &k_run<TEAM, MODE, true> : &k_run<TEAM, MODE, false>, grid, lds, b->stream, b->d_prog.get(), A);
 #endif
 }
 
@@ -294,8 +284,7 @@ int launch(tg_batch *b, tg::RunArgs &A) {
     } else {
         b->launched[par][0].add(A.mode);
         rc = par ? tg_detail::launch_par(team, launch_springs(b), b->d_prog.get(), A, tg::ParTable{b->par_dev.get(), b->par_group, b->par_stride}, grid, lds, b->stream)
-                 : (team == 64 ? launch_team<64>(b, A, grid, lds) : (team == 16 ? launch_team<16>(b, A, grid, lds)
-                    : (team == 4 ? launch_team<4>(b, A, grid, lds) : launch_team<1>(b, A, grid, lds))));
+                 : tg_detail::dispatch_team(team, [&](auto team_tag) { return launch_team<decltype(team_tag)::value>(b, A, grid, lds); });
     }
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
     if (b->timing) {
@@ -309,19 +298,12 @@ int launch(tg_batch *b, tg::RunArgs &A) {
 }
 
 #if !defined(TG_PROFILE)
-template <int MODE, bool SPRINGS, class Real>
-int launch_forward_variant(tg_batch *b, const tg::RunArgs &A, size_t lds) {
-    if (lds > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_forward<MODE, SPRINGS, Real>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_forward<MODE, SPRINGS, Real>), dim3(A.batch), dim3(64), lds, b->stream, b->d_prog.get(), A);
-    return TG_SUCCESS;
-}
 template <int MODE, class Real>
 int launch_forward_mode(tg_batch *b, const tg::RunArgs &A) {
     const size_t lds = (size_t)std::max(b->P.lds_per_team, lds_per_team(b->P, MODE)) * sizeof(Real);
     if (lds > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident forward-mode kernel");
     b->launched[0][0].add(MODE);      // no forward-mode kernel is ever specialised (tg_batch_info)
-    int rc = launch_springs(b) ? launch_forward_variant<MODE, true, Real>(b, A, lds) : launch_forward_variant<MODE, false, Real>(b, A, lds);
+    int rc = tg_detail::launch_kernel(launch_springs(b) ? &k_forward<MODE, true, Real> : &k_forward<MODE, false, Real>, A.batch, lds, b->stream, b->d_prog.get(), A);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
     return rc;
 }
@@ -1039,6 +1021,69 @@ int tg_batch_dynamics(tg_batch *b, const double *q_host, const double *dq_host, 
     return TG_SUCCESS;
 }
 
+// ---- the pose solvers: constraint projection (mvi_project.hpp) and equilibrium search (mvi_equilibrium.hpp) on the frame of mvi_pose.hpp
+
+// out[0..3] of a tg_system_*_lds call for a kernel that keeps per_team doubles of LDS per team
+static int pose_lds(const tg_system *sys, int per_team, const char *too_large, int32_t out[4]) {
+    const long long bytes = (long long)(64 / sys->team) * per_team * (long long)sizeof(double);
+    out[0] = sys->team; out[1] = per_team; out[2] = (int32_t)std::min<long long>(bytes, 0x7fffffff); out[3] = 0;
+    if (bytes > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, too_large);
+    return TG_SUCCESS;
+}
+
+// what every entry point of a pose solver checks first
+static int pose_check(const tg_batch *b, const double *q, const double *q_out, double tolerance, int32_t max_iterations) {
+    if (!b || !q || !q_out) return fail(TG_ERR_INVALID, "null argument");
+    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
+    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    return TG_SUCCESS;
+}
+
+// The launch of a pose solver behind its checks: the mode's arguments and the grid.  The pose is an argument of the call: nothing of the
+// integrator (q1, q2, p, lambda1, status) is read or written, and a loaded specialised library has no say.  Iteration and status
+// words nobody asked for go to the batch's own.
+static int pose_prepare(tg_batch *b, int mode, double tolerance, int32_t max_iterations, int32_t *iterations_out_dev, int32_t *status_out_dev,
+                        tg::RunArgs &A, int &grid) {
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch;
+    HIP_TRY(b->pose_ints.ensure(b->P.nq + 2 * B));
+    A = base_args(b, mode);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.tolerance = tolerance; A.max_iterations = max_iterations;
+    A.iters = iterations_out_dev ? iterations_out_dev : b->pose_ints.get() + b->P.nq;
+    A.status = status_out_dev ? status_out_dev : b->pose_ints.get() + b->P.nq + B;
+    const int per_block = 64 / b->sys->team;
+    grid = (b->batch + per_block - 1) / per_block;
+    return TG_SUCCESS;
+}
+
+// Staging of the host-facing pose solvers: q0 and the mask in; q, mu, the iteration and status words out.  `extra` is the call's
+// own: the projection's dq0 and dq, the search's V.
+struct PoseStage {
+    double *q0, *q, *mu, *extra;
+    int *mask, *iters, *status;
+};
+static int pose_stage_in(tg_batch *b, const double *q_host, const int32_t *free_host, PoseStage &s) {
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc;
+    HIP_TRY(b->pose.ensure(B * (2 * nq + nc + std::max<size_t>(2 * nq, 2))));      // (whichever call needs more)
+    HIP_TRY(b->pose_ints.ensure(nq + 2 * B));
+    s.q0 = b->pose.get(); s.q = s.q0 + B * nq; s.mu = s.q + B * nq; s.extra = s.mu + B * nc;
+    s.mask = b->pose_ints.get(); s.iters = s.mask + nq; s.status = s.iters + B;
+    HIP_TRY(hipMemcpyAsync(s.q0, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (free_host && nq) HIP_TRY(hipMemcpyAsync(s.mask, free_host, nq * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    return TG_SUCCESS;
+}
+static int pose_stage_out(tg_batch *b, const PoseStage &s, double *q_out, double *mu_out, int32_t *iterations_out, int32_t *status_out) {
+    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc;
+    HIP_TRY(hipMemcpyAsync(q_out, s.q, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, s.mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, s.iters, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, s.status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return TG_SUCCESS;
+}
+
 /* Team size, doubles of LDS per team and bytes of LDS per workgroup of the projection kernel for this system (out[0..2]; out[3] 0):
  * the rollout slice plus the KKT image, q0, the solver's row scales and the free configs' places (mvi_project.hpp).
  * TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a workgroup can have. */
@@ -1046,36 +1091,24 @@ int tg_system_projection_lds(const tg_system *sys, int32_t out[4]) {
     if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
     tg::ProjectArgs J{};
     tg::project_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nc, J);
-    const long long bytes = (long long)(64 / sys->team) * J.lds_per_team * (long long)sizeof(double);
-    out[0] = sys->team; out[1] = J.lds_per_team; out[2] = (int32_t)std::min<long long>(bytes, 0x7fffffff); out[3] = 0;
-    if (bytes > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident projection kernel");
-    return TG_SUCCESS;
+    return pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident projection kernel", out);
 }
 
 int tg_batch_project_constraints_device(tg_batch *b, const double *q_dev, const double *dq_dev, const int32_t *free_dev, double tolerance,
                                         int32_t max_iterations, double *q_out_dev, double *dq_out_dev, double *mu_out_dev,
                                         int32_t *iterations_out_dev, int32_t *status_out_dev) {
-    if (!b || !q_dev || !q_out_dev) return fail(TG_ERR_INVALID, "null argument");
-    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
-    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    if (int rc = pose_check(b, q_dev, q_out_dev, tolerance, max_iterations)) return rc;
     if (dq_out_dev && !dq_dev) return fail(TG_ERR_INVALID, "dq_out without dq");
     if (dq_dev && !dq_out_dev) return fail(TG_ERR_INVALID, "dq without dq_out");
     int32_t geo[4];
     if (int rc = tg_system_projection_lds(b->sys, geo)) return rc;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch;
-    HIP_TRY(b->proj_ints.ensure(b->P.nq + 2 * B));
-    // the state is an argument of this call: nothing of the integrator (q1, q2, p, lambda1, status) is read or written, and neither a
-    // loaded specialised library nor a parameter table has a say (constraints do not depend on inertia, gravity or damping)
-    tg::RunArgs A = base_args(b, tg::MODE_PROJECT);
-    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
-    A.tolerance = tolerance; A.max_iterations = max_iterations;
-    A.iters = iterations_out_dev ? iterations_out_dev : b->proj_ints.get() + b->P.nq;
-    A.status = status_out_dev ? status_out_dev : b->proj_ints.get() + b->P.nq + B;
+    // no parameter table has a say either (constraints do not depend on inertia, gravity or damping)
+    tg::RunArgs A;
+    int grid;
+    if (int rc = pose_prepare(b, tg::MODE_PROJECT, tolerance, max_iterations, iterations_out_dev, status_out_dev, A, grid)) return rc;
     tg::ProjectArgs J{};
     tg::project_layout(b->P.lds_per_team, b->P.nq, b->P.nc, J);
     J.free_mask = free_dev; J.q0 = q_dev; J.dq0 = dq_dev; J.q = q_out_dev; J.dq = dq_out_dev; J.mu = mu_out_dev;
-    const int per_block = 64 / b->sys->team, grid = (b->batch + per_block - 1) / per_block;
     b->launched[0][0].add(tg::MODE_PROJECT);
     int rc = tg_detail::launch_project(b->sys->team, launch_springs(b), b->d_prog.get(), A, J, grid, (size_t)geo[2], b->stream);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
@@ -1084,30 +1117,19 @@ int tg_batch_project_constraints_device(tg_batch *b, const double *q_dev, const 
 
 int tg_batch_project_constraints(tg_batch *b, const double *q_host, const double *dq_host, const int32_t *free_host, double tolerance,
                                  int32_t max_iterations, double *q_out, double *dq_out, double *mu_out, int32_t *iterations_out, int32_t *status_out) {
-    if (!b || !q_host || !q_out) return fail(TG_ERR_INVALID, "null argument");
-    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
-    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    if (int rc = pose_check(b, q_host, q_out, tolerance, max_iterations)) return rc;
     if (dq_out && !dq_host) return fail(TG_ERR_INVALID, "dq_out without dq");
     int32_t geo[4];
     if (int rc = tg_system_projection_lds(b->sys, geo)) return rc;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc;
-    HIP_TRY(b->proj.ensure(B * (4 * nq + nc)));
-    HIP_TRY(b->proj_ints.ensure(nq + 2 * B));
-    double *q0 = b->proj.get(), *dq0 = q0 + B * nq, *q = dq0 + B * nq, *dq = q + B * nq, *mu = dq + B * nq;
-    int *mask = b->proj_ints.get(), *iters = mask + nq, *status = iters + B;
-    HIP_TRY(hipMemcpyAsync(q0, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (dq_host) HIP_TRY(hipMemcpyAsync(dq0, dq_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (free_host && nq) HIP_TRY(hipMemcpyAsync(mask, free_host, nq * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    if (int rc = tg_batch_project_constraints_device(b, q0, dq_host ? dq0 : nullptr, free_host ? mask : nullptr, tolerance, max_iterations,
-                                                     q, dq_host ? dq : nullptr, mu, iters, status)) return rc;
-    HIP_TRY(hipMemcpyAsync(q_out, q, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (dq_out) HIP_TRY(hipMemcpyAsync(dq_out, dq, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, iters, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return TG_SUCCESS;
+    PoseStage s;
+    if (int rc = pose_stage_in(b, q_host, free_host, s)) return rc;
+    const size_t rates = (size_t)b->batch * b->P.nq;
+    double *dq0 = s.extra, *dq = dq0 + rates;
+    if (dq_host) HIP_TRY(hipMemcpyAsync(dq0, dq_host, rates * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (int rc = tg_batch_project_constraints_device(b, s.q0, dq_host ? dq0 : nullptr, free_host ? s.mask : nullptr, tolerance, max_iterations,
+                                                     s.q, dq_host ? dq : nullptr, s.mu, s.iters, s.status)) return rc;
+    if (dq_out) HIP_TRY(hipMemcpyAsync(dq_out, dq, rates * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    return pose_stage_out(b, s, q_out, mu_out, iterations_out, status_out);
 }
 
 /* Team size, doubles of LDS per team and bytes of LDS per workgroup of the equilibrium kernel for this system (out[0..2]; out[3] 0):
@@ -1118,36 +1140,25 @@ int tg_system_equilibrium_lds(const tg_system *sys, int32_t out[4]) {
     if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
     tg::EquilibriumArgs J{};
     tg::equilibrium_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nc, J);
-    const long long bytes = (long long)(64 / sys->team) * J.lds_per_team * (long long)sizeof(double);
-    out[0] = sys->team; out[1] = J.lds_per_team; out[2] = (int32_t)std::min<long long>(bytes, 0x7fffffff); out[3] = 0;
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident equilibrium kernel", out);
     if (sys->H.p.n_ncs > 0) return fail(TG_ERR_UNSUPPORTED, "a NonlinearConfigSpring has a force but no potential energy (as in the reference): nothing to minimise");
-    if (bytes > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident equilibrium kernel");
-    return TG_SUCCESS;
+    return rc;
 }
 
 int tg_batch_minimize_potential_device(tg_batch *b, const double *q_dev, const int32_t *free_dev, double tolerance, int32_t max_iterations,
                                        double *q_out_dev, double *mu_out_dev, double *v_out_dev, int32_t *iterations_out_dev,
                                        int32_t *status_out_dev) {
-    if (!b || !q_dev || !q_out_dev) return fail(TG_ERR_INVALID, "null argument");
-    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
-    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    if (int rc = pose_check(b, q_dev, q_out_dev, tolerance, max_iterations)) return rc;
     int32_t geo[4];
     if (int rc = tg_system_equilibrium_lds(b->sys, geo)) return rc;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch;
-    HIP_TRY(b->equi_ints.ensure(b->P.nq + 2 * B));
-    // the pose is an argument of this call: nothing of the integrator (q1, q2, p, lambda1, status) is read or written.  A loaded
-    // specialised library has no say; a parameter table has (masses and gravity move an equilibrium; damping plays no part)
-    tg::RunArgs A = base_args(b, tg::MODE_EQUILIBRIUM);
-    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
-    A.tolerance = tolerance; A.max_iterations = max_iterations;
-    A.iters = iterations_out_dev ? iterations_out_dev : b->equi_ints.get() + b->P.nq;
-    A.status = status_out_dev ? status_out_dev : b->equi_ints.get() + b->P.nq + B;
+    // a parameter table has a say (masses and gravity move an equilibrium; damping plays no part)
+    tg::RunArgs A;
+    int grid;
+    if (int rc = pose_prepare(b, tg::MODE_EQUILIBRIUM, tolerance, max_iterations, iterations_out_dev, status_out_dev, A, grid)) return rc;
     tg::EquilibriumArgs J{};
     tg::equilibrium_layout(b->P.lds_per_team, b->P.nq, b->P.nc, J);
     J.free_mask = free_dev; J.q0 = q_dev; J.q = q_out_dev; J.mu = mu_out_dev; J.v = v_out_dev;
     const bool par = b->par_rows > 0;
-    const int per_block = 64 / b->sys->team, grid = (b->batch + per_block - 1) / per_block;
     int rc = tg_detail::launch_equilibrium(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
                                            tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0}, grid,
                                            (size_t)geo[2], b->stream);
@@ -1158,27 +1169,14 @@ int tg_batch_minimize_potential_device(tg_batch *b, const double *q_dev, const i
 
 int tg_batch_minimize_potential(tg_batch *b, const double *q_host, const int32_t *free_host, double tolerance, int32_t max_iterations,
                                 double *q_out, double *mu_out, double *v_out, int32_t *iterations_out, int32_t *status_out) {
-    if (!b || !q_host || !q_out) return fail(TG_ERR_INVALID, "null argument");
-    if (!(tolerance > 0.0)) return fail(TG_ERR_INVALID, "tolerance must be positive");
-    if (max_iterations < 0) return fail(TG_ERR_INVALID, "max_iterations must not be negative");
+    if (int rc = pose_check(b, q_host, q_out, tolerance, max_iterations)) return rc;
     int32_t geo[4];
     if (int rc = tg_system_equilibrium_lds(b->sys, geo)) return rc;
-    HIP_TRY(hipSetDevice(b->device));
-    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc;
-    HIP_TRY(b->equi.ensure(B * (2 * nq + nc + 2)));
-    HIP_TRY(b->equi_ints.ensure(nq + 2 * B));
-    double *q0 = b->equi.get(), *q = q0 + B * nq, *mu = q + B * nq, *v = mu + B * nc;
-    int *mask = b->equi_ints.get(), *iters = mask + nq, *status = iters + B;
-    HIP_TRY(hipMemcpyAsync(q0, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    if (free_host && nq) HIP_TRY(hipMemcpyAsync(mask, free_host, nq * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    if (int rc = tg_batch_minimize_potential_device(b, q0, free_host ? mask : nullptr, tolerance, max_iterations, q, mu, v, iters, status)) return rc;
-    HIP_TRY(hipMemcpyAsync(q_out, q, B * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (v_out) HIP_TRY(hipMemcpyAsync(v_out, v, B * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (iterations_out) HIP_TRY(hipMemcpyAsync(iterations_out, iters, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return TG_SUCCESS;
+    PoseStage s;
+    if (int rc = pose_stage_in(b, q_host, free_host, s)) return rc;
+    if (int rc = tg_batch_minimize_potential_device(b, s.q0, free_host ? s.mask : nullptr, tolerance, max_iterations, s.q, s.mu, s.extra, s.iters, s.status)) return rc;
+    if (v_out) HIP_TRY(hipMemcpyAsync(v_out, s.extra, (size_t)b->batch * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    return pose_stage_out(b, s, q_out, mu_out, iterations_out, status_out);
 }
 
 // z and hz in device memory; horizon > 0: only steps k_begin .. k_end - 1 of every seed of a seeds x horizon batch

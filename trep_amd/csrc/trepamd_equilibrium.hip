@@ -7,13 +7,8 @@
 // of its own so that it compiles beside trepamd.hip.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
+#include "launch_generic.hpp"
 #include "mvi_equilibrium.hpp"
-
-namespace tg_detail {
-int fail(int code, const std::string &msg);
-}
 
 namespace {
 
@@ -26,21 +21,6 @@ __global__ __launch_bounds__(64, 1) void k_equilibrium(const tg::DevProg *__rest
     tg::run_equilibrium<TEAM, SPRINGS, PAR>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, traj);
 }
 
-template <int TEAM, bool SPRINGS, bool PAR>
-int launch_variant(const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_equilibrium<TEAM, SPRINGS, PAR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return tg_detail::fail(TG_ERR_HIP, "hipFuncSetAttribute failed");
-    hipLaunchKernelGGL((k_equilibrium<TEAM, SPRINGS, PAR>), dim3(grid), dim3(64), lds, stream, d_prog, A, J, T);
-    return TG_SUCCESS;
-}
-
-template <int TEAM>
-int launch_team(bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
-    if (par) return springs ? launch_variant<TEAM, true, true>(d_prog, A, J, T, grid, lds, stream) : launch_variant<TEAM, false, true>(d_prog, A, J, T, grid, lds, stream);
-    return springs ? launch_variant<TEAM, true, false>(d_prog, A, J, T, grid, lds, stream) : launch_variant<TEAM, false, false>(d_prog, A, J, T, grid, lds, stream);
-}
-
 }  // namespace
 
 namespace tg_detail {
@@ -49,9 +29,12 @@ int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_pr
     (void)team; (void)springs; (void)par; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
     return fail(TG_ERR_UNSUPPORTED, "the profiling build has no equilibrium kernel");
 #else
-    return team == 64 ? launch_team<64>(springs, par, d_prog, A, J, T, grid, lds, stream)
-           : (team == 16 ? launch_team<16>(springs, par, d_prog, A, J, T, grid, lds, stream)
-              : (team == 4 ? launch_team<4>(springs, par, d_prog, A, J, T, grid, lds, stream) : launch_team<1>(springs, par, d_prog, A, J, T, grid, lds, stream)));
+    return dispatch_team(team, [&](auto team_tag) {
+        constexpr int TEAM = decltype(team_tag)::value;
+        auto kernel = par ? (springs ? &k_equilibrium<TEAM, true, true> : &k_equilibrium<TEAM, false, true>)
+                          : (springs ? &k_equilibrium<TEAM, true, false> : &k_equilibrium<TEAM, false, false>);
+        return launch_kernel(kernel, grid, lds, stream, d_prog, A, J, T);
+    });
 #endif
 }
 }  // namespace tg_detail

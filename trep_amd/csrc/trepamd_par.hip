@@ -5,13 +5,7 @@
 // geometry, LDS slice, launch bounds -- is its twin's.  A translation unit of its own so that it compiles beside trepamd.hip.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
-#include "mvi_core.hpp"
-
-namespace tg_detail {
-int fail(int code, const std::string &msg);
-}
+#include "launch_generic.hpp"
 
 namespace {
 
@@ -26,18 +20,9 @@ __global__ __launch_bounds__(64, (MODE == tg::MODE_DERIV1 || MODE == tg::MODE_DE
     tg::run_trajectory<TEAM, MODE, SPRINGS, tg::CProg, tg::CArgs, -1, true>(P, A, lds + (size_t)team * stride, lane, traj, 0, 1, T);
 }
 
-template <int TEAM, int MODE, bool SPRINGS>
-int launch_variant(const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_run_par<TEAM, MODE, SPRINGS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return tg_detail::fail(TG_ERR_HIP, "hipFuncSetAttribute failed");
-    hipLaunchKernelGGL((k_run_par<TEAM, MODE, SPRINGS>), dim3(grid), dim3(64), lds, stream, d_prog, A, T);
-    return TG_SUCCESS;
-}
-
 template <int TEAM, int MODE>
 int launch_one(bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
-    return springs ? launch_variant<TEAM, MODE, true>(d_prog, A, T, grid, lds, stream) : launch_variant<TEAM, MODE, false>(d_prog, A, T, grid, lds, stream);
+    return tg_detail::launch_kernel(springs ? &k_run_par<TEAM, MODE, true> : &k_run_par<TEAM, MODE, false>, grid, lds, stream, d_prog, A, T);
 }
 
 template <int TEAM>
@@ -64,9 +49,7 @@ int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunA
     (void)team; (void)springs; (void)d_prog; (void)A; (void)T; (void)grid; (void)lds; (void)stream;
     return fail(TG_ERR_UNSUPPORTED, "the profiling build has no per-trajectory parameter kernels");
 #else
-    return team == 64 ? launch_team<64>(springs, d_prog, A, T, grid, lds, stream)
-           : (team == 16 ? launch_team<16>(springs, d_prog, A, T, grid, lds, stream)
-              : (team == 4 ? launch_team<4>(springs, d_prog, A, T, grid, lds, stream) : launch_team<1>(springs, d_prog, A, T, grid, lds, stream)));
+    return dispatch_team(team, [&](auto team_tag) { return launch_team<decltype(team_tag)::value>(springs, d_prog, A, T, grid, lds, stream); });
 #endif
 }
 }  // namespace tg_detail

@@ -6,13 +6,8 @@
 // that it compiles beside trepamd.hip.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
+#include "launch_generic.hpp"
 #include "mvi_project.hpp"
-
-namespace tg_detail {
-int fail(int code, const std::string &msg);
-}
 
 namespace {
 
@@ -25,20 +20,6 @@ __global__ __launch_bounds__(64, 1) void k_project(const tg::DevProg *__restrict
     tg::run_project<TEAM, SPRINGS>(P, A, J, lds + (size_t)team * J.lds_per_team, lane, traj);
 }
 
-template <int TEAM, bool SPRINGS>
-int launch_variant(const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ProjectArgs &J, int grid, size_t lds, hipStream_t stream) {
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void *>(&k_project<TEAM, SPRINGS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return tg_detail::fail(TG_ERR_HIP, "hipFuncSetAttribute failed");
-    hipLaunchKernelGGL((k_project<TEAM, SPRINGS>), dim3(grid), dim3(64), lds, stream, d_prog, A, J);
-    return TG_SUCCESS;
-}
-
-template <int TEAM>
-int launch_team(bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ProjectArgs &J, int grid, size_t lds, hipStream_t stream) {
-    return springs ? launch_variant<TEAM, true>(d_prog, A, J, grid, lds, stream) : launch_variant<TEAM, false>(d_prog, A, J, grid, lds, stream);
-}
-
 }  // namespace
 
 namespace tg_detail {
@@ -47,9 +28,10 @@ int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::
     (void)team; (void)springs; (void)d_prog; (void)A; (void)J; (void)grid; (void)lds; (void)stream;
     return fail(TG_ERR_UNSUPPORTED, "the profiling build has no projection kernel");
 #else
-    return team == 64 ? launch_team<64>(springs, d_prog, A, J, grid, lds, stream)
-           : (team == 16 ? launch_team<16>(springs, d_prog, A, J, grid, lds, stream)
-              : (team == 4 ? launch_team<4>(springs, d_prog, A, J, grid, lds, stream) : launch_team<1>(springs, d_prog, A, J, grid, lds, stream)));
+    return dispatch_team(team, [&](auto team_tag) {
+        constexpr int TEAM = decltype(team_tag)::value;
+        return launch_kernel(springs ? &k_project<TEAM, true> : &k_project<TEAM, false>, grid, lds, stream, d_prog, A, J);
+    });
 #endif
 }
 }  // namespace tg_detail

@@ -503,6 +503,17 @@ class BatchMidpointVI(object):
             return np.array([0 if c.kinematic else 1 for c in configs], dtype=np.int32)
         return np.ones(len(configs), dtype=np.int32)
 
+    def _pose_call(self, Q, keep_kinematic, constant_q_list):
+        """What the pose solvers share before their call: the batch refreshed, Q broadcast to [B][nq], the free mask (None: every
+        config) and the outputs every one of them has.  Returns (Q, free, q, mu, iterations, status)."""
+        self.refresh()
+        B = self._batch
+        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
+        free = None if not (keep_kinematic or constant_q_list) else self.free_mask(keep_kinematic, constant_q_list)
+        q, mu = np.zeros((B, self.nq)), np.zeros((B, self.nc))
+        iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        return Q, free, q, mu, iters, status
+
     def satisfy_constraints(self, Q, dQ=None, tolerance=1e-10, keep_kinematic=False, constant_q_list=None, max_iterations=50):
         """System.satisfy_constraints (reference trep/system.py:158-214) for B poses in one launch: every Q[b] moves to the nearest
         pose (least squares over the free configs; the others keep their values) with h(q) = 0, by Newton on the KKT conditions
@@ -511,14 +522,10 @@ class BatchMidpointVI(object):
         None, [B][nc] multipliers, [B] Newton steps, [B] TG_OK / TG_NOT_CONVERGED (q = the last iterate) / TG_SINGULAR (q = the
         iterate before the rejected solve).  Nothing is raised for a trajectory that fails: look at status.  The system's own
         configuration and the integrator state of the batch are left alone."""
-        self.refresh()
+        Q, free, q, mu, iters, status = self._pose_call(Q, keep_kinematic, constant_q_list)
         B = self._batch
-        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
         dQ = None if dQ is None else _lib.as_f64(np.broadcast_to(np.asarray(dQ, dtype=float), (B, self.nq)), (B, self.nq))
-        free = None if not (keep_kinematic or constant_q_list) else self.free_mask(keep_kinematic, constant_q_list)
-        q, mu = np.zeros((B, self.nq)), np.zeros((B, self.nc))
         dq = None if dQ is None else np.zeros((B, self.nq))
-        iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
         _lib.check(self._L.tg_batch_project_constraints(self._h, _lib.ptr(Q), _lib.ptr(dQ), None if free is None else free.ctypes.data,
                                                         float(tolerance), int(max_iterations), _lib.ptr(q), _lib.ptr(dq), _lib.ptr(mu),
                                                         iters.ctypes.data, status.ctypes.data))
@@ -533,12 +540,8 @@ class BatchMidpointVI(object):
         returned pose, [B] trials, [B] TG_OK / TG_NOT_CONVERGED (q = the last accepted iterate) / TG_SINGULAR (the
         regularisation ran out).  Nothing is raised for a pose that fails: look at status.  The system's own configuration and
         the integrator state of the batch are left alone."""
-        self.refresh()
-        B = self._batch
-        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
-        free = None if not (keep_kinematic or constant_q_list) else self.free_mask(keep_kinematic, constant_q_list)
-        q, mu, v = np.zeros((B, self.nq)), np.zeros((B, self.nc)), np.zeros((B, 2))
-        iters, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        Q, free, q, mu, iters, status = self._pose_call(Q, keep_kinematic, constant_q_list)
+        v = np.zeros((self._batch, 2))
         _lib.check(self._L.tg_batch_minimize_potential(self._h, _lib.ptr(Q), None if free is None else free.ctypes.data, float(tolerance),
                                                        int(max_iterations), _lib.ptr(q), _lib.ptr(mu), _lib.ptr(v), iters.ctypes.data,
                                                        status.ctypes.data))
