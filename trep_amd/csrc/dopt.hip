@@ -4,10 +4,13 @@
 // One optimisation problem ("seed") = one trajectory X [N+1][nX], U [N][nU] with its linearisation
 // A [N][nX][nX], B [N][nX][nU].  The seed axis is the parallel axis: every kernel below runs one
 // workgroup per seed (the k axis of a Riccati / adjoint / tangent sweep is inherently serial), so
-// S seeds occupy S CUs; the dense nX x nX work of one seed is spread over the 256 lanes of its
-// workgroup with the matrices resident in LDS (P, A_k: 2 x 51 KB for the 40-DOF puppet, nX = 80).
-// MI355X has the same fp64 rate on the vector and the matrix pipes and the operands here are
-// 80 x 80 at most, so the products are register-tiled VALU code (4x4 tiles from LDS), not MFMA.
+// S seeds occupy S CUs; the dense nX x nX work of one seed is spread over the lanes of its workgroup
+// with the matrices resident in LDS (P, A_k: 2 x 51 KB for the 40-DOF puppet, nX = 80).
+// The LQ sweep and the cost exist twice: as register-tiled VALU code (k_tv_lq, k_cost: any size that
+// fits, and what TREPAMD_LQ_LEGACY / TREPAMD_COST_LEGACY select) and on the matrix cores
+// (k_tv_lq_mfma, k_tv_lq_ds, k_cost_mfma: v_mfma_f64_16x16x4_f64 over 16 x 16 tiles, nX <= 96), which
+// is what a call gets whenever its sizes allow; the gamma solvers of the two matrix-core sweeps are
+// in lq_solve.hpp.  lq_plan / tangent_plan below decide, on the host alone, which kernel a call runs.
 //
 // All entry points take DEVICE pointers and run on the device's default stream, which is ordered
 // with the (blocking) streams of the tg_batch objects.
@@ -18,14 +21,14 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "../../include/trep_amd.h"
+#include "lq_solve.hpp"
 
 namespace tg_detail {
 int fail(int code, const std::string &msg);
 }
-// ROCm device-library wavefront reduction (DPP based)
-extern "C" __device__ __attribute__((const)) unsigned int __ockl_wfred_max_u32(unsigned int);
 
 namespace {
 
@@ -348,378 +351,16 @@ __global__ __launch_bounds__(LQ_T) void k_tv_lq(const tg_lq_problem a) {
 //     16 x 16 output tiles (wave w owns tiles w, w+4, ...): two LDS reads feed 2048 flops instead of 5, and all
 //     operand reads are row segments of 16 consecutive doubles (P is symmetric, so P' rows serve as P columns;
 //     P B is stored instead of B'P for the same reason) -- no bank conflicts, no transposes;
-//   * the solve [C | K] = gamma^-1 [B'b + r | Kpart] runs in registers without a single barrier: each wavefront
-//     takes the nU columns of gamma plus its quarter of the 1 + nX right-hand-side columns, one column per lane,
-//     rows in registers; every wave repeats the (identical) pivot search on its own copy of gamma.  LAPACK's pivot
-//     rule (largest magnitude in the column, rows never move) as before.
+//   * the solve [C | K] = gamma^-1 [B'b + r | Kpart] runs in registers (lq_solve.hpp): the last wave factorises gamma,
+//     one row per lane, once per step (lq_factor_rows) while the others accumulate Q + A'(P A); then every wave
+//     replays the steps on its slice of the 1 + nX right-hand sides (lq_apply_rows).  LAPACK's pivot rule (largest
+//     magnitude in the column, rows never move) as before.
 // Same arithmetic up to summation order; tests/test_gpu_discopt_device.py holds both kernels to the numpy sweep.
 // ------------------------------------------------------------------------------------------------------
 typedef double v4d __attribute__((ext_vector_type(4)));
 
-// One wavefront: Gauss-Jordan on [gamma | its slice of the right-hand sides], one column per lane, NR >= nU rows in
-// registers.  G [nU][ldw] = [gamma | rhs(1 + nX)] is only READ (every wave loads gamma and its own slice); solutions go
-// to Cs [nU] (rhs 0) and Ks [nU][ldx] (rhs 1 + j), in variable order.  scr: 3 * NR doubles of per-wave LDS scratch.
-template <int NR>
-__device__ __forceinline__ void lq_gj_wave(const double *G_generic, int ldw, int nU, int rhs_lo, int rhs_n, double *Ks_generic, int ldx,
-                                        double *Cs_generic, double *scr_generic, int lane, int *sing) {
-    typedef __attribute__((address_space(3))) double lds_double;
-    const lds_double *G = (const lds_double *)G_generic;
-    lds_double *Ks = (lds_double *)Ks_generic, *Cs = (lds_double *)Cs_generic, *colbuf = (lds_double *)scr_generic, *dinv = colbuf + NR;
-    __attribute__((address_space(3))) int *var = (__attribute__((address_space(3))) int *)(colbuf + 2 * NR);
-    const bool is_rhs = lane >= nU && lane < nU + rhs_n;
-    const int gcol = lane < nU ? lane : nU + rhs_lo + (lane - nU);       // column of G this lane holds
-    const bool have = lane < nU || is_rhs;
-    double a[NR];
-#pragma unroll
-    for (int i = 0; i < NR; i++) a[i] = (have && i < nU) ? G[i * ldw + gcol] : 0.0;
-    unsigned int used = 0u;
-    bool ok = true;
-    for (int k = 0; k < nU; k++) {
-        if (lane == k) {
-#pragma unroll
-            for (int i = 0; i < NR; i++) colbuf[i] = a[i];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        float mf = 0.0f;
-        if (lane < nU && !((used >> lane) & 1u)) mf = (float)fabs(colbuf[lane]);
-        const unsigned int key = __ockl_wfred_max_u32((__float_as_uint(mf) & ~0x3Fu) | (unsigned int)(63 - lane));
-        const int r = __builtin_amdgcn_readfirstlane(63 - (int)(key & 0x3Fu));
-        if (!(__uint_as_float(key & ~0x3Fu) > 0.0f)) ok = false;
-        used |= 1u << r;
-        // the whole pivot column in registers first (wave-uniform addresses: LDS broadcasts, all in flight together); a
-        // load inside a `(i == r) ? ... : ...` arm becomes a scalar branch with its own s_waitcnt per row
-        double cb[NR];
-#pragma unroll
-        for (int i = 0; i < NR; i++) cb[i] = colbuf[i];
-        // this lane's pivot-row entry and the pivot: r is wave-uniform but not a compile-time register index.  A chain of
-        // uniform branches picks them (a 0/1-weighted FMA sum would be NR dependent fp64 FMAs, ~30 cycles each)
-        double p = 0.0, piv = 1.0;
-#pragma unroll
-        for (int i = 0; i < NR; i++) if (i == r) { p = a[i]; piv = cb[i]; }
-        double inv = __builtin_amdgcn_rcp(piv);            // seed + one cubic refinement: three dependent fp64 operations
-        { const double e = fma(-piv, inv, 1.0); inv = fma(inv, fma(e, e, e), inv); }
-        if (lane == 0) { var[r] = k; dinv[r] = inv; }
-        const double q = ok ? -(inv * p) : 0.0;    // a_i <- a_i - (c_i / pivot) p for the other rows
-#pragma unroll
-        for (int i = 0; i < NR; i++) {
-            const double upd = fma(cb[i], q, a[i]);
-            a[i] = (i == r) ? a[i] : upd;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    if (!ok && lane == 0) *sing = 1;
-    if (is_rhs) {
-        const int g = rhs_lo + (lane - nU);
-#pragma unroll
-        for (int i = 0; i < NR; i++) {
-            if (i < nU) {
-                const int v = var[i];
-                const double x = a[i] * dinv[i];
-                if (g == 0) Cs[v] = x; else Ks[v * ldx + g - 1] = x;
-            }
-        }
-    }
-}
-
-// The same solve with one matrix ROW per lane (lanes 0 .. NR-1) and the columns in registers: NR columns of gamma plus SL right-hand-side
-// columns of this wave's slice.  A pivot step is then: one 32-lane DPP max over |a_ik| (LAPACK's rule: largest magnitude of the
-// column among the rows not used yet; near ties within 2^-17 go to the lower row), the pivot row broadcast with v_readlane (two
-// entries ahead of their two FMAs), one FMA per remaining column -- no LDS traffic, no dynamic register index (the column-per-lane
-// variant above needs the pivot ROW out of a register array and pays ~2.3 k cycles per step for it).  Rows / columns nU .. NR-1 are
-// an identity block, so all NR steps run without a branch on nU.  ~4x faster than lq_gj_wave on the 18 x 18 puppet systems.
-template <int NR, int SL>
-__device__ __forceinline__ void lq_gj_rows(const double *G_generic, int ldw, int nU, int rhs_lo, int rhs_n, double *Ks_generic, int ldx,
-                                           double *Cs_generic, int lane, int *sing) {
-    typedef __attribute__((address_space(3))) double lds_double;
-    const lds_double *G = (const lds_double *)G_generic;
-    lds_double *Ks = (lds_double *)Ks_generic, *Cs = (lds_double *)Cs_generic;
-    const bool mine = lane < nU, ident = lane >= nU && lane < NR;
-    double m[NR], b[SL];
-#pragma unroll
-    for (int j = 0; j < NR; j++) m[j] = mine ? (j < nU ? G[lane * ldw + j] : 0.0) : ((ident && j == lane) ? 1.0 : 0.0);
-#pragma unroll
-    for (int c = 0; c < SL; c++) b[c] = (mine && c < rhs_n) ? G[lane * ldw + nU + rhs_lo + c] : 0.0;
-    int mycol = -1;
-    double diag = 1.0;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NR; k++) {
-        const bool free_row = (mine || ident) && mycol < 0;
-        const float cand = free_row ? (float)fabs(m[k]) : 0.0f;
-        unsigned int key = (__float_as_uint(cand) & ~0x3Fu) | (unsigned int)(63 - lane);
-        // max over each 16-lane row (DPP row_shr 1, 2, 4, 8), then over the two rows that hold matrix rows
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x111, 0xf, 0xf, true));
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x112, 0xf, 0xf, true));
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x114, 0xf, 0xf, true));
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x118, 0xf, 0xf, true));
-        const unsigned int best = max((unsigned int)__builtin_amdgcn_readlane((int)key, 15), (unsigned int)__builtin_amdgcn_readlane((int)key, 31));
-        const int src = 63 - (int)(best & 0x3Fu);
-        if (!(__uint_as_float(best & ~0x3Fu) > 0.0f)) ok = false;
-        auto bcast = [&](double v) -> double {
-            const long long w = __double_as_longlong(v);
-            const int lo = __builtin_amdgcn_readlane((int)(w & 0xFFFFFFFFLL), src), hi = __builtin_amdgcn_readlane((int)(w >> 32), src);
-            return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-        };
-        const bool is_piv = lane == src;
-        const double piv = bcast(m[k]);
-        double inv = __builtin_amdgcn_rcp(piv);            // seed + one cubic refinement (the multipliers need not be correctly rounded)
-        { const double e = fma(-piv, inv, 1.0); inv = fma(inv, fma(e, e, e), inv); }
-        const double l = (ok && !is_piv) ? m[k] * inv : 0.0;
-#pragma unroll
-        for (int j = k + 1; j < NR; j += 2) {
-            const double p0 = bcast(m[j]), p1 = bcast(m[j + 1 < NR ? j + 1 : j]);
-            m[j] = fma(-l, p0, m[j]);
-            if (j + 1 < NR) m[j + 1] = fma(-l, p1, m[j + 1]);
-        }
-#pragma unroll
-        for (int c = 0; c < SL; c += 2) {
-            const double p0 = bcast(b[c]), p1 = bcast(b[c + 1 < SL ? c + 1 : c]);
-            b[c] = fma(-l, p0, b[c]);
-            if (c + 1 < SL) b[c + 1] = fma(-l, p1, b[c + 1]);
-        }
-        if (is_piv) { mycol = k; diag = m[k]; }
-    }
-    if (!ok && lane == 0) *sing = 1;
-    if (mine && mycol >= 0 && mycol < nU) {       // row `lane` was the pivot of variable mycol: its right-hand sides / pivot are that variable's solution
-        const double dinv = 1.0 / diag;
-#pragma unroll
-        for (int c = 0; c < SL; c++) {
-            if (c < rhs_n) {
-                const int g = rhs_lo + c;
-                const double x = b[c] * dinv;
-                if (g == 0) Cs[mycol] = x; else Ks[mycol * ldx + g - 1] = x;
-            }
-        }
-    }
-}
-
-// The same elimination in two parts, so that the 18 dependent pivot steps (search -> reciprocal -> multipliers) are done ONCE per Riccati
-// step instead of once per wavefront.  lq_factor_rows: the matrix alone (one row per lane): pivot lane and multipliers of every step go to
-// LDS -- the multiplier of (row i, step k) over the dead entry G[i][k], the pivot lanes / solved columns / reciprocal pivots to `fac`
-// (32 doubles dinv | 32 ints solved column per row | NR ints pivot lane per step).  lq_apply_rows: a wave replays the steps on its slice of
-// right-hand sides: per step one multiplier read, and per column two v_readlane + one FMA.  Same operations in the same order per column
-// as lq_gj_rows: the results are bit-identical.
-template <int NR>
-__device__ __forceinline__ void lq_factor_rows(double *G_generic, int ldw, int nU, int lane, double *fac_generic, int *sing) {
-    typedef __attribute__((address_space(3))) double lds_double;
-    typedef __attribute__((address_space(3))) int lds_int;
-    lds_double *G = (lds_double *)G_generic, *dinv_s = (lds_double *)fac_generic;
-    lds_int *col_s = (lds_int *)(dinv_s + 32), *piv_s = col_s + 32;
-    const bool mine = lane < nU, ident = lane >= nU && lane < NR;
-    double m[NR];
-#pragma unroll
-    for (int j = 0; j < NR; j++) m[j] = mine ? (j < nU ? G[lane * ldw + j] : 0.0) : ((ident && j == lane) ? 1.0 : 0.0);
-    int mycol = -1;
-    double diag = 1.0;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < NR; k++) if (k < nU) {      // (steps nU .. NR-1 are the identity block: they change nothing; a uniform branch per unrolled step)
-        const bool free_row = (mine || ident) && mycol < 0;
-        const float cand = free_row ? (float)fabs(m[k]) : 0.0f;
-        unsigned int key = (__float_as_uint(cand) & ~0x3Fu) | (unsigned int)(63 - lane);
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x111, 0xf, 0xf, true));
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x112, 0xf, 0xf, true));
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x114, 0xf, 0xf, true));
-        key = max(key, (unsigned int)__builtin_amdgcn_update_dpp(0, (int)key, 0x118, 0xf, 0xf, true));
-        const unsigned int best = max((unsigned int)__builtin_amdgcn_readlane((int)key, 15), (unsigned int)__builtin_amdgcn_readlane((int)key, 31));
-        const int src = 63 - (int)(best & 0x3Fu);
-        if (!(__uint_as_float(best & ~0x3Fu) > 0.0f)) ok = false;
-        auto bcast = [&](double v) -> double {
-            const long long w = __double_as_longlong(v);
-            const int lo = __builtin_amdgcn_readlane((int)(w & 0xFFFFFFFFLL), src), hi = __builtin_amdgcn_readlane((int)(w >> 32), src);
-            return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-        };
-        const bool is_piv = lane == src;
-        const double piv = bcast(m[k]);
-        double inv = __builtin_amdgcn_rcp(piv);
-        { const double e = fma(-piv, inv, 1.0); inv = fma(inv, fma(e, e, e), inv); }
-        const double l = (ok && !is_piv) ? m[k] * inv : 0.0;
-#pragma unroll
-        for (int j = k + 1; j < NR; j += 2) {
-            const double p0 = bcast(m[j]), p1 = bcast(m[j + 1 < NR ? j + 1 : j]);
-            m[j] = fma(-l, p0, m[j]);
-            if (j + 1 < NR) m[j + 1] = fma(-l, p1, m[j + 1]);
-        }
-        if (is_piv) { mycol = k; diag = m[k]; }
-        if (mine) G[lane * ldw + k] = l;
-        if (lane == 0) piv_s[k] = src;
-    }
-    if (!ok && lane == 0) *sing = 1;
-    if (lane < 32) { col_s[lane] = mycol; dinv_s[lane] = 1.0 / diag; }
-}
-
-// gamma = R_k + B'PB is symmetric and, with a positive definite R_k, positive definite: it can be eliminated in index order without a
-// pivot search.  Same layout as lq_factor_rows (one row per lane, the columns in registers) with the pivot of step k taken from lane k:
-// the broadcasts are v_readlane with a constant lane, and the per-step chain is reciprocal -> multiplier -> first FMA instead of
-// candidate -> four DPP maxima -> two v_readlane -> v_readfirstlane -> reciprocal -> ...  (the pivoted factorisation is ~20 k cycles of
-// the ~70 k of a Riccati step, executed by one wave while seven wait at the barrier).  Every pivot is guarded -- |pivot| must exceed
-// 2^-20 of the largest entry of its row (the Newton model's R_k + HZ_uu can be indefinite far from the optimum) -- and nothing is
-// written before all guards have passed: on failure the caller runs lq_factor_rows on the untouched matrix.  Writes the same tables as
-// lq_factor_rows (pivot lane of step k = k, row i solves column i), so lq_apply_rows replays it unchanged.
-template <int NR>
-__device__ __forceinline__ bool lq_factor_rows_spd(double *G_generic, int ldw, int nU, int lane, double *fac_generic) {
-    typedef __attribute__((address_space(3))) double lds_double;
-    typedef __attribute__((address_space(3))) int lds_int;
-    lds_double *G = (lds_double *)G_generic, *dinv_s = (lds_double *)fac_generic;
-    lds_int *col_s = (lds_int *)(dinv_s + 32), *piv_s = col_s + 32;
-    const bool mine = lane < nU, ident = lane >= nU && lane < NR;
-    double m[NR], amax = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; j++) {
-        m[j] = mine ? (j < nU ? G[lane * ldw + j] : 0.0) : ((ident && j == lane) ? 1.0 : 0.0);
-        amax = fmax(amax, fabs(m[j]));
-    }
-    const double guard = 9.5367431640625e-07 * amax;   // 2^-20 of the row's largest entry
-    double myinv = 1.0;
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < NR; k++) if (k < nU) {
-        auto bcast = [&](double v) -> double {
-            const long long w = __double_as_longlong(v);
-            const int lo = __builtin_amdgcn_readlane((int)(w & 0xFFFFFFFFLL), k), hi = __builtin_amdgcn_readlane((int)(w >> 32), k);
-            return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-        };
-        const bool is_piv = lane == k;
-        bad = bad || (is_piv && !(fabs(m[k]) > guard));
-        const double piv = bcast(m[k]);
-        double inv = __builtin_amdgcn_rcp(piv);
-        { const double e = fma(-piv, inv, 1.0); inv = fma(inv, fma(e, e, e), inv); }
-        const double l = is_piv ? 0.0 : m[k] * inv;
-#pragma unroll
-        for (int j = k + 1; j < NR; j += 2) {
-            const double p0 = bcast(m[j]), p1 = bcast(m[j + 1 < NR ? j + 1 : j]);
-            m[j] = fma(-l, p0, m[j]);
-            if (j + 1 < NR) m[j + 1] = fma(-l, p1, m[j + 1]);
-        }
-        myinv = is_piv ? inv : myinv;
-        m[k] = is_piv ? m[k] : l;           // column k is dead below and above the pivot: keep the multiplier there
-    }
-    if (__any(bad ? 1 : 0)) return false;
-    if (mine) {
-#pragma unroll
-        for (int k = 0; k < NR; k++) if (k < nU) G[lane * ldw + k] = lane == k ? 0.0 : m[k];
-    }
-    if (lane < nU) piv_s[lane] = lane;
-    if (lane < 32) { col_s[lane] = lane < nU ? lane : -1; dinv_s[lane] = myinv; }
-    return true;
-}
-
-// The same unpivoted factorisation with TWO matrix rows per lane (rows 2 i and 2 i + 1 in lane i < NR / 2 <= 16): the pivot row of step k then sits
-// in lane k / 2 of the first 16-lane DPP row, and the elimination is `v_fmac_f64_dpp ... row_newbcast:k/2` -- one instruction per (row, column)
-// instead of two v_readlane + one FMA, no SGPR hazards.  And it leaves gamma^-1 itself (in-place Gauss-Jordan inversion, over gamma in G) instead of
-// the multipliers: the replay of the elimination on the 1 + nX right-hand sides -- 18 steps of two v_readlane + one FMA per column on 18 of 64
-// lanes, the longest phase of the step (17 k cycles) -- becomes a product gamma^-1 [r | Kpart] on the matrix cores (lq_apply_inverse).  Same guards
-// as lq_factor_rows_spd; nothing is written unless all of them passed (the caller then falls back to the pivoted factorisation + replay).
-template <int L>
-__device__ __forceinline__ double lq_bcast16(double v) {
-    return __longlong_as_double(__builtin_amdgcn_update_dpp((long long)0, __double_as_longlong(v), 0x150 + L, 0xf, 0xf, true));
-}
-template <int L>
-__device__ __forceinline__ void lq_fmac16(double &a, double b, double c) {      // a += (lane L's b) * c
-    asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(a) : "v"(b), "v"(c), "n"(L));
-}
-template <int K, int NR>
-__device__ __forceinline__ void lq_spd2_steps(double (&m0)[NR], double (&m1)[NR], int lane, int nU, double &inv0, double &inv1) {
-    if constexpr (K < NR) {
-        if (K < nU) {      // (uniform)
-            constexpr int L = K >> 1;
-            constexpr bool ODD = (K & 1) != 0;
-            const double piv = lq_bcast16<L>(ODD ? m1[K] : m0[K]);
-            double inv = __builtin_amdgcn_rcp(piv);
-            { const double e = fma(-piv, inv, 1.0); inv = fma(inv, fma(e, e, e), inv); }
-            const bool pl = lane == L;
-            double n0 = -(m0[K] * inv), n1 = -(m1[K] * inv);      // minus the multipliers of the lane's two rows
-            if (ODD) { n1 = pl ? 0.0 : n1; inv1 = pl ? inv : inv1; } else { n0 = pl ? 0.0 : n0; inv0 = pl ? inv : inv0; }
-            // IN-PLACE Gauss-Jordan inversion: column K of the matrix is dead after this step and becomes column K of the inverse's
-            // numerator (pivot row: 1, other rows: minus their multiplier); the columns j < K already are such columns and are updated
-            // like the live matrix columns j > K
-#pragma unroll
-            for (int j = 0; j < NR; j++) {
-                if (j == K) continue;
-                if (ODD) { lq_fmac16<L>(m0[j], m1[j], n0); lq_fmac16<L>(m1[j], m1[j], n1); }
-                else { lq_fmac16<L>(m1[j], m0[j], n1); lq_fmac16<L>(m0[j], m0[j], n0); }
-            }
-            m0[K] = (!ODD && pl) ? 1.0 : n0; m1[K] = (ODD && pl) ? 1.0 : n1;
-        }
-        lq_spd2_steps<K + 1, NR>(m0, m1, lane, nU, inv0, inv1);
-    }
-}
-template <int NR>
-__device__ __forceinline__ bool lq_factor_rows_spd2(double *G_generic, int ldw, int nU, int lane, double *fac_generic) {
-    static_assert(NR % 2 == 0 && NR <= 32, "two rows per lane on one 16-lane DPP row");
-    typedef __attribute__((address_space(3))) double lds_double;
-    typedef __attribute__((address_space(3))) int lds_int;
-    lds_double *G = (lds_double *)G_generic, *dinv_s = (lds_double *)fac_generic;
-    lds_int *col_s = (lds_int *)(dinv_s + 32), *piv_s = col_s + 32;
-    const int r0 = 2 * (lane & 15), r1 = r0 + 1;
-    const bool have = lane < NR / 2, in0 = have && r0 < nU, in1 = have && r1 < nU;
-    double m0[NR], m1[NR], a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int j = 0; j < NR; j++) {
-        const double x0 = G[(in0 ? r0 : 0) * ldw + (j < nU ? j : 0)], x1 = G[(in1 ? r1 : 0) * ldw + (j < nU ? j : 0)];
-        m0[j] = (in0 && j < nU) ? x0 : ((have && !in0 && j == r0) ? 1.0 : 0.0);
-        m1[j] = (in1 && j < nU) ? x1 : ((have && !in1 && j == r1) ? 1.0 : 0.0);
-        a0 = fmax(a0, fabs(m0[j])); a1 = fmax(a1, fabs(m1[j]));
-    }
-    double inv0 = 0.0, inv1 = 0.0;
-    lq_spd2_steps<0, NR>(m0, m1, lane, nU, inv0, inv1);
-    // the guards: |pivot| > 2^-20 of the row's largest entry, from the reciprocal kept by each row (a zero pivot gives inf / NaN: fails)
-    const bool bad = (in0 && !(fabs(inv0) * (9.5367431640625e-07 * a0) < 1.0)) || (in1 && !(fabs(inv1) * (9.5367431640625e-07 * a1) < 1.0));
-    if (__any(bad ? 1 : 0)) return false;
-#pragma unroll
-    for (int k = 0; k < NR; k++) if (k < nU) {      // gamma^-1 [row][k] = numerator / pivot of the row
-        if (in0) G[r0 * ldw + k] = m0[k] * inv0;
-        if (in1) G[r1 * ldw + k] = m1[k] * inv1;
-    }
-    (void)piv_s; (void)col_s; (void)dinv_s;
-    return true;
-}
-
-template <int NR, int SL>
-__device__ __forceinline__ void lq_apply_rows(const double *G_generic, int ldw, int nU, int rhs_lo, int rhs_n, double *Ks_generic, int ldx,
-                                              double *Cs_generic, int lane, const double *fac_generic) {
-    typedef __attribute__((address_space(3))) double lds_double;
-    typedef __attribute__((address_space(3))) int lds_int;
-    const lds_double *G = (const lds_double *)G_generic, *dinv_s = (const lds_double *)fac_generic;
-    const lds_int *col_s = (const lds_int *)(dinv_s + 32), *piv_s = col_s + 32;
-    lds_double *Ks = (lds_double *)Ks_generic, *Cs = (lds_double *)Cs_generic;
-    const bool mine = lane < nU;
-    double b[SL];
-#pragma unroll
-    for (int c = 0; c < SL; c++) b[c] = (mine && c < rhs_n) ? G[lane * ldw + nU + rhs_lo + c] : 0.0;
-    for (int k = 0; k < nU; k++) {
-        const int src = __builtin_amdgcn_readfirstlane(piv_s[k]);
-        const double l = mine ? G[lane * ldw + k] : 0.0;
-        auto bcast = [&](double v) -> double {
-            const long long w = __double_as_longlong(v);
-            const int lo = __builtin_amdgcn_readlane((int)(w & 0xFFFFFFFFLL), src), hi = __builtin_amdgcn_readlane((int)(w >> 32), src);
-            return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-        };
-#pragma unroll
-        for (int c = 0; c < SL; c += 2) {
-            const double p0 = bcast(b[c]), p1 = bcast(b[c + 1 < SL ? c + 1 : c]);
-            b[c] = fma(-l, p0, b[c]);
-            if (c + 1 < SL) b[c + 1] = fma(-l, p1, b[c + 1]);
-        }
-    }
-    const int mycol = lane < 32 ? col_s[lane] : -1;
-    if (mine && mycol >= 0 && mycol < nU) {
-        const double dinv = dinv_s[lane];
-#pragma unroll
-        for (int c = 0; c < SL; c++) {
-            if (c < rhs_n) {
-                const int g = rhs_lo + c;
-                const double x = b[c] * dinv;
-                if (g == 0) Cs[mycol] = x; else Ks[mycol * ldx + g - 1] = x;
-            }
-        }
-    }
-}
-
 struct LqLayout {   // LDS layout of k_tv_lq_mfma in doubles
-    int ldx, nUp, ldw, Pm, Am, Bm, Kp, Ks, G, bv, bn, wv, rv, scr, fac, total;
+    int ldx, nUp, ldw, Pm, Am, Bm, Kp, Ks, G, bv, bn, wv, rv, fac, total;
     __host__ __device__ LqLayout(int nX, int nU) {
         ldx = round_up(nX, 16); nUp = round_up(nU, 4); ldw = nU + 1 + ldx;
         int o = 0;
@@ -727,14 +368,15 @@ struct LqLayout {   // LDS layout of k_tv_lq_mfma in doubles
         Kp = o; o += nUp * ldx;
         Ks = o; o += (nUp * ldx > ldx * nUp ? nUp * ldx : ldx * nUp);   // K_k [nUp][ldx]; before the solve: P B [ldx][nUp]
         G = o; o += nU * ldw; bv = o; o += ldx; bn = o; o += ldx; wv = o; o += nUp; rv = o; o += nUp;
-        scr = o; o += nU > 32 ? (LQM_T / 64) * 3 * round_up(nU, 4) : 0;     // scratch of lq_gj_wave (more than 32 inputs) only
-        fac = o; o += nU <= 32 ? 32 + 16 + 16 : 0;                          // lq_factor_rows: reciprocal pivots, solved column per row, pivot lane per step
+        fac = o; o += nU <= tg::LqFac::ROWS ? tg::LqFac::SIZE : 0;          // what lq_factor_rows leaves for lq_apply_rows
         total = o;
     }
 };
 
 template <int NT, int NR>   // 16 x 16 tiles per dimension: nX <= 16 NT; rows of the input solve in registers: nU <= NR
 __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
+    static_assert(NR <= 32, "the last wave factorises gamma with one row per lane of 32 (lq_plan sends more inputs to k_tv_lq)");
+#if defined(__HIP_DEVICE_COMPILE__)     // (the solvers of lq_solve.hpp exist in the device pass only)
     extern __shared__ double lds[];
     __shared__ int s_sing;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
@@ -744,7 +386,7 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
     constexpr int ldx = 16 * NT, NTILES = NT * NT, NW = LQM_T / 64, TMAX = (NTILES + NW - 1) / NW;
     const int nUp = L.nUp, ldw = L.ldw, NUT = (nU + 15) >> 4;
     double *Pm = lds + L.Pm, *Am = lds + L.Am, *Bm = lds + L.Bm, *Kp = lds + L.Kp, *Ks = lds + L.Ks, *PB = Ks, *G = lds + L.G;
-    double *bv = lds + L.bv, *bn = lds + L.bn, *wv = lds + L.wv, *rv = lds + L.rv, *scr = lds + L.scr + wave * 3 * NR, *fac = lds + L.fac;
+    double *bv = lds + L.bv, *bn = lds + L.bn, *wv = lds + L.wv, *rv = lds + L.rv, *fac = lds + L.fac;
     for (int i = tid; i < L.total; i += LQM_T) lds[i] = 0.0;
     if (tid == 0) s_sing = 0;
     __syncthreads();
@@ -866,8 +508,7 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
         // The upper-triangle tiles of the new P that this wave owns (phases 3 / 4).  (Loading their weights Q_k here, a phase early, takes the
         // load latency off the tile chains -- 16.5 k -> 7 k cycles -- but the factorising wave needs ~20 k anyway, and the accumulators live
         // through phase 2b cost phase 1 its registers: 38.4 instead of 35.6 us per step.)
-        constexpr bool SPLIT = NR <= 32;
-        constexpr int NTRI = NT * (NT + 1) / 2, TW = SPLIT ? NW - 1 : NW, TSYM = (NTRI + TW - 1) / TW;
+        constexpr int NTRI = NT * (NT + 1) / 2, TW = NW - 1, TSYM = (NTRI + TW - 1) / TW;      // (the last wave factorises gamma meanwhile)
         static_assert(TSYM <= TMAX, "accumulator array too small for the upper-triangle tiles");
         const double *Qk = a.Q_dev + (size_t)s * a.Q_seed_stride + (size_t)k * a.Q_step_stride;
         int ti_[TMAX], tj_[TMAX];
@@ -920,10 +561,10 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
         LQ_STAMP(1);
         // ---- phase 3 / 4 ----------------------------------------------------------------------------------------------------
         // The new P tiles = Q + A'(P A) - Kpart' K are symmetric (Q_k, A'(P A) with symmetric P, Kpart' gamma^-1 Kpart): only the
-        // NT (NT + 1) / 2 tiles on and above the diagonal are computed, phase 6 mirrors them.  Up to 32 inputs: the LAST wave factorises
+        // NT (NT + 1) / 2 tiles on and above the diagonal are computed, phase 6 mirrors them.  The LAST wave factorises
         // gamma (lq_factor_rows: the 18 dependent pivot steps once per step, not once per wave) WHILE the other waves accumulate
         // Q + A'(P A) -- that part does not need the gains --; then every wave replays the steps on its slice of the right-hand
-        // sides (lq_apply_rows) and the tile owners add -Kpart' K.  More inputs: every wave solves its slice itself (lq_gj_wave).
+        // sides (lq_apply_rows) and the tile owners add -Kpart' K.
         auto tiles_q_apa = [&]() {      // acc = Q_k (+ curvature) + A'(P A)
 #pragma unroll
             for (int i = 0; i < TMAX; i++) {
@@ -964,23 +605,14 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
             }
         };
         const int lo = wave * slice, nrhs = lo < rhs_total ? (rhs_total - lo < slice ? rhs_total - lo : slice) : 0;
-        if constexpr (SPLIT) {
-            if (wave == NW - 1) lq_factor_rows<NR>(G, ldw, nU, lane, fac, &s_sing);
-            else tiles_q_apa();
-            LQ_STAMP(6);
-            for (int o = tid; o < (nUp - nU) * ldx; o += LQM_T) Ks[nU * ldx + o] = 0.0;   // padding rows (the buffer held P B)
-            __syncthreads();
-            lq_apply_rows<NR, (16 * NT + 1 + NW - 1) / NW>(G, ldw, nU, lo, nrhs, Ks, ldx, wv, lane, fac);
-            __syncthreads();
-            LQ_STAMP(2);
-        } else {
-            lq_gj_wave<NR>(G, ldw, nU, lo, nrhs, Ks, ldx, wv, scr, lane, &s_sing);
-            LQ_STAMP(6);
-            for (int o = tid; o < (nUp - nU) * ldx; o += LQM_T) Ks[nU * ldx + o] = 0.0;   // padding rows (the buffer held P B)
-            __syncthreads();
-            LQ_STAMP(2);
-            tiles_q_apa();
-        }
+        if (wave == NW - 1) tg::lq_factor_rows<NR>(G, ldw, nU, lane, fac, &s_sing);
+        else tiles_q_apa();
+        LQ_STAMP(6);
+        for (int o = tid; o < (nUp - nU) * ldx; o += LQM_T) Ks[nU * ldx + o] = 0.0;   // padding rows (the buffer held P B)
+        __syncthreads();
+        tg::lq_apply_rows<NR, (16 * NT + 1 + NW - 1) / NW>(G, ldw, nU, lo, nrhs, Ks, ldx, wv, lane, fac);
+        __syncthreads();
+        LQ_STAMP(2);
         double *Cs = wv;
         {   // outputs K_k, C_k
             double *Ko = a.K_dev + (sN + k) * (size_t)nU * nX;
@@ -1035,6 +667,7 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
     if (a.P0_dev) for (int e = tid; e < nX * nX; e += LQM_T) a.P0_dev[(size_t)s * nX * nX + e] = Pm[(e / nX) * ldx + e % nX];
     if (a.b0_dev && affine) for (int i = tid; i < nX; i += LQM_T) a.b0_dev[(size_t)s * nX + i] = bv[i];
     if (a.status_dev && tid == 0) a.status_dev[s] = (s_sing || (a.Pt_dev && a.status_dev[s] != TG_OK)) ? TG_SINGULAR : TG_OK;      // (a later chunk of a chunked sweep keeps an earlier chunk's verdict)
+#endif
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1052,7 +685,9 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_mfma(const tg_lq_problem a) {
 //     kernel holds A_{k-1}, B_{k-1} in 40 VGPRs through the whole step and is the worse for it: 67 spilled VGPRs) and no commit pass;
 //     B_k is dead after the gamma / Kpart tiles and is refilled in place the same way; inside a step the barriers only order LDS
 //     traffic (no vmcnt wait: the loads of step k-1 have the whole of step k to land), the step's last barrier waits for them;
-//   * gamma = R_k + B'PB is factorised without a pivot search (lq_factor_rows_spd), the pivoted factorisation being the fallback;
+//   * gamma = R_k + B'PB is inverted in place without a pivot search (lq_factor_rows_spd2) and the gains are a matrix-core product
+//     (the inverse product in phase 4); if a pivot guard fails, the pivoted factorisation and its replay (lq_factor_rows, lq_apply_rows) take over
+//     for that step (lq_factor_call leaves the choice in the table's flag, LqFac::FORM);
 //   * Kpart is kept once, as the right-hand-side block of G.
 // Same arithmetic otherwise (the products sum the same non-zero terms in compact-row order).
 // ------------------------------------------------------------------------------------------------------
@@ -1071,7 +706,7 @@ struct LqDsLayout {
         Ks = o; o += nUp * ldx;                                             // K_k [nUp][ldx]; before the solve: P B [ldx][nUp]
         G = o; o += nUp * ldw;
         bv = o; o += ldx; bn = o; o += ldx; wv = o; o += nUp; rv = o; o += nUp; rn = o; o += nUp;
-        fac = o; o += 32 + 16 + 16 + 2;      // (+ the form flag of lq_factor_call)
+        fac = o; o += tg::LqFac::SIZE_WITH_FORM;
         total = o;
     }
 };
@@ -1080,25 +715,6 @@ struct LqDsLayout {
 // global_load_lds fills in flight (they write LDS, so the compiler counts them in: s_waitcnt vmcnt(0) -- ~8 k cycles at the first
 // barrier after their issue); those land in the OTHER buffer and are awaited by the step's last barrier (__syncthreads).
 #define LQ_LDS_SYNC() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-// (the pivoted fallback as a call of its own: its code is only fetched when a guard failed)
-template <int NR>
-__device__ __noinline__ void lq_factor_pivoted_call(double *G, int ldw, int nU, int lane, double *fac, int *sing) {
-    ldw = __builtin_amdgcn_readfirstlane(ldw); nU = __builtin_amdgcn_readfirstlane(nU);
-    lq_factor_rows<NR>(G, ldw, nU, lane, fac, sing);
-}
-
-// gamma's factorisation as a CALL: one wave of eight runs it, and inlined its 2 x 20 matrix registers (unpivoted attempt + pivoted fallback)
-// are part of the sweep kernel's register allocation (158 spilled VGPRs)
-template <int NR>
-__device__ __noinline__ void lq_factor_call(double *G, int ldw, int nU, int lane, double *fac, int *sing) {
-    // (arguments of a call travel in vector registers: say that the sizes are wave-uniform, or every `k < nU` becomes a divergent branch)
-    ldw = __builtin_amdgcn_readfirstlane(ldw); nU = __builtin_amdgcn_readfirstlane(nU);
-    // fac[64] (as an int): 1 = G's gamma block holds gamma^-1 (lq_apply_inverse), 0 = the multipliers of the pivoted factorisation (lq_apply_rows)
-    const bool inverse = lq_factor_rows_spd2<NR>(G, ldw, nU, lane, fac);
-    if (!inverse) lq_factor_pivoted_call<NR>(G, ldw, nU, lane, fac, sing);
-    if (lane == 0) *reinterpret_cast<int *>(fac + 64) = inverse ? 1 : 0;
-}
 
 // Launch arguments re-read per phase: the struct sits at the head of the kernel-argument segment; reading it through a laundered
 // constant-address-space pointer at the head of every phase keeps its ~40 scalars -- and everything derived from them -- from being
@@ -1154,6 +770,7 @@ __device__ __forceinline__ KLq &lq_fresh_args() {
 
 template <int NT, int NR>
 __global__ __launch_bounds__(LQM_T) void k_tv_lq_ds(const tg_lq_problem a0) {
+#if defined(__HIP_DEVICE_COMPILE__)     // (as in k_tv_lq_mfma)
     extern __shared__ double lds[];
     __shared__ int s_sing;
     typedef __attribute__((address_space(3))) void lds_void;
@@ -1409,7 +1026,7 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_ds(const tg_lq_problem a0) {
         }
         {   // ---- phase 3: wave 0 factorises gamma while the others accumulate Q_k + A'(P A) on the upper-triangle tiles --------------
             LQ_DS_PHASE;
-            if (wave == 0) lq_factor_call<NR>(G, ldw, nU, lane, fac, &s_sing);
+            if (wave == 0) tg::lq_factor_call<NR>(G, ldw, nU, lane, fac, &s_sing);
             else if (wave != 4) {
                 const double *Qk = a.Q_dev + (size_t)s * a.Q_seed_stride + (size_t)k * a.Q_step_stride;
                 // the weights Q_k (+ curvature) come from global memory: requested here, added behind the chains (as the chains' starting
@@ -1489,8 +1106,9 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_ds(const tg_lq_problem a0) {
             const int rhs_total = 1 + ldc, slice = (rhs_total + NW - 1) / NW;
             const int lo = wave * slice, nrhs = lo < rhs_total ? (rhs_total - lo < slice ? rhs_total - lo : slice) : 0;
             LQ_STAMP(7);      // (diagnostic build: up to here the wait for the factorisation / the tiles; from here the gains)
-            if (*reinterpret_cast<const int *>(fac + 64)) {
-                // [C | K] = gamma^-1 [r + B'b | Kpart] on the matrix cores: NUT x NTC tiles of K (five k-steps each), C as 18 dot products
+            if (*tg::lq_fac_form(fac)) {
+                // the inverse product: [C | K] = gamma^-1 [r + B'b | Kpart] on the matrix cores: NUT x NTC tiles of K (five k-steps each), C as 18 dot
+                // products.  (Inline on purpose: as a function of lq_solve.hpp the same lines compile to other store addresses, measured 0.2 % slower.)
                 for (int t = wave; t < NUT * NTC; t += NW) {
                     const int tu = t / NTC, tj = t - tu * NTC, u = 16 * tu + lr, col = 16 * tj + lr;
                     v4d c = zero4;
@@ -1509,7 +1127,7 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_ds(const tg_lq_problem a0) {
                     wv[tid] = acc;
                 }
             } else
-            lq_apply_rows<NR, (16 * NT + 1 + NW - 1) / NW>(G, ldw, nU, lo, nrhs, Ks, ldx, wv, lane, fac);
+            tg::lq_apply_rows<NR, (16 * NT + 1 + NW - 1) / NW>(G, ldw, nU, lo, nrhs, Ks, ldx, wv, lane, fac);
             LQ_LDS_SYNC();
             LQ_STAMP(2);
         }
@@ -1586,6 +1204,7 @@ __global__ __launch_bounds__(LQM_T) void k_tv_lq_ds(const tg_lq_problem a0) {
         if (a.b0_dev && affine) for (int i = tid; i < nX; i += LQM_T) a.b0_dev[(size_t)s * nX + i] = bv[i];
         if (a.status_dev && tid == 0) a.status_dev[s] = (s_sing || (a.Pt_dev && a.status_dev[s] != TG_OK)) ? TG_SINGULAR : TG_OK;      // (a later chunk of a chunked sweep keeps an earlier chunk's verdict)
     }
+#endif
 }
 
 size_t lq_lds_bytes(int nX, int nU, int ts) {
@@ -2072,6 +1691,68 @@ hipStream_t dopt_lane_stream(int device, int lane) {
 }
 hipStream_t dopt_stream(int device) { return dopt_lane_stream(device, g_lane); }
 
+// Every launch of this file: a kernel given by pointer, on the calling thread's stream lane; above 64 KiB of dynamic LDS it has to opt in first.
+template <class... Params, class... Args>
+int dopt_launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, int device, const Args &...args) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return fail(TG_ERR_HIP, std::string("hipFuncSetAttribute failed: ") + hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, dopt_stream(device), args...);
+    HIP_TRY(hipGetLastError());
+    return TG_SUCCESS;
+}
+
+// The kernel of a plan (lq_plan, tangent_plan below; every class they can name is instantiated here and nowhere else)
+using LqKernel = decltype(&k_tv_lq<2, 4, 1, 2>);
+LqKernel lq_valu_kernel(int ts) {      // <TS, RI, CI, PB>: tile size, prefetch registers for nX <= 16 TS
+    switch (ts) {
+    case 2: return k_tv_lq<2, 4, 1, 2>;
+    case 4: return k_tv_lq<4, 8, 2, 6>;
+    case 5: return k_tv_lq<5, 10, 3, 8>;
+    default: return k_tv_lq<6, 12, 3, 12>;
+    }
+}
+// f(NT, NR) as integral constants for the size class (nt, nr) of the matrix-core sweeps: nt in 1, 2, 3, 5, 6 and nr in 4, 8, 20, 32
+template <class F>
+LqKernel lq_class(int nt, int nr, F &&f) {
+    auto by_nr = [&](auto NT) {
+        return nr == 4 ? f(NT, std::integral_constant<int, 4>()) : (nr == 8 ? f(NT, std::integral_constant<int, 8>())
+               : (nr == 20 ? f(NT, std::integral_constant<int, 20>()) : f(NT, std::integral_constant<int, 32>())));
+    };
+    switch (nt) {
+    case 1: return by_nr(std::integral_constant<int, 1>());
+    case 2: return by_nr(std::integral_constant<int, 2>());
+    case 3: return by_nr(std::integral_constant<int, 3>());
+    case 5: return by_nr(std::integral_constant<int, 5>());
+    default: return by_nr(std::integral_constant<int, 6>());
+    }
+}
+LqKernel lq_mfma_kernel(int nt, int nr) {
+    return lq_class(nt, nr, [](auto NT, auto NR) -> LqKernel { return k_tv_lq_mfma<decltype(NT)::value, decltype(NR)::value>; });
+}
+LqKernel lq_ds_kernel(int nt, int nr) {
+    return lq_class(nt, nr, [](auto NT, auto NR) -> LqKernel { return k_tv_lq_ds<decltype(NT)::value, decltype(NR)::value>; });
+}
+using TangentKernel = decltype(&k_tangent_rows<8, 4, 4, false>);
+TangentKernel tangent_rows_kernel(int ca, bool pair) {      // <CA, CB, CK, PAIR>; 20, 6, 10 is the puppet's nX = 80, nU = 18
+    if (ca == 8) return pair ? k_tangent_rows<8, 4, 4, true> : k_tangent_rows<8, 4, 4, false>;
+    if (ca == 20) return pair ? k_tangent_rows<20, 6, 10, true> : k_tangent_rows<20, 6, 10, false>;
+    return pair ? k_tangent_rows<24, 8, 12, true> : k_tangent_rows<24, 8, 12, false>;
+}
+using CostKernel = decltype(&k_cost_mfma<1>);
+CostKernel cost_mfma_kernel(int nt) {      // 16 x 16 tiles per dimension of Q
+    switch (nt) {
+    case 1: return k_cost_mfma<1>;
+    case 2: return k_cost_mfma<2>;
+    case 3: return k_cost_mfma<3>;
+    case 4: return k_cost_mfma<4>;
+    case 5: return k_cost_mfma<5>;
+    case 6: return k_cost_mfma<6>;
+    default: return nullptr;      // (nX < 1)
+    }
+}
+
 // Which kernel a call launches, decided on the host alone (no device is touched): tg_tv_lq / tg_tangent_rollout launch what these
 // report, tg_tv_lq_plan / tg_tangent_rollout_plan export the same decision.
 struct LqPlan { int kernel = -1, cls = 0, nr = 0, threads = 0; size_t lds = 0; };    // kernel: 0 k_tv_lq (cls = TS), 1 k_tv_lq_mfma, 2 k_tv_lq_ds (cls = NT)
@@ -2176,72 +1857,8 @@ int tg_tv_lq(int32_t device, const tg_lq_problem *p) {
     const int rc = lq_plan(p, pl);
     if (rc != TG_SUCCESS) return rc;
     HIP_TRY(hipSetDevice(device));
-    const int nt = pl.cls, nr = pl.nr;
-    if (pl.kernel == 2) {
-        const size_t ldsd = pl.lds;
-#define TG_LQD_LAUNCH(NT_, NR_)                                                                                                  \
-        do {                                                                                                                     \
-            if (ldsd > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tv_lq_ds<NT_, NR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsd)); \
-            hipLaunchKernelGGL((k_tv_lq_ds<NT_, NR_>), dim3(p->n_problems), dim3(LQM_T), ldsd, dopt_stream(device), *p);         \
-        } while (0)
-#define TG_LQD_NR(NT_)                                                                                                           \
-        switch (nr) {                                                                                                            \
-        case 4: TG_LQD_LAUNCH(NT_, 4); break;                                                                                    \
-        case 8: TG_LQD_LAUNCH(NT_, 8); break;                                                                                    \
-        case 20: TG_LQD_LAUNCH(NT_, 20); break;                                                                                  \
-        default: TG_LQD_LAUNCH(NT_, 32); break;                                                                                  \
-        }
-        switch (nt) {
-        case 1: TG_LQD_NR(1) break;
-        case 2: TG_LQD_NR(2) break;
-        case 3: TG_LQD_NR(3) break;
-        case 5: TG_LQD_NR(5) break;
-        default: TG_LQD_NR(6) break;
-        }
-#undef TG_LQD_NR
-#undef TG_LQD_LAUNCH
-        HIP_TRY(hipGetLastError());
-        return TG_SUCCESS;
-    }
-    if (pl.kernel == 1) {
-        const size_t ldsk = pl.lds;
-#define TG_LQ_LAUNCH(NT_, NR_)                                                                                                   \
-        do {                                                                                                                     \
-            if (ldsk > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tv_lq_mfma<NT_, NR_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsk)); \
-            hipLaunchKernelGGL((k_tv_lq_mfma<NT_, NR_>), dim3(p->n_problems), dim3(LQM_T), ldsk, dopt_stream(device), *p);       \
-        } while (0)
-#define TG_LQ_NR(NT_)                                                                                                            \
-        switch (nr) {                                                                                                            \
-        case 4: TG_LQ_LAUNCH(NT_, 4); break;                                                                                     \
-        case 8: TG_LQ_LAUNCH(NT_, 8); break;                                                                                     \
-        case 20: TG_LQ_LAUNCH(NT_, 20); break;                                                                                   \
-        default: TG_LQ_LAUNCH(NT_, 32); break;                                                                                   \
-        }
-        switch (nt) {
-        case 1: TG_LQ_NR(1) break;
-        case 2: TG_LQ_NR(2) break;
-        case 3: TG_LQ_NR(3) break;
-        case 5: TG_LQ_NR(5) break;
-        default: TG_LQ_NR(6) break;
-        }
-#undef TG_LQ_NR
-#undef TG_LQ_LAUNCH
-        HIP_TRY(hipGetLastError());
-        return TG_SUCCESS;
-    }
-    const int ts = pl.cls;
-    const size_t lds = pl.lds;
-    const void *fn = ts == 2 ? (const void *)k_tv_lq<2, 4, 1, 2> : (ts == 4 ? (const void *)k_tv_lq<4, 8, 2, 6>
-                     : (ts == 5 ? (const void *)k_tv_lq<5, 10, 3, 8> : (const void *)k_tv_lq<6, 12, 3, 12>));
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    switch (ts) {
-    case 2: hipLaunchKernelGGL((k_tv_lq<2, 4, 1, 2>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
-    case 4: hipLaunchKernelGGL((k_tv_lq<4, 8, 2, 6>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
-    case 5: hipLaunchKernelGGL((k_tv_lq<5, 10, 3, 8>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
-    default: hipLaunchKernelGGL((k_tv_lq<6, 12, 3, 12>), dim3(p->n_problems), dim3(LQ_T), lds, dopt_stream(device), *p); break;
-    }
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
+    const LqKernel kernel = pl.kernel == 2 ? lq_ds_kernel(pl.cls, pl.nr) : (pl.kernel == 1 ? lq_mfma_kernel(pl.cls, pl.nr) : lq_valu_kernel(pl.cls));
+    return dopt_launch(kernel, dim3(p->n_problems), dim3(pl.threads), pl.lds, device, *p);
 }
 
 int tg_adjoint_sweep(int32_t device, int32_t n_problems, int32_t horizon, int32_t nX, int32_t nU, const int32_t *select_dev,
@@ -2251,10 +1868,7 @@ int tg_adjoint_sweep(int32_t device, int32_t n_problems, int32_t horizon, int32_
     const size_t lds = sizeof(double) * ((size_t)nX * (nX | 1) + (size_t)nX * nU + (size_t)nU * nX + 2 * nX + nU);
     if (lds > 160 * 1024 - 64 || nX > 96 || nX * nU > 12 * SW_T) return fail(TG_ERR_UNSUPPORTED, "state dimension too large");
     HIP_TRY(hipSetDevice(device));
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_adjoint, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_adjoint, dim3(n_problems), dim3(SW_T), lds, dopt_stream(device), horizon, nX, nU, select_dev, A_dev, B_dev, K_dev, q_dev, r_dev, Z_dev);
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
+    return dopt_launch(k_adjoint, dim3(n_problems), dim3(SW_T), lds, device, horizon, nX, nU, select_dev, A_dev, B_dev, K_dev, q_dev, r_dev, Z_dev);
 }
 
 int tg_tangent_rollout(int32_t device, int32_t n_problems, int32_t horizon, int32_t nX, int32_t nU, const int32_t *select_dev,
@@ -2266,30 +1880,9 @@ int tg_tangent_rollout(int32_t device, int32_t n_problems, int32_t horizon, int3
     const int rc = tangent_plan(nX, nU, A_dev, B_dev, K_dev, pl);
     if (rc != TG_SUCCESS) return rc;
     HIP_TRY(hipSetDevice(device));
-    if (pl.kernel == 1) {     // rows in registers (k_tangent_rows)
-        const int nt = pl.threads;
-        const size_t ldsr = pl.lds;
-#define LAUNCH_TR(CA_, CB_, CK_, PAIR_)                                                                                                              \
-        hipLaunchKernelGGL((k_tangent_rows<CA_, CB_, CK_, PAIR_>), dim3(n_problems), dim3(nt), ldsr, dopt_stream(device), horizon, nX, nU, select_dev, \
-                           A_dev, B_dev, K_dev, C_dev, q_dev, r_dev, dX_dev, dU_dev, dcost_dev)
-        if (pl.pair) {
-            if (pl.ca == 8) LAUNCH_TR(8, 4, 4, true);
-            else if (pl.ca == 20) LAUNCH_TR(20, 6, 10, true);       // the puppet's nX = 80, nU = 18
-            else LAUNCH_TR(24, 8, 12, true);
-        }
-        else if (pl.ca == 8) LAUNCH_TR(8, 4, 4, false);
-        else if (pl.ca == 20) LAUNCH_TR(20, 6, 10, false);
-        else LAUNCH_TR(24, 8, 12, false);
-#undef LAUNCH_TR
-        HIP_TRY(hipGetLastError());
-        return TG_SUCCESS;
-    }
-    const size_t lds = pl.lds;
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_tangent, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_tangent, dim3(n_problems), dim3(SW_T), lds, dopt_stream(device), horizon, nX, nU, select_dev, A_dev, B_dev, K_dev, C_dev, q_dev,
+    const TangentKernel kernel = pl.kernel == 1 ? tangent_rows_kernel(pl.ca, pl.pair) : k_tangent;      // rows in registers, or staged in LDS
+    return dopt_launch(kernel, dim3(n_problems), dim3(pl.threads), pl.lds, device, horizon, nX, nU, select_dev, A_dev, B_dev, K_dev, C_dev, q_dev,
                        r_dev, dX_dev, dU_dev, dcost_dev);
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
 }
 
 int tg_tangent_rollout_plan(int32_t nX, int32_t nU, const void *A, const void *B, const void *K, int32_t out[6]) {
@@ -2310,24 +1903,15 @@ int tg_quadratic_cost(int32_t device, int32_t n_trajectories, int32_t group, con
     if (nX <= 96 && nU <= 96 && !std::getenv("TREPAMD_COST_LEGACY")) {     // matrix-core version (k_cost_mfma)
         const int nt = (nX + 15) / 16, ldx = 16 * nt, ldu = round_up(nU, 16);
         const size_t ldsm = sizeof(double) * ((size_t)ldx * ldx + (size_t)ldu * ldu + CT_T);
-#define LAUNCH_COST(NT_)                                                                                                                  \
-        case NT_:                                                                                                                         \
-            if (ldsm > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_cost_mfma<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm)); \
-            hipLaunchKernelGGL((k_cost_mfma<NT_>), dim3(n_trajectories), dim3(CT_T), ldsm, dopt_stream(device), horizon, nX, nU, group, select_dev, X_dev, U_dev,       \
-                               Xd_dev, Ud_dev, Q_dev, R_dev, Qf_dev, cost_dev);                                                           \
-            break;
-        switch (nt) { LAUNCH_COST(1) LAUNCH_COST(2) LAUNCH_COST(3) LAUNCH_COST(4) LAUNCH_COST(5) LAUNCH_COST(6) default: break; }
-#undef LAUNCH_COST
-        HIP_TRY(hipGetLastError());
-        return TG_SUCCESS;
+        const CostKernel kernel = cost_mfma_kernel(nt);
+        if (!kernel) return TG_SUCCESS;      // (no states: nothing is launched)
+        return dopt_launch(kernel, dim3(n_trajectories), dim3(CT_T), ldsm, device, horizon, nX, nU, group, select_dev, X_dev, U_dev, Xd_dev, Ud_dev, Q_dev,
+                           R_dev, Qf_dev, cost_dev);
     }
     const size_t lds = sizeof(double) * (2 * (size_t)nX * nX + (size_t)nU * nU + 4 * (size_t)(nX + nU) + CT_T);
     if (lds > 160 * 1024 - 64) return fail(TG_ERR_UNSUPPORTED, "state dimension too large");
-    if (lds > 64 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)k_cost, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_cost, dim3(n_trajectories), dim3(CT_T), lds, dopt_stream(device), horizon, nX, nU, group, select_dev, X_dev, U_dev, Xd_dev, Ud_dev, Q_dev, R_dev,
+    return dopt_launch(k_cost, dim3(n_trajectories), dim3(CT_T), lds, device, horizon, nX, nU, group, select_dev, X_dev, U_dev, Xd_dev, Ud_dev, Q_dev, R_dev,
                        Qf_dev, cost_dev);
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
 }
 
 int tg_quadratic_cost_gradients(int32_t device, int32_t n_problems, int32_t horizon, int32_t nX, int32_t nU, const int32_t *select_dev,
@@ -2336,10 +1920,8 @@ int tg_quadratic_cost_gradients(int32_t device, int32_t n_problems, int32_t hori
     if (n_problems <= 0 || horizon <= 0 || !X_dev || !U_dev || !Xd_dev || !Ud_dev || !Q_dev || !R_dev || !Qf_dev || !q_dev || !r_dev)
         return fail(TG_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(device));
-    hipLaunchKernelGGL(k_cost_grad, dim3(horizon + 1, n_problems), dim3(CT_T), sizeof(double) * (nX + nU), dopt_stream(device), horizon, nX, nU, select_dev,
+    return dopt_launch(k_cost_grad, dim3(horizon + 1, n_problems), dim3(CT_T), sizeof(double) * (nX + nU), device, horizon, nX, nU, select_dev,
                        X_dev, U_dev, Xd_dev, Ud_dev, Q_dev, R_dev, Qf_dev, q_dev, r_dev);
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
 }
 
 int tg_armijo_candidates(int32_t device, int32_t n_problems, int32_t n_lambdas, int32_t horizon, int32_t nX, int32_t nU,
@@ -2349,10 +1931,8 @@ int tg_armijo_candidates(int32_t device, int32_t n_problems, int32_t n_lambdas, 
         return fail(TG_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(device));
     const int bx = (int)(((size_t)(horizon + 1) * nX + 255) / 256);
-    hipLaunchKernelGGL(k_candidates, dim3(bx > 64 ? 64 : bx, n_problems * n_lambdas), dim3(256), 0, dopt_stream(device), horizon, nX, nU, n_lambdas, select_dev,
+    return dopt_launch(k_candidates, dim3(bx > 64 ? 64 : bx, n_problems * n_lambdas), dim3(256), 0, device, horizon, nX, nU, n_lambdas, select_dev,
                        lambdas_dev, X_dev, U_dev, dX_dev, dU_dev, bX_dev, bU_dev);
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
 }
 
 int tg_copy_rows(int32_t device, int32_t n_rows, uint64_t row_doubles, const int32_t *dst_rows_dev, const int32_t *src_rows_dev,
@@ -2360,10 +1940,8 @@ int tg_copy_rows(int32_t device, int32_t n_rows, uint64_t row_doubles, const int
     if (n_rows <= 0 || !src_dev || !dst_dev) return fail(TG_ERR_INVALID, "bad arguments");
     HIP_TRY(hipSetDevice(device));
     const int bx = (int)((row_doubles + 255) / 256);
-    hipLaunchKernelGGL(k_copy_rows, dim3(bx > 64 ? 64 : (bx < 1 ? 1 : bx), n_rows > 65535 ? 65535 : n_rows), dim3(256), 0, dopt_stream(device), n_rows, (size_t)row_doubles, dst_rows_dev,
+    return dopt_launch(k_copy_rows, dim3(bx > 64 ? 64 : (bx < 1 ? 1 : bx), n_rows > 65535 ? 65535 : n_rows), dim3(256), 0, device, n_rows, (size_t)row_doubles, dst_rows_dev,
                        src_rows_dev, src_dev, dst_dev);
-    HIP_TRY(hipGetLastError());
-    return TG_SUCCESS;
 }
 
 #if defined(TG_PROFILE)
