@@ -28,6 +28,10 @@ BUILDERS = {
     "damper_link": lambda: systems.damper_link(),
     "puppet_forces": lambda: systems.puppet_forces(),
     "extensor_tendon": lambda: systems.extensor_tendon(),
+    "spatial_loop": lambda: systems.spatial_loop(),
+    "mixed_loop": lambda: systems.mixed_loop(),
+    "ladder_point": lambda: systems.ladder_point(),
+    "ladder_mixed": lambda: systems.ladder_mixed(),
 }
 D1 = ["q2_dq1", "q2_dp1", "q2_du1", "q2_dk2", "p2_dq1", "p2_dp1", "p2_du1", "p2_dk2",
       "l1_dq1", "l1_dp1", "l1_du1", "l1_dk2"]
@@ -91,6 +95,8 @@ TEAM_CELLS = {
     "spring_arm": {1: {"deriv1", "deriv2z", "dynamics_deriv1"}, 4: set(), 16: set(), 64: set()},
     "scissor4": {1: _ALL, 4: {"deriv1", "deriv2z", "dynamics_deriv1"}, 16: set(), 64: set()},
     "puppet_basic": {16: {"deriv2z"}, 64: set()},
+    "spatial_loop": {1: _ALL, 4: set(), 16: set(), 64: set()},
+    "mixed_loop": {1: _ALL, 4: set(), 16: set(), 64: set()},
 }
 
 
@@ -163,7 +169,7 @@ TB_GROUP = 2                                        # trajectories per gain set 
 # feedback moves X by 1e-6 .. 1e-2 (test_time_base_cpu.py checks it): forces on a heavy puppet move it little, kinematic configs are
 # set by their input directly, and on the puppet a move above 1e-4 makes the reference loop itself diverge through the string lengths
 TB_LOOP = {"pend_on_cart": (3e-3, 1.0), "wrench_arm": (1e-4, 0.3), "spring_arm": (1e-4, 0.3), "puppet_forces": (3e-2, 1.0),
-           "puppet40": (1e-4, 0.1)}
+           "puppet40": (1e-4, 0.1), "mixed_loop": (1e-4, 0.3)}
 # another start where the first one is badly conditioned (conditioning rule, test_time_base_cpu.py): of eight scissor-lift draws, the
 # 1-ulp floor of X over 24 steps ranges from 3e-13 to 4e-11; this one has 3e-13
 TB_START = {"scissor4": 3}
@@ -199,6 +205,8 @@ def tb_step_sizes(pattern, N=TB_N, name=""):
     and 1 / dt^2, and the project's tolerances were set at DT.)"""
     if pattern == "alternating":
         return TB_DT * np.where(np.arange(N) % 2 == 0, 0.6, 1.5)
+    if pattern == "uniform":                        # (no case of the table: the model-branch cases below, MB_*)
+        return np.full(N, TB_DT)
     assert pattern == "random"
     return TB_DT * (0.6 + 0.9 * np.random.default_rng(tb_seed("steps", name)).random(N))       # (a shorter list is a prefix)
 
@@ -454,6 +462,44 @@ def tb_horizon(name, pattern):
 def tb_bound(quantity, e_ref=None):
     """max(project tolerance, 64 e_ref): the rule of the LQ tests, the floor from the reference's own error."""
     return max(TB_TOL[quantity], 64.0 * (e_ref or {}).get(quantity, 0.0))
+
+
+# ---- model branches only spatial_loop, mixed_loop and the two ladders reach (test_model_branches_cpu.py, test_gpu_model_branches.py,
+# test_gpu_world_frame_shapes.py, tools/model_branches_parity.py).  The cases are cases of the machinery above on a uniform time base:
+# MB_N steps from starts on the recorded trajectories, the oracle's run as the reference, its response to one ulp of the start as the floor.
+MB_N = 12
+MB_GENERIC = ("spatial_loop", "mixed_loop")        # the generic kernels, at the team the library gives them
+MB_LADDERS = ("ladder_point", "ladder_mixed")      # the specialised world-frame path (team 64)
+MB_TEAM = {"spatial_loop": 16, "mixed_loop": 16, "ladder_point": 64, "ladder_mixed": 64}      # test_model_branches_cpu.py holds it to the library's
+MB_CLOSED_LOOP = ("mixed_loop",)
+# (system, quantity) whose bound needs the second term of max(tolerance, 64 e_ref) (at most one quantity per system;
+# test_model_branches_cpu.py asserts that exactly these floors are over the tolerance)
+MB_SECOND_TERM = set()
+
+
+def mb_batch(name):
+    """One full block of teams plus a ragged one; 5 at a team of 64."""
+    return max(2 * (64 // MB_TEAM[name]) + 1, 5)
+
+
+def mb_case(name):
+    return tb_case(name, "uniform", MB_N, mb_batch(name))
+
+
+def mb_reference(name):
+    return tb_reference(name, "uniform", MB_N, mb_batch(name))
+
+
+def mb_e_ref(name, closed_loop=False):
+    return tb_e_ref(name, "uniform", MB_N, mb_batch(name), closed_loop=closed_loop)
+
+
+def mb_bound(name, quantity, e_ref):
+    return tb_bound(quantity, e_ref) if (name, quantity) in MB_SECOND_TERM else TB_TOL[quantity]
+
+
+def mb_contraction(name):
+    return tb_contraction(name, mb_batch(name))
 
 
 # ---- shared by the discopt device tests (test_gpu_discopt_device.py, test_gpu_lq_classes.py, test_gpu_discopt_sizes.py) ----
@@ -824,6 +870,8 @@ FW_SYSTEMS = collections.OrderedDict([
     ("wrench_body", (24, 0.05)),
     ("puppet_forces", (12, 0.05)),
     ("extensor_tendon", (24, 0.05)),
+    ("spatial_loop", (24, 0.05)),
+    ("mixed_loop", (24, 0.05)),
 ])
 FW_CASES = [(n, k) for n in FW_SYSTEMS for k in FW_KERNELS]
 # The ladder: (base step along a q variable, halvings) per kernel, and per (system, kernel) where the default misses the floor rule of
@@ -837,7 +885,11 @@ FW_LADDER = {("scissor4", "dyn"): (0.02, 3), ("scissor4", "lag2"): (0.32, 3), ("
              ("puppet_basic", "lag2"): (0.32, 3),
              ("nonlinear_spring_arm", "dyn"): (0.01, 3), ("nonlinear_spring_arm", "lag1"): (0.005, 2), ("nonlinear_spring_arm", "lag2"): (0.01, 2),
              ("dual_pendulums", "dyn"): (0.16, 5), ("dual_pendulums", "lag1"): (0.08, 4), ("spring_link", "lag1"): (0.16, 4), ("dual_pendulums", "lag2"): (0.16, 5),
-             ("extensor_tendon", "dyn"): (0.16, 4), ("extensor_tendon", "lag1"): (0.16, 4), ("extensor_tendon", "lag2"): (0.08, 3)}
+             ("extensor_tendon", "dyn"): (0.16, 4), ("extensor_tendon", "lag1"): (0.16, 4), ("extensor_tendon", "lag2"): (0.08, 3),
+             # spatial_loop's telescopic branch hangs on the axis of its rz joint: near its recorded states the mass matrix is close to singular
+             # in that config, and the dynamics' arrays have a pole a few hundredths away along q.  The default step reaches across it (floor of
+             # f_dq 3.6e-2); the floor falls with the eighth power of the step down to 0.005 and stays at 1e-11 .. 5e-11 (rounding) below
+             ("spatial_loop", "dyn"): (0.005, 3)}
 
 
 def fw_ladder_of(name, kernel):
@@ -845,7 +897,8 @@ def fw_ladder_of(name, kernel):
 # another draw where the first one fails the sensitivity rule of test_forward_cpu.py: (system, kernel) -> draw number
 # (puppet_basic: seven of twelve references of draw 0 are under the bound.  nonlinear_spring_arm: a ladder that straddles a knot of one of
 # the force splines differences a kink, and the floor of such a trajectory is 1e-6 ... 1e-3; these are draws on which no ladder does)
-FW_DRAW = {("puppet_basic", "lag2"): 1, ("nonlinear_spring_arm", "lag1"): 4, ("nonlinear_spring_arm", "lag2"): 3}
+# mixed_loop: the (dq, q) pairs of draw 0 all join configs of different chains, whose mixed derivatives are zero -- draw 1 reaches that block)
+FW_DRAW = {("puppet_basic", "lag2"): 1, ("nonlinear_spring_arm", "lag1"): 4, ("nonlinear_spring_arm", "lag2"): 3, ("mixed_loop", "lag2"): 1}
 # (system, kernel, array) whose bound needs the second term of max(tolerance, 64 e_ref): measured floor e_ref (test_forward_cpu.py
 # asserts that exactly these are over FW_FLOOR, and each under twice the figure here)
 FW_SECOND_TERM = {
@@ -886,6 +939,12 @@ FW_SECOND_TERM = {
     ("extensor_tendon", "dyn"): {"f_dq": 6.1e-12, "f_ddq": 3.4e-12},
     ("extensor_tendon", "lag1"): {"L_dq": 5.1e-13, "L_ddq": 7.7e-13, "L_dqdq": 7.3e-13, "L_ddqdq": 1.2e-13, "L_ddqddq": 4.6e-13},
     ("extensor_tendon", "lag2"): {"L_dq": 1.3e-10, "L_ddq": 1.0e-10, "L_dqdq": 1.1e-10, "L_ddqdq": 3.1e-11, "L_ddqddq": 1.5e-10},
+    ("spatial_loop", "dyn"): {"f_dq": 2.6e-11, "f_ddq": 6.6e-12, "f_dddk": 9.2e-12, "lambda_dq": 1.4e-11, "lambda_ddq": 1.7e-12},
+    ("spatial_loop", "lag1"): {"L_dq": 1.5e-13, "L_ddq": 8.9e-14, "L_dqdq": 2.6e-13, "L_ddqdq": 1.3e-13, "L_ddqddq": 7.3e-14},
+    ("spatial_loop", "lag2"): {"L_dq": 2.7e-12, "L_ddq": 4.0e-12, "L_dqdq": 2.6e-11, "L_ddqdq": 1.1e-12, "L_ddqddq": 4.2e-12},
+    ("mixed_loop", "dyn"): {"f_dq": 1.8e-12},
+    ("mixed_loop", "lag1"): {"L_dq": 1.7e-14, "L_ddq": 1.4e-13, "L_dqdq": 5.6e-13, "L_ddqddq": 1.3e-13},
+    ("mixed_loop", "lag2"): {"L_dq": 2.0e-12, "L_ddq": 2.3e-12, "L_dqdq": 1.9e-11, "L_ddqdq": 2.8e-12, "L_ddqddq": 8.5e-13},
 }
 
 

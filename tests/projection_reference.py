@@ -16,8 +16,9 @@ F_PARITY = common.TB_TOL["f"]         # the project's calc_f parity figure: how 
 MARGIN = 64                           # the project's margin convention (FW_FLOOR, lq_parity)
 STEP_CAP = 8                          # the reference converges on every row of the table within this many steps
 
-SYSTEMS = ("plane_link", "scissor4", "puppet_basic", "puppet40")
-CONSTANT = {"plane_link": ["a"], "scissor4": ["SLIDER"], "puppet_basic": None, "puppet40": None}     # None: the first two configs
+SYSTEMS = ("plane_link", "scissor4", "puppet_basic", "puppet40", "spatial_loop", "mixed_loop")
+CONSTANT = {"plane_link": ["a"], "scissor4": ["SLIDER"], "puppet_basic": None, "puppet40": None,     # None: the first two configs
+            "spatial_loop": ["a"], "mixed_loop": ["a"]}
 MASKS = ("all", "keep_kinematic", "constant")
 CASES = [(n, m, 0.02) for n in SYSTEMS for m in MASKS] + [(n, "all", 0.1) for n in SYSTEMS]
 # Which draw of a case's seed the table uses (0 unless listed).  scissor4 at 0.1 of noise: undamped Newton leaves its basin on about

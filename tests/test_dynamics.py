@@ -7,7 +7,8 @@ import pytest
 
 from common import GOLDEN, build, relerr
 
-NAMES = ["pendulum5", "pend_on_cart", "scissor4", "puppet40", "puppet_basic", "spring_arm", "spring_link", "plane_link", "wrench_arm", "wrench_torque", "dual_pendulums", "wrench_spatial", "wrench_body", "damper_link", "nonlinear_spring_arm"]
+NAMES = ["pendulum5", "pend_on_cart", "scissor4", "puppet40", "puppet_basic", "spring_arm", "spring_link", "plane_link", "wrench_arm", "wrench_torque", "dual_pendulums", "wrench_spatial", "wrench_body", "damper_link", "nonlinear_spring_arm",
+         "spatial_loop", "mixed_loop", "ladder_point", "ladder_mixed"]
 
 
 def golden():
@@ -239,12 +240,15 @@ def test_gpu_lagrangian_derivatives_match_reference(name):
 
 # ---- second derivatives of the continuous dynamics (system.py:982-1078; calc_dynamics_deriv2, system.c:1301-2029) ---------
 D2_NAMES = ["pendulum5", "pend_on_cart", "scissor4", "spring_arm", "plane_link", "wrench_arm", "wrench_torque", "wrench_body",
-            "damper_link", "nonlinear_spring_arm", "puppet40"]
+            "damper_link", "nonlinear_spring_arm", "puppet40", "spatial_loop", "mixed_loop", "ladder_point", "ladder_mixed"]
 D2_KEYS = ["dqdq", "ddqdq", "ddqddq", "dddkdq", "dudq", "duddq", "dudu"]
 
 
 def golden2():
-    return dict(np.load(os.path.join(GOLDEN, "dynamics2.npz")))
+    """dynamics2.npz and the ladders' file next to it (one state each: together the two would pass the size a committed file may have)."""
+    out = dict(np.load(os.path.join(GOLDEN, "dynamics2.npz")))
+    out.update(np.load(os.path.join(GOLDEN, "dynamics2_ladders.npz")))
+    return out
 
 
 def _check_second(name, got, g2, s, tol):
@@ -302,7 +306,8 @@ def test_a_direction_on_no_variable_gives_zero_derivatives():
     assert np.abs(out["f_dq"][1]).max() > 0.0 and np.all(out["f_du"][1] == 0.0)
 
 
-@pytest.mark.parametrize("name", ["pendulum5", "scissor4", "puppet40", "spring_arm", "plane_link"])
+@pytest.mark.parametrize("name", ["pendulum5", "scissor4", "puppet40", "spring_arm", "plane_link", "spatial_loop", "mixed_loop", "ladder_point",
+                                  "ladder_mixed"])
 def test_emulated_higher_order_lagrangian_derivatives_match_reference(name):
     """Third- and fourth-order derivatives of the Lagrangian (System_L_dqdqdq ... L_ddqddqdqdq, system.c:204-622): the Lagrangian kernel
     on dual numbers with one direction (third order) and two nested ones (fourth), through the host emulation, against the reference's
@@ -385,7 +390,8 @@ def test_gpu_forward_mode_entry_points_check_their_directions():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["pendulum5", "scissor4", "puppet40", "spring_arm", "plane_link", "nonlinear_spring_arm"])
+@pytest.mark.parametrize("name", ["pendulum5", "scissor4", "puppet40", "spring_arm", "plane_link", "nonlinear_spring_arm", "spatial_loop",
+                                  "mixed_loop", "ladder_point", "ladder_mixed"])
 def test_gpu_higher_order_lagrangian_accessors_match_reference(name):
     """System.L_dqdqdq, L_ddqdqdq, L_ddqddqdq (third order) and L_ddqdqdqdq, L_ddqddqdqdq (fourth order), system.py:869-949:
     the Lagrangian kernel on dual numbers (one direction / two nested ones) against the reference's table look-ups, for seeded index

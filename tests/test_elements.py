@@ -9,7 +9,8 @@ import pytest
 from common import golden
 
 NAMES = ["pend_on_cart", "scissor4", "spring_arm", "nonlinear_spring_arm", "spring_link", "plane_link", "wrench_arm", "wrench_torque",
-         "wrench_spatial", "wrench_body", "damper_link", "extensor_tendon", "puppet_basic"]
+         "wrench_spatial", "wrench_body", "damper_link", "extensor_tendon", "puppet_basic", "spatial_loop", "mixed_loop", "ladder_point",
+         "ladder_mixed"]
 
 
 def _system(name):

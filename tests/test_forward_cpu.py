@@ -165,7 +165,8 @@ INSENSITIVE = {
     ("wrench_arm", "lag1"): (1, 0), ("wrench_arm", "lag2"): (4, 0), ("wrench_spatial", "dyn"): (2, 0), ("wrench_spatial", "lag1"): (1, 0),
     ("wrench_spatial", "lag2"): (3, 0), ("wrench_body", "dyn"): (4, 0), ("wrench_body", "lag1"): (1, 0), ("wrench_body", "lag2"): (3, 0),
     ("puppet_forces", "dyn"): (1, 0), ("puppet_forces", "lag1"): (1, 0), ("puppet_forces", "lag2"): (2, 0), ("extensor_tendon",
-    "lag2"): (4, 0)
+    "lag2"): (4, 0), ("spatial_loop", "lag1"): (0, 2), ("spatial_loop", "lag2"): (11, 0), ("mixed_loop", "dyn"): (4, 0),
+    ("mixed_loop", "lag1"): (1, 2), ("mixed_loop", "lag2"): (10, 0)
 }
 MARGIN = 1000.0
 
@@ -263,6 +264,13 @@ ALL_ZERO = {
     ("puppet_forces", "lag2"): ['L_ddq/dq,dq', 'L_ddqddq/dq,dq', 'L_ddqddq/dq,q', 'L_ddqddq/q,dq', 'L_ddqdq/dq,dq'],
     ("extensor_tendon", "lag1"): ['L_ddqddq/dq'],
     ("extensor_tendon", "lag2"): ['L_ddq/dq,dq', 'L_ddqddq/dq,dq', 'L_ddqddq/dq,q', 'L_ddqddq/q,dq', 'L_ddqdq/dq,dq', 'L_dq/dq,dq', 'L_dqdq/dq,dq'],
+    ("spatial_loop", "dyn"): ['f_dddk/ddq_k', 'f_dddk/dq', 'f_ddq/ddq_k', 'lambda_dddk/ddq_k', 'lambda_dddk/dq', 'lambda_ddq/ddq_k'],
+    ("spatial_loop", "lag1"): ['L_ddqddq/dq'],
+    ("spatial_loop", "lag2"): ['L_ddq/dq,dq', 'L_ddq/q,dq', 'L_ddqddq/dq,dq', 'L_ddqddq/dq,q', 'L_ddqddq/q,dq', 'L_ddqdq/dq,dq', 'L_ddqdq/q,dq', 'L_dq/dq,dq', 'L_dq/q,dq', 'L_dqdq/dq,dq', 'L_dqdq/q,dq'],
+    ("mixed_loop", "dyn"): ['f_dddk/ddq_k', 'f_dddk/dq', 'f_dddk/u', 'f_ddq/ddq_k', 'f_ddq/u', 'f_du/ddq_k', 'f_du/dq', 'f_du/u', 'lambda_dddk/ddq_k', 'lambda_dddk/dq',
+                            'lambda_dddk/u', 'lambda_ddq/ddq_k', 'lambda_ddq/u', 'lambda_du/ddq_k', 'lambda_du/dq', 'lambda_du/u'],
+    ("mixed_loop", "lag1"): ['L_ddqddq/dq'],
+    ("mixed_loop", "lag2"): ['L_ddq/dq,dq', 'L_ddqddq/dq,dq', 'L_ddqddq/dq,q', 'L_ddqddq/q,dq', 'L_ddqdq/dq,dq', 'L_dq/dq,dq', 'L_dqdq/dq,dq'],
 }
 
 

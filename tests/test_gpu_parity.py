@@ -385,7 +385,7 @@ def test_deriv1_accessors_dropin():
     assert mvi.q2_dk2().shape == (2, 0)
 
 
-@pytest.mark.parametrize("name", ["pend_on_cart", "scissor4", "puppet40", "pendulum5", "spring_arm", "nonlinear_spring_arm", "plane_link", "wrench_arm", "puppet_forces", "wrench_torque", "wrench_spatial", "wrench_body", "damper_link"])
+@pytest.mark.parametrize("name", ["pend_on_cart", "scissor4", "puppet40", "pendulum5", "spring_arm", "nonlinear_spring_arm", "plane_link", "wrench_arm", "puppet_forces", "wrench_torque", "wrench_spatial", "wrench_body", "damper_link", "spatial_loop", "mixed_loop"])
 def test_dsystem_linearization_matches_reference(name):
     """DSystem.set(X[k],U[k],k,xk_hint=X[k+1]) -> f, fdx (A_k), fdu (B_k) vs the reference's DSystem."""
     import trep_amd
@@ -414,7 +414,7 @@ def test_dsystem_linearization_matches_reference(name):
     assert lin.A.shape == (3, one.nX, one.nX) and lin.B.shape == (3, one.nX, one.nU)
 
 
-@pytest.mark.parametrize("name,spec", _spec_cases(["pend_on_cart", "scissor4", "puppet40", "pendulum5", "spring_arm", "nonlinear_spring_arm", "plane_link", "wrench_arm", "puppet_forces", "wrench_torque", "wrench_spatial", "wrench_body", "damper_link"]))
+@pytest.mark.parametrize("name,spec", _spec_cases(["pend_on_cart", "scissor4", "puppet40", "pendulum5", "spring_arm", "nonlinear_spring_arm", "plane_link", "wrench_arm", "puppet_forces", "wrench_torque", "wrench_spatial", "wrench_body", "damper_link", "spatial_loop", "mixed_loop"]))
 def test_dsystem_second_order_matches_reference(name, spec):
     """fdxdx(z), fdxdu(z), fdudu(z) vs the reference DSystem (dsystem.py:320-386) for two z."""
     import trep_amd
@@ -440,7 +440,7 @@ def test_dsystem_second_order_matches_reference(name, spec):
     _assert_kernels(bd.varint.kernel_info(), spec, ["rollout", "deriv2z"])
 
 
-@pytest.mark.parametrize("name,spec", _spec_cases(["pend_on_cart", "scissor4", "puppet40", "puppet_basic", "spring_arm", "nonlinear_spring_arm", "plane_link", "wrench_arm", "puppet_forces", "wrench_torque", "wrench_spatial", "wrench_body", "damper_link"]))
+@pytest.mark.parametrize("name,spec", _spec_cases(["pend_on_cart", "scissor4", "puppet40", "puppet_basic", "spring_arm", "nonlinear_spring_arm", "plane_link", "wrench_arm", "puppet_forces", "wrench_torque", "wrench_spatial", "wrench_body", "damper_link", "spatial_loop", "mixed_loop"]))
 def test_full_second_derivative_tensors_match_reference(name, spec):
     """MidpointVI.q2_dq1dq1() ... p2_dk2dk2(), lambda1_dq1dq1() ... accessors vs the reference's [A][B][out] tensors."""
     import trep_amd
@@ -928,7 +928,7 @@ def _newton_like(rng, pat, nd, dt=0.01):
     return A
 
 
-@pytest.mark.parametrize("name", ["puppet40", "puppet_basic", "scissor4"])
+@pytest.mark.parametrize("name", ["puppet40", "puppet_basic", "scissor4", "ladder_point", "ladder_mixed"])
 def test_structured_newton_solve_matches_the_pivoting_solvers(name):
     """The structured solve of the specialised rollout kernels (csrc/bbd.hpp: blocks of the bordered-block-diagonal plan eliminated
     side by side without a pivot search, then the border system, then back-substitution) against the reference's LU_decomp /

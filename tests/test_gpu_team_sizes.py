@@ -22,6 +22,10 @@ CELLS = [(n, t) for n in sorted(TEAM_CELLS) for t in sorted(TEAM_CELLS[n])]
 LEGAL = [(n, t) for n, t in CELLS if "rollout" not in TEAM_CELLS[n][t]]
 REFUSING = [(n, t) for n, t in CELLS if TEAM_CELLS[n][t]]
 BIG = ("puppet_basic",)
+# Place of a system in the seeds of test_team_cell_matches_oracle.  Append a new system at the end: the draws of the others stay.
+_SEED_ORDER = ["damper_link", "dual_pendulums", "pend_on_cart", "pendulum1", "pendulum5", "plane_link", "puppet_basic", "scissor4", "spring_arm",
+               "spring_link", "wrench_arm", "spatial_loop", "mixed_loop"]
+assert sorted(_SEED_ORDER) == sorted(TEAM_CELLS)
 
 
 def _batch(monkeypatch, system, B, team):
@@ -177,7 +181,7 @@ def _run_cell(monkeypatch, name, team, B, rng, refused=()):
 def test_team_cell_matches_oracle(monkeypatch, name, team):
     """Every mode the cell allows, at three ragged batch sizes (two full blocks and one team, three blocks less one team, a single
     partial block); the rollout also against the same system at the team it gets by itself."""
-    rng = np.random.default_rng(1000 + 64 * team + sorted(TEAM_CELLS).index(name))
+    rng = np.random.default_rng(1000 + 64 * team + _SEED_ORDER.index(name))
     refused = TEAM_CELLS[name][team]
     for B in _shapes(name, team):
         seed = int(rng.integers(1 << 30))
@@ -246,6 +250,15 @@ def test_team_cell_refusals(monkeypatch, name, team):
     mvi.close()
 
 
+# Size of the closed loop's random gains where 0.01 is too much for the reference itself: mixed_loop has kinematic configs inside a closed
+# chain, and a feedback that moves them that far opens the loop -- with these inputs the oracle's own loop (common.tb_oracle_rollout) does
+# not converge on trajectories 4 and 7 of the batch at team 16; at 1e-3 every trajectory takes the open loop's 30 iterations.  With gains
+# that small the feedback does little: this cell checks what the test is about -- the subset launch against the full one, bit for bit --
+# and the closed loop of mixed_loop itself is held to the oracle in test_gpu_model_branches.py, with gains scaled per column
+# (common.tb_closed_loop_inputs) that move X by 1e-6 .. 1e-2.
+_LOOP_GAIN = {"mixed_loop": 1e-3}
+
+
 def _legal(name, team, kind):
     return kind not in TEAM_CELLS[name][team]
 
@@ -288,7 +301,7 @@ def test_team_cell_remapped_launches(monkeypatch, name, team):
     Q0, Q1, U, K = _starts(name, d, B, N, rng)
     bX = np.zeros((B, N + 1, nX))
     bU = np.concatenate([U, K], axis=2)
-    Kp = 0.01 * rng.standard_normal((B, N, nU, nX))
+    Kp = _LOOP_GAIN.get(name, 0.01) * rng.standard_normal((B, N, nU, nX))
     mvi = _batch(monkeypatch, system, B, team)
     mvi.initialize_from_configs(0.0, Q0, DT, Q1)
     bX[:] = np.concatenate([mvi.q2, mvi.p2, mvi.q2[:, nd:]], axis=1)[:, None, :]

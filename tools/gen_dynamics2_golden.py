@@ -29,16 +29,23 @@ BUILDERS = {
     "damper_link": (lambda: systems.damper_link(api=trep), 1),
     "nonlinear_spring_arm": (lambda: systems.nonlinear_spring_arm(api=trep), 2),
     "puppet40": (lambda: systems.puppet(api=trep), 1),
+    "spatial_loop": (lambda: systems.spatial_loop(api=trep), 2),
+    "mixed_loop": (lambda: systems.mixed_loop(api=trep), 2),
+    "ladder_point": (lambda: systems.ladder_point(api=trep), 1),
+    "ladder_mixed": (lambda: systems.ladder_mixed(api=trep), 1),
 }
+# recorded in a file of their own, tests/golden/dynamics2_ladders.npz: with their [16][16][16] tensors dynamics2.npz would pass the 1 MiB
+# a committed file may have
+OWN_FILE = {"ladder_point": "dynamics2_ladders.npz", "ladder_mixed": "dynamics2_ladders.npz"}
 NAMES = ["dqdq", "ddqdq", "ddqddq", "dddkdq", "dudq", "duddq", "dudu"]
 
 
 def main():
     which = sys.argv[1:] or list(BUILDERS)
     g = dict(np.load(os.path.join(REPO, "tests", "golden", "dynamics.npz")))
-    path = os.path.join(REPO, "tests", "golden", "dynamics2.npz")
-    out = dict(np.load(path)) if os.path.exists(path) else {}
     for name in which:
+        path = os.path.join(REPO, "tests", "golden", OWN_FILE.get(name, "dynamics2.npz"))
+        out = dict(np.load(path)) if os.path.exists(path) else {}
         build, n_states = BUILDERS[name]
         system = build()
         t0 = time.time()
@@ -66,16 +73,18 @@ def main():
         out[name + "_states"] = np.arange(n_states)
         print(name, "%.1f s" % (time.time() - t0), {k.split("_", 1)[1] if False else k: out[k].shape for k in rec if k.endswith("dqdq") and "_f_" in k})
         np.savez_compressed(path, **out)
-    print("wrote %s (%.1f kB)" % (path, os.path.getsize(path) / 1e3))
+        print("wrote %s (%.1f kB)" % (path, os.path.getsize(path) / 1e3))
 
 
 def lagrangian_higher():
     """tests/golden/lagrangian_higher.npz: the reference's L_dqdqdq, L_ddqdqdq, L_ddqdqdqdq, L_ddqddqdq, L_ddqddqdqdq
     (system.py:869-949) for seeded index tuples (biased to the first 14 configs so that the puppet's tuples share kinematic chains)."""
     g = dict(np.load(os.path.join(REPO, "tests", "golden", "dynamics.npz")))
+    path = os.path.join(REPO, "tests", "golden", "lagrangian_higher.npz")
     out = {}
     rng = np.random.default_rng(5)     # systems are visited in a fixed order: appending one leaves the earlier tuples unchanged
-    for name in ("pendulum5", "scissor4", "puppet40", "spring_arm", "plane_link", "nonlinear_spring_arm"):
+    for name in ("pendulum5", "scissor4", "puppet40", "spring_arm", "plane_link", "nonlinear_spring_arm", "spatial_loop", "mixed_loop",
+                 "ladder_point", "ladder_mixed"):
         system = BUILDERS[name][0]()
         system.q, system.dq, system.u, system.ddqk = g[name + "_q"][0], g[name + "_dq"][0], g[name + "_u"][0], g[name + "_ddqk"][0]
         C = system.configs
@@ -87,7 +96,12 @@ def lagrangian_higher():
         out[name + "_idx"] = np.array(idx, dtype=np.int32)
         out[name + "_vals"] = np.array(vals)
         print(name, "largest |value| per accessor", np.abs(out[name + "_vals"]).max(axis=0), "non-zero", (np.abs(out[name + "_vals"]) > 1e-12).sum(axis=0))
-    np.savez_compressed(os.path.join(REPO, "tests", "golden", "lagrangian_higher.npz"), **out)
+    if os.path.exists(path):            # arrays already in the file stay as they are: only systems it does not hold yet are added
+        old = dict(np.load(path))
+        for k in old:       # the tuples exactly; the values to 1e-9 of the accessor's scale (another build of the reference may round otherwise)
+            assert np.array_equal(old[k], out[k]) or (k.endswith("_vals") and np.allclose(old[k], out[k], rtol=1e-9, atol=1e-9 * max(1.0, np.abs(old[k]).max()))), k
+        out.update(old)
+    np.savez_compressed(path, **out)
 
 
 if __name__ == "__main__":

@@ -35,14 +35,25 @@ BUILDERS = {
     "wrench_body": lambda: systems.wrench_body(api=trep),
     "damper_link": lambda: systems.damper_link(api=trep),
     "nonlinear_spring_arm": lambda: systems.nonlinear_spring_arm(api=trep),
+    "spatial_loop": lambda: systems.spatial_loop(api=trep),
+    "mixed_loop": lambda: systems.mixed_loop(api=trep),
+    "ladder_point": lambda: systems.ladder_point(api=trep),
+    "ladder_mixed": lambda: systems.ladder_mixed(api=trep),
 }
 N_STATES = 4
 
 
 def main():
+    # names on the command line: only those systems are computed and the other arrays of the file are kept as they are (a system's
+    # seed depends on its place in BUILDERS alone, so appending one leaves the earlier states unchanged)
+    which = sys.argv[1:] or list(BUILDERS)
+    path = os.path.join(REPO, "tests", "golden", "dynamics.npz")
+    kept = dict(np.load(path)) if sys.argv[1:] else {}
     out = {}
-    g = {n: np.load(os.path.join(REPO, "tests", "golden", n + ".npz")) for n in BUILDERS}
+    g = {n: np.load(os.path.join(REPO, "tests", "golden", n + ".npz")) for n in which}
     for si, (name, build) in enumerate(BUILDERS.items()):
+        if name not in which:
+            continue
         system = build()
         rng = np.random.default_rng(4100 + si)
         # configurations that satisfy the constraints: states of the recorded rollouts
@@ -79,7 +90,8 @@ def main():
             out[name + "_lam_du"].append(system.lambda_du())
         out[name + "_q"], out[name + "_dq"], out[name + "_u"], out[name + "_ddqk"] = qs, dqs, us, ddks
     out = dict((k, np.array(v)) for k, v in out.items())
-    np.savez_compressed(os.path.join(REPO, "tests", "golden", "dynamics.npz"), **out)
+    kept.update(out)
+    np.savez_compressed(path, **kept)
     for k in sorted(out):
         print(k, out[k].shape)
 

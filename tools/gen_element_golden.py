@@ -18,7 +18,8 @@ import trep.puppets  # noqa: E402
 from trep_amd import systems  # noqa: E402
 
 NAMES = ["pend_on_cart", "scissor4", "spring_arm", "nonlinear_spring_arm", "spring_link", "plane_link", "wrench_arm", "wrench_torque",
-         "wrench_spatial", "wrench_body", "damper_link", "extensor_tendon", "puppet_basic"]
+         "wrench_spatial", "wrench_body", "damper_link", "extensor_tendon", "puppet_basic", "spatial_loop", "mixed_loop", "ladder_point",
+         "ladder_mixed"]
 BUILD = {"pend_on_cart": systems.pend_on_cart, "scissor4": lambda api: systems.scissor_lift(4, api=api), "puppet_basic": systems.puppet_basic}
 POT = [("V", 0), ("V_dq", 1), ("V_dqdq", 2), ("V_dqdqdq", 3)]
 CON = [("h", 0), ("h_dq", 1), ("h_dqdq", 2), ("h_dqdqdq", 3), ("h_dqdqdqdq", 4)]
@@ -35,8 +36,10 @@ def tensor(fn, sets):
 
 
 def main():
-    out = {}
-    for name in NAMES:
+    # names on the command line: only those systems are computed, every other array of the file is kept as it is
+    path = os.path.join(REPO, "tests", "golden", "elements.npz")
+    out = dict(np.load(path)) if sys.argv[1:] else {}
+    for name in (sys.argv[1:] or NAMES):
         build = BUILD.get(name, None)
         system = build(api=trep) if build else getattr(systems, name)(api=trep)
         rng = np.random.default_rng(77)
@@ -65,6 +68,10 @@ def main():
                     continue
                 out["%s_force%d_%s" % (name, i, acc)] = tensor(getattr(force, acc), [C if ch == "q" else U for ch in sig])
         print(name, "potentials", len(system.potentials), "forces", len(system.forces), "constraints", len(system.constraints))
+    if sys.argv[1:]:
+        np.savez_compressed(path, **out)
+        print("wrote", path, os.path.getsize(path), "bytes,", len(out), "arrays")
+        return
     # MidpointVI.discrete_fm2 / set_midpoint (midpointvi.c:430-482, 2710-2728) on the wrench arm
     ref = systems.wrench_arm(api=trep)
     rng = np.random.default_rng(3)
@@ -90,7 +97,6 @@ def main():
     for acc, n in (("length", 0), ("length_dq", 1), ("length_dqdq", 2), ("length_dqdqdq", 3), ("velocity", 0), ("velocity_dq", 1),
                    ("velocity_dqdq", 2), ("velocity_ddq", 1), ("velocity_ddqdq", 2)):
         out["tape_" + acc] = tensor(getattr(tape, acc), [C] * n)
-    path = os.path.join(REPO, "tests", "golden", "elements.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path), "bytes,", len(out), "arrays")
 

@@ -451,6 +451,97 @@ def gen_extensor_tendon():
     save("extensor_tendon", **arrays)
 
 
+LOOP_N = 60
+
+
+def gen_small_loop(name, seed):
+    """spatial_loop / mixed_loop: closed at q = 0; two trajectories from rest under different kinematic schedules (and seeded inputs),
+    60 steps, first and full second derivative tensors at steps 1, 30, 60, DSystem captures."""
+    system = getattr(systems, name)(api=trep)
+    h0 = [c.h() for c in system.constraints]
+    print("  %s h(0) = %s" % (name, h0))
+    assert max(abs(h) for h in h0) <= 2.0 ** -56, h0      # closed by construction: a rounding of the plane product at most; recorded as h0
+    rng = np.random.default_rng(20250 + seed)
+    N = LOOP_N
+    t = DT * np.arange(1, N + 1)
+    arrays = dict(dt=DT, **topology(system))
+    arrays["input_names"] = np.array([str(u.name) for u in system.inputs])
+    arrays["h0"] = np.array(h0)
+    for b in range(2):
+        q0 = np.zeros(system.nQ)
+        U = rng.standard_normal((N, system.nu))
+        if name == "spatial_loop":
+            K = ((0.3, -0.2)[b] * np.sin((3.0, 4.0)[b] * t))[:, None]
+        else:       # config order: kr, lift
+            K = np.stack([(0.3, -0.25)[b] * np.sin(3.0 * t), (0.1, 0.15)[b] * np.sin((2.0, 5.0)[b] * t)], axis=1)
+            assert [c.name for c in system.kin_configs] == ["kr", "lift"]
+        r = rollout(system, q0, U, K, N, deriv_steps=(1, 30, N) if b == 0 else (), deriv2_full=True)
+        assert r["IT"].max() <= 6, r["IT"]
+        for key, val in r.items():
+            arrays["b%d_%s" % (b, key)] = val
+        arrays["b%d_q0" % b] = q0
+        arrays["b%d_U" % b] = U
+        arrays["b%d_K" % b] = K
+    ds = dsystem_captures(system, arrays["b0_Q"], arrays["b0_P"], arrays["b0_U"], arrays["b0_K"], (0, 10, 50), seed=seed)
+    save(name, **arrays, **ds)
+
+
+def consistent_pose(system, guess):
+    """A pose near `guess` that satisfies the constraints: the reference's own System.satisfy_constraints (SLSQP) where scipy is
+    installed, otherwise the numpy Newton projection of tests/projection_reference.py on the reference's h and h_dq; polished by
+    min-norm Newton steps on the reference's h to the rounding level either way."""
+    C = list(system.configs)
+
+    def ev(q):
+        system.q = q
+        return (np.array([c.h() for c in system.constraints]),
+                np.array([[c.h_dq(a) for a in C] for c in system.constraints]))
+    ev.nc = system.nc
+    try:
+        import scipy.optimize  # noqa: F401
+        system.q = guess
+        system.satisfy_constraints()
+        q = np.array(system.q)
+    except ImportError:
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+        import projection_reference
+        q = projection_reference.project_one(ev, np.array(guess, dtype=float), np.ones(len(C), dtype=bool), tolerance=1e-13)[0]
+    for _ in range(4):
+        h, Dh = ev(q)
+        q = q - np.linalg.lstsq(Dh, h, rcond=None)[0]
+    system.q = q
+    return q
+
+
+def gen_ladder(name, seed):
+    """ladder_point / ladder_mixed: the straight-down pose is singular (the tips' z does not move to first order), so the two starts
+    are seeded bent poses made consistent on the CPU; rollouts from rest, 60 steps, first derivatives and five second-derivative
+    tensors at steps 1, 30, 60, DSystem captures with the z-contracted second-order terms."""
+    system = getattr(systems, name)(api=trep)
+    rng = np.random.default_rng(20250 + seed)
+    N = LOOP_N
+    U = np.zeros((N, 0)); K = np.zeros((N, 0))
+    arrays = dict(dt=DT, **topology(system))
+    names = [c.name for c in system.configs]
+    select = ("q2_dq1dq1", "p2_dq1dp1", "l1_dq1dq1", "q2_dp1dp1", "p2_dp1dp1")
+    for b in range(2):
+        guess = 0.15 * rng.standard_normal(system.nQ)
+        # bend the chains towards each other (and up from the singular straight pose): a rotates about +x, b about -x
+        for n, sgn in (("a1x", 1.0), ("b1x", -1.0), ("a3x", -1.0), ("b3x", 1.0)):
+            guess[names.index(n)] += 0.5 * sgn
+        q0 = consistent_pose(system, guess)
+        hmax = max(abs(c.h()) for c in system.constraints)
+        assert hmax < 1e-12, hmax
+        r = rollout(system, q0, U, K, N, deriv_steps=(1, 30, N) if b == 0 else (), deriv2_select=select)
+        assert r["IT"].max() <= 6, r["IT"]
+        print("  %s start %d: |h| %.1e, iterations %s" % (name, b, hmax, np.bincount(r["IT"])))
+        for key, val in r.items():
+            arrays["b%d_%s" % (b, key)] = val
+        arrays["b%d_q0" % b] = q0
+    ds = dsystem_captures(system, arrays["b0_Q"], arrays["b0_P"], U, K, (0, 10, 50), seed=seed)
+    save(name, **arrays, **ds)
+
+
 def gen_discopt_cart():
     """One DOptimizer trace on the pend-on-cart problem of examples/pend-on-cart-optimization.py:48-116
     (torque input enabled, 5 s horizon): a few quasi-Newton then Newton steps; per step the method,
@@ -622,7 +713,15 @@ def gen_discopt_cart_nonuniform():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["known", "pend1", "pend5", "cart", "scissor", "puppet", "puppet_basic", "spring_arm", "nonlinear_spring_arm", "spring_link", "plane_link", "wrench_arm", "puppet_forces", "extensor_tendon", "wrench_torque", "dual_pendulums", "wrench_spatial", "wrench_body", "damper_link", "discopt", "discopt_puppet", "discopt_nonuniform"]
+    which = sys.argv[1:] or ["known", "pend1", "pend5", "cart", "scissor", "puppet", "puppet_basic", "spring_arm", "nonlinear_spring_arm", "spring_link", "plane_link", "wrench_arm", "puppet_forces", "extensor_tendon", "wrench_torque", "dual_pendulums", "wrench_spatial", "wrench_body", "damper_link", "discopt", "discopt_puppet", "discopt_nonuniform", "spatial_loop", "mixed_loop", "ladder_point", "ladder_mixed"]
+    if "spatial_loop" in which:
+        gen_small_loop("spatial_loop", seed=41)
+    if "mixed_loop" in which:
+        gen_small_loop("mixed_loop", seed=42)
+    if "ladder_point" in which:
+        gen_ladder("ladder_point", seed=43)
+    if "ladder_mixed" in which:
+        gen_ladder("ladder_mixed", seed=44)
     if "known" in which:
         gen_known_answer()
     if "pend1" in which:

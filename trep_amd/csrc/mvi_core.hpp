@@ -1870,10 +1870,12 @@ struct Core {
         // ---- phase C: the image (the whole union: poses and BW are dead now) is cleared; per config b: I s_b, Z_b = Y_b + I w_b, GG_b
         {
             typedef double tg_d2 __attribute__((ext_vector_type(2)));
-            static_assert(((SP::o_Df | (nf * ld)) & 1) == 0, "newton_matrix_composite: image not 16-byte aligned");
+            static_assert((SP::o_Df & 1) == 0, "newton_matrix_composite: image not 16-byte aligned");
             tg_d2 *A2 = reinterpret_cast<tg_d2 *>(A);
             const tg_d2 z2 = {0.0, 0.0};
             if (on) TG_FOR(i, (nf * ld) >> 1) A2[i] = z2;
+            // an odd nf has an odd row stride nf + 2, so an odd image: its last element (the padding column of the last row) on its own
+            if constexpr ((nf * ld) & 1) { if (on && lane == 0) A[nf * ld - 1] = 0.0; }
         }
         if (on && lane < nd) {
             const double *c = CMP + 16 * (rep[lane] >> 20);
@@ -1955,10 +1957,11 @@ struct Core {
         // converges -- one in four -- would form the vectors and clear the image in vain; measured 30.4 against 30.0 and 30.6 against 30.2 ms)
         {
             typedef double tg_d2 __attribute__((ext_vector_type(2)));
-            static_assert(((SP::o_Df | NCLEAR) & 1) == 0, "newton_matrix_world: image not 16-byte aligned");
+            static_assert((SP::o_Df & 1) == 0, "newton_matrix_world: image not 16-byte aligned");
             tg_d2 *A2 = reinterpret_cast<tg_d2 *>(A);
             const tg_d2 z2 = {0.0, 0.0};
             if (on) TG_FOR(i, NCLEAR >> 1) A2[i] = z2;
+            if constexpr (NCLEAR & 1) { if (on && lane == 0) A[NCLEAR - 1] = 0.0; }      // (odd image: see newton_matrix_composite)
         }
         const double qdt = 0.25 * dt, rdt = inv_dt;
         // the entries (a, b) and (b, a) of every prefix config a above the lane's config b: s_a = (e_x, 0) and w_a = 0 exactly, so of the four

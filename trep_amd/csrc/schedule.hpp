@@ -104,6 +104,7 @@ struct ScheduleBuilder {
     std::map<int, int> ep_of_frame;
     std::vector<int> pose_need;      // bit 0: the midpoint pose of joint j is read (a body hangs below it), bit 1: its q2 pose (a constraint end point does)
     int off = 0;      // LDS layout cursor (doubles from the team's base)
+    static constexpr int kCompositeMinNd = 8;      // smallest nd the composite form (and with it the world-frame evaluation) takes: composite_form(), and the 16-byte alignment of what it reads (counts_and_step_layout)
     int take(int n) { int o = off; off += (n > 0 ? n : 0); return o; }
 
     explicit ScheduleBuilder(const tg_system_desc *desc) : d(desc), P(H.p), nfr(desc->n_frames), nq(desc->n_configs), nd(desc->n_dyn), nc(desc->n_constraints) {}
@@ -489,6 +490,10 @@ inline void ScheduleBuilder::counts_and_step_layout() {
     P.o_J = take(6 * nitems); P.o_W = take(6 * nitems); P.o_vB = take(6 * nb); P.o_gam = take(3 * nb);
     P.o_Ldq = take(nd); P.o_Lddq = take(nd); P.o_Dh1 = take(P.n_dh); P.o_Dh2 = take(P.n_dh);  // compact: one value per (constraint, dependent config) item
     P.o_scal = take(P.nf); P.o_misc = take(2); P.o_nu = take(P.nu + P.nk);
+    // the world-frame evaluation reads a body's four inertia entries and clears the matrix image with 16-byte LDS accesses (mvi_core.hpp,
+    // eval_world / newton_matrix_composite): both on an even double for every system it can take (kCompositeMinNd).  An
+    // odd nf puts o_scal's end on an odd one.
+    if (nd >= kCompositeMinNd) off = (off + 1) & ~1;
     P.o_I = take(4 * nb);   // mass and principal inertias of every body (copied from the table once per kernel)
     P.o_ctol = take(nc);    // constraint tolerances, likewise
     P.o_sV = take(ns ? nq : 0); P.o_sH = take(P.n_spair);   // spring gradient per dynamic config, Hessian per item pair (midpoint)
@@ -563,6 +568,7 @@ inline void ScheduleBuilder::sweep_lists_and_plan() {
 // the Newton matrix and the poses share storage; end of the step layout.  Then the first-derivative kernel's arrays behind it
 inline void ScheduleBuilder::layout_pose_union_and_deriv1() {
     P.df_ld = (P.nf + 1) | 1;  // augmented with the right-hand side; odd stride avoids LDS bank conflicts
+    if (nd >= kCompositeMinNd) off = (off + 1) & ~1;      // (the image on an even double: see o_I in counts_and_step_layout)
     const int shared0 = off;
     P.o_Df = take(P.nf * P.df_ld);
     const int end_df = off;
@@ -743,7 +749,7 @@ inline void ScheduleBuilder::composite_form() {
         }
     }
     const int need = 16 * (int)group_of.size() + 27 * nd;                      // J / W area
-    if (all_rep && nd >= 8 && nd <= 64 && nb <= 32 && group_of.size() <= 32 && from_pairs == from_cmp && need <= 12 * nitems && nitems < 4096 &&
+    if (all_rep && nd >= kCompositeMinNd && nd <= 64 && nb <= 32 && group_of.size() <= 32 && from_pairs == from_cmp && need <= 12 * nitems && nitems < 4096 &&
         17 * nb <= 2 * nj + std::max(12 * nj, 2 * nitems)) {      // (the per-body entries, 17 doubles apart: sin / cos + joint-pose area, dead by then)
         P.cmp_ok = 1; P.n_cgroups = (int)group_of.size(); P.n_cmpairs = (int)H.cmp_pair.size();
         P.o_cmp = P.o_J; P.o_csw = P.o_cmp + 16 * P.n_cgroups; P.o_ccz = P.o_csw + 12 * nd;

@@ -241,6 +241,124 @@ def wrench_body(api=None):
     return system
 
 
+def _rot(axis, angle):
+    c, s = math.cos(angle), math.sin(angle)
+    i, j = {"x": (1, 2), "y": (2, 0), "z": (0, 1)}[axis]
+    R = np.eye(3)
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    return R
+
+
+def _se3(R, p=(0.0, 0.0, 0.0)):
+    """The (x axis, y axis, z axis, origin) form const_se3 takes, from a rotation matrix and a position."""
+    R = np.asarray(R, dtype=float)
+    return [[float(v) for v in R[:, 0]], [float(v) for v in R[:, 1]], [float(v) for v in R[:, 2]], [float(v) for v in p]]
+
+
+def _offsets(T, p, children):
+    """Constant tx, ty, tz frames down to the point p, then `children`."""
+    return [T.tx(float(p[0])), [T.ty(float(p[1])), [T.tz(float(p[2])), children]]]
+
+
+def spatial_loop(api=None):
+    """An out-of-plane closed loop: a six-joint spatial arm behind a kinematic rz and a constant rotation, and a telescopic
+    two-joint arm on a fixed pivot, their tips joined by PointToPoint3D.  Closed at q = 0 by construction (the pivot sits one unit
+    above the first tip's zero-configuration position).  Synthetic test system: all three point components, a kinematic rotary
+    config at the root, a const_se3 with a rotation, tx / ty / tz links."""
+    T = _api(api)
+    R0, p0 = _rot("x", 0.4), np.array([0.2, 0.1, 0.0])
+    tip = p0 + R0.dot([0.8, 0.6, -1.0])
+    system = T.System()
+    system.import_frames([
+        T.rz('turn', name='Turn', kinematic=True), [
+            T.const_se3(_se3(R0, p0), name='Tilt'), [
+                T.rx('a'), [T.tz(-1.0, name='A1', mass=2.0), [
+                    T.ry('b'), [T.tx(0.8, name='A2', mass=(1.0, 0.1, 0.2, 0.3)), [
+                        T.rz('c'), [T.ty(0.6, name='TipA', mass=0.5)]]]]]]]] +
+        _offsets(T, tip + [0.0, 0.0, 1.0], [
+            T.rz('d'), [T.rx('e'), [T.tz('s'), [T.tz(-1.0, name='TipB', mass=1.5)]]]]))
+    T.potentials.Gravity(system, (0.5, -1.0, -9.8))
+    T.forces.Damping(system, 0.1)
+    T.constraints.PointToPoint3D(system, 'TipA', 'TipB')
+    return system
+
+
+MIXED_LOOP_NORMAL = (0.2, 1.0, 0.1)
+
+
+def mixed_loop(api=None):
+    """A planar two-arm loop closed in y and z (PointToPoint2D 'yz') with a kinematic rotary joint in the middle of one chain and a
+    kinematic tz under the other, and a side point held in a plane whose frame sits behind a constant rotation Ry(0.3) Rx(-0.2) on a
+    third, rotating branch (the normal is carried through that rotation).  A ConfigForce and a BodyWrench with two inputs.  Closed at
+    q = 0: the plane frame is placed 0.4 from the side point along a direction orthogonal to the rotated normal.  Synthetic test
+    system."""
+    T = _api(api)
+    Rp = _rot("y", 0.3).dot(_rot("x", -0.2))
+    nw = Rp.dot(MIXED_LOOP_NORMAL)
+    o = np.cross(nw, [0.0, 1.0, 0.0])
+    o /= np.linalg.norm(o)
+    side, tip = np.array([0.3, 0.5, -1.0]), np.array([0.0, 0.5, -2.4])
+    system = T.System()
+    system.import_frames([
+        T.ty(0.5), [T.rx('a'), [T.tz(-1.0, name='L1', mass=2.0), [
+            T.tx(0.3, name='Side'),
+            T.rx('kr', name='Knee', kinematic=True), [T.tz(-0.8, name='L2', mass=(1.0, 0.1, 0.2, 0.3)), [
+                T.rx('b'), [T.tz(-0.6, name='TipA', mass=0.5)]]]]]],
+        T.tz('lift', name='Lift', kinematic=True), _offsets(T, tip + [0.0, 0.0, 0.9], [
+            T.rx('c'), [T.tz('s'), [T.tz(-0.9, name='TipB', mass=1.5)]]])] +
+        _offsets(T, side + 0.4 * o, [
+            T.rz('d'), [T.tx(0.5, name='Vane', mass=1.0),
+                        T.const_se3(_se3(Rp), name='Plane')]]))
+    T.potentials.Gravity(system, (0.0, -1.0, -9.8))
+    T.forces.Damping(system, 0.1)
+    T.constraints.PointToPoint2D(system, 'yz', 'TipA', 'TipB')
+    T.constraints.PointOnPlane(system, 'Plane', MIXED_LOOP_NORMAL, 'Side')
+    T.forces.ConfigForce(system, 'a', 'a-torque')
+    T.forces.BodyWrench(system, 'TipA', (0, 'tip-fy', 0.3, 'tip-tx', 0, 0), name='tip')
+    return system
+
+
+def _ladder_chain(T, side, y, bent):
+    """Four links of rx, ry, tz -1 hanging from ty(y); bent: the body of link 2 (and what hangs below it) sits behind a constant
+    rz(0.3) under its joints."""
+    chain = [T.tz(-0.5, name=side + 'Tip', mass=0.5)]
+    for link in (4, 3, 2, 1):
+        body = [T.tz(-1.0, name='%sL%d' % (side, link), mass=(1.0, 0.1, 0.2, 0.3)), chain]
+        if bent and link == 2:
+            body = [T.rz(0.3), body]
+        chain = [T.rx('%s%dx' % (side, link)), [T.ry('%s%dy' % (side, link)), body]]
+    return [T.ty(y), chain]
+
+
+def ladder_point(api=None):
+    """Two spatial chains of four rx / ry links each, their tips joined by PointToPoint3D: 16 dynamic configs, 3 constraints, an odd
+    Newton system (nf = 19) on the world-frame path of the specialised kernel.  The straight-down pose is singular; consistent bent
+    starts are recorded in tests/golden/ladder_point.npz.  Synthetic test system."""
+    T = _api(api)
+    system = T.System()
+    system.import_frames(_ladder_chain(T, 'a', -0.5, False) + _ladder_chain(T, 'b', 0.5, False))
+    T.potentials.Gravity(system, (0.0, 0.0, -9.8))
+    T.forces.Damping(system, 0.1)
+    T.constraints.PointToPoint3D(system, 'aTip', 'bTip')
+    return system
+
+
+def ladder_mixed(api=None):
+    """The chains of ladder_point with link 2 of each behind a constant rz(0.3), closed by one constraint of each kind: the tips meet
+    in x and y (PointToPoint2D 'xy'), one tip stays in a tilted fixed plane (PointOnPlane) and the first links keep their distance
+    (Distance): nf = 20.  Starts as for ladder_point (tests/golden/ladder_mixed.npz).  Synthetic test system."""
+    T = _api(api)
+    system = T.System()
+    system.import_frames(_ladder_chain(T, 'a', -0.5, True) + _ladder_chain(T, 'b', 0.5, True) +
+                         [T.tz(-4.0), [T.ry(0.2, name='Floor')]])
+    T.potentials.Gravity(system, (0.0, 0.0, -9.8))
+    T.forces.Damping(system, 0.1)
+    T.constraints.PointToPoint2D(system, 'xy', 'aTip', 'bTip')
+    T.constraints.PointOnPlane(system, 'Floor', (0.1, 0.2, 1.0), 'aTip')
+    T.constraints.Distance(system, 'aL1', 'bL1', 1.0)
+    return system
+
+
 def dual_pendulums(api=None):
     """examples/dual_pendulums.py:28-44: two pendulums on neighbouring pivots joined by a linear spring and a linear
     damper, under gravity."""
