@@ -17,20 +17,31 @@
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TG_WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_s_barrier(); \
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
+// TG_RSYNC: the phase boundary of code that only the ROLLOUT runs (eval_world, newton_matrix_world, the rollout loop of
+// run_trajectory, pose_sweep_dual on the rollout's lists).  In a build with helper waves the team is a full wavefront and the rollout's
+// workgroup is that one wave: nobody else reads its LDS slice, and the LDS operations of a wave execute in the order they were issued.  A
+// wavefront-scope fence is then enough -- it orders the compiler's accesses and emits no instruction, where each workgroup-scope release
+// drains every LDS operation in flight (s_waitcnt lgkmcnt(0)); a read is still waited for, counted, before its value is used.
+// Everywhere else it is TG_SYNC.
 #if defined(TG_HELPER_WAVES)
 #define TG_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local"); __builtin_amdgcn_wave_barrier(); \
                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); } while (0)
+#define TG_RSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local"); __builtin_amdgcn_wave_barrier(); \
+                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local"); } while (0)
 #else
 #define TG_SYNC() TG_WSYNC()
+#define TG_RSYNC() TG_SYNC()
 #endif
 #else
 #define TG_SYNC() ((void)0)
 #define TG_WSYNC() ((void)0)
+#define TG_RSYNC() ((void)0)
 #endif
 #else
 #define TG_HD inline
 #define TG_SYNC() ((void)0)
 #define TG_WSYNC() ((void)0)
+#define TG_RSYNC() ((void)0)
 #endif
 
 #if defined(__HIPCC__)

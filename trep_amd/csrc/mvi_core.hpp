@@ -718,7 +718,7 @@ struct Core {
                     }
                 }
             }
-            TG_SYNC();
+            if (rollout_lists) TG_RSYNC(); else TG_SYNC();
             TG_STAMP(5);
             TG_STAMP(15);
         } else {
@@ -947,7 +947,7 @@ struct Core {
                     }
                 }
             }
-            TG_SYNC();
+            TG_RSYNC();
             chain_round_quads<SP, RD + 1>(on, sched, nxt);
         }
     }
@@ -1293,14 +1293,14 @@ struct Core {
     //   E6  lane k < nd: L_dq, L_ddq, forces, the residual entry.
     // Five phases of one trip each instead of eight (three of them two trips); verified against the reference's L_dq / L_ddq in
     // tools/proto/world_eval.py (1e-16) before it was written here.  The derivative kernels keep the item form (they need J and W).
-    template <int D0, int D1> TG_HD void wev_sum(const double *SW, double (&V)[6]) const {
-        // V += the u-halves of list entries D0 .. D1-1 (padded entries point at the all-zero record): every load before the adds
+    template <int D0, int D1> TG_HD void wev_sum(const double *SU, double (&V)[6]) const {
+        // V += the u records of list entries D0 .. D1-1 (padded entries point at the all-zero record): every load before the adds
         if constexpr (D0 < D1) {
             double x[D1 - D0][6];
 #pragma unroll
             for (int d = D0; d < D1; d++) {
                 const int idx = (wvl[d >> 2] >> (8 * (d & 3))) & 0xFF;
-                ld6<true>(SW + 12 * idx + 6, x[d - D0]);
+                ld6<true>(SU + 6 * idx, x[d - D0]);
             }
 #pragma unroll
             for (int d = D0; d < D1; d++) {
@@ -1315,7 +1315,12 @@ struct Core {
         constexpr int nd = SP::nd, NB = SP::n_bodies, NG = SP::n_cgroups, MAXD = FB ? SP::fb_depth : SP::wev_depth;
         static_assert(TEAM == 64 && nd + 3 * NB < 64, "eval_world: one lane per config and per (body, axis), and the last lane free");
         static_assert(!FB || nd + 3 * NB < 63, "eval_world: the prefix record needs a second lane without a role");
-        static_assert((SP::o_csw & 1) == 0 && (SP::o_I & 1) == 0 && (SP::o_cmp & 1) == 0 && (SP::o_G & 1) == 0, "eval_world: 16-byte LDS accesses");
+        // twist records: NREC of them (the configs, the zero record, the prefix record), s in [SW, SW + 6 NREC), u -- later w -- in
+        // [SU, SU + 6 NREC).  6 doubles apart a 16-byte access of 64 lanes has no bank conflict; the 12 of one (s | u) record had a
+        // two-way one on every access.  NREC from where the schedule puts o_ccz: the area is the same, only its inside is rearranged.
+        constexpr int NREC = (SP::o_ccz - SP::o_csw) / 12;
+        static_assert((SP::o_ccz - SP::o_csw) % 12 == 0 && NREC == nd + (FB ? 2 : 1), "eval_world: the twist area holds nd + 1 records, nd + 2 with a prefix");
+        static_assert((SP::o_csw & 1) == 0 && ((SP::o_csw + 6 * NREC) & 1) == 0 && (SP::o_I & 1) == 0 && (SP::o_cmp & 1) == 0 && (SP::o_G & 1) == 0, "eval_world: 16-byte LDS accesses");
         // table rows of E3, requested ahead of the pose sweep: the end point's anchor row (as fetch_attach), the body lane's constant offset
         const int l0 = tg_opaque(lane);
         const bool blane = l0 >= nd && l0 < nd + 3 * NB;
@@ -1332,7 +1337,7 @@ struct Core {
         const int banc = P.b_anchor[wb_];
         if (!rates_ready) {
             if (on) TG_FOR(i, P.nq) S[P.o_dq + i] = (S[P.o_q2 + i] - S[P.o_q1 + i]) / dt;
-            TG_SYNC();
+            TG_RSYNC();
         }
         TG_STAMP(0);
         pose_sweep_dual(on, true);
@@ -1340,7 +1345,7 @@ struct Core {
         const double *G = S + P.o_G, *G2 = S + P.o_W;
         // per-body world entries: behind the q2 poses in the W area (with the dead body-velocity / gravity vectors that follow it) -- the body
         // lanes write them while other lanes still read the midpoint poses
-        double *SW = S + P.o_csw, *CMP = S + P.o_cmp, *BW = S + P.o_W + 12 * P.n_joints;
+        double *SW = S + P.o_csw, *SU = SW + 6 * NREC, *CMP = S + P.o_cmp, *BW = S + P.o_W + 12 * P.n_joints;
         constexpr int BWS = 17;
         static_assert(12 * SP::n_joints + BWS * NB <= 6 * SP::n_items + 9 * NB, "eval_world: body entries do not fit behind the q2 poses");
         // ---- E3: constraint end points (q2 poses); lane k <= nd: world twist of config k; lane (body b, axis r): the body's world pose
@@ -1377,8 +1382,8 @@ struct Core {
 #pragma unroll
                     for (int i = 0; i < SP::fb_n; i++) { const double dqa = S[P.o_dq + SP::fb_cfg[i]]; uv[SP::fb_axis[i]] = lane == TEAM - 2 ? dqa : uv[SP::fb_axis[i]]; }
                 }
-                st6<true>(SW + 12 * rec, sv);
-                st6<true>(SW + 12 * rec + 6, uv);
+                st6<true>(SW + 6 * rec, sv);
+                st6<true>(SU + 6 * rec, uv);
             } else if (blane) {
                 const int b = wb_, r = wr_;
                 const double *ga = G + 12 * (banc < 0 ? 0 : banc);
@@ -1420,7 +1425,7 @@ struct Core {
                 bD0 = Dr[0]; bD1 = Dr[1]; bD2 = Dr[2]; bC0 = m * p[0]; bC1 = m * p[1]; bC2 = m * p[2]; bm = m;
             }
         }
-        TG_SYNC();
+        TG_RSYNC();
         TG_STAMP(2);
         // ---- E4: constraint values and Dh2 at q2 (constraints(on, 2, true, Dh2, 0)) ----
         const ResTab rt = fetch_residual();
@@ -1480,11 +1485,11 @@ struct Core {
             {
                 double V[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
                 constexpr int HALF = (MAXD + 1) / 2;
-                wev_sum<0, HALF>(SW, V);
-                wev_sum<HALF, MAXD>(SW, V);
+                wev_sum<0, HALF>(SU, V);
+                wev_sum<HALF, MAXD>(SU, V);
                 if (lane < nd) {
                     double sk[6];
-                    ld6<true>(SW + 12 * lane, sk);
+                    ld6<true>(SW + 6 * lane, sk);
                     bracket(V, sk, wev_w);
                 } else if (blane) {
                     const int r = wr_;
@@ -1498,7 +1503,7 @@ struct Core {
                 }
             }
         }
-        TG_SYNC();
+        TG_RSYNC();
         TG_STAMP(6);
         // ---- E5: composites of the subtree groups (lane = entry; membership is compile-time)
         if (on && lane < 16) {
@@ -1510,7 +1515,7 @@ struct Core {
                 CMP[16 * g + lane] = acc;
             }
         }
-        TG_SYNC();
+        TG_RSYNC();
         TG_STAMP(3);
         // ---- E6: L_dq, L_ddq and the residual entry of config k ----
         if (on && lane < nd) {
@@ -1518,7 +1523,7 @@ struct Core {
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3];
             const double h0 = c[10], h1 = c[11], h2 = c[12], h3 = c[13], h4 = c[14], h5 = c[15];
             double sk[6];
-            ld6<true>(SW + 12 * lane, sk);
+            ld6<true>(SW + 6 * lane, sk);
             const double *w = wev_w;
             const double lddq = sk[0] * h0 + sk[1] * h1 + sk[2] * h2 + sk[3] * h3 + sk[4] * h4 + sk[5] * h5;
             const double Gx = M * sk[0] + (sk[4] * Cz - sk[5] * Cy), Gy = M * sk[1] + (sk[5] * Cx - sk[3] * Cz), Gz = M * sk[2] + (sk[3] * Cy - sk[4] * Cx);
@@ -1951,8 +1956,8 @@ struct Core {
         constexpr int nd = SP::nd, nf = SP::nf, ld = SP::df_ld, NP = FB ? SP::fb_npairs : SP::n_cmpairs;
         constexpr int NCLEAR = PK ? SP::bbd_pk_size : nf * ld;
         constexpr int TP = (NP + TEAM - 1) / TEAM;
-        double *A = S + P.o_Df, *SW = S + P.o_csw, *CZ = S + P.o_ccz;
-        constexpr int SWS = 12;
+        constexpr int NREC = (SP::o_ccz - SP::o_csw) / 12;      // (eval_world's two arrays of 6-double records: s, then u -- from here on w)
+        double *A = S + P.o_Df, *SW = S + P.o_csw, *SU = SW + 6 * NREC, *CZ = S + P.o_ccz;
         // phase C: the image is cleared, per config b: I s_b, Z_b = Y_b + I w_b, GG_b (both here and not in eval_world: an evaluation that
         // converges -- one in four -- would form the vectors and clear the image in vain; measured 30.4 against 30.0 and 30.6 against 30.2 ms)
         {
@@ -1988,7 +1993,7 @@ struct Core {
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3], Dxx = c[4], Dxy = c[5], Dxz = c[6], Dyy = c[7], Dyz = c[8], Dzz = c[9];
             const double h0 = c[10], h1 = c[11], h2 = c[12], h3 = c[13], h4 = c[14], h5 = c[15];
             double s[6];
-            ld6<true>(SW + SWS * lane, s);
+            ld6<true>(SW + 6 * lane, s);
             const double *w = wev_w;
             auto apply = [&](const double *x, double *y) {
                 y[0] = M * x[0] - (Cy * x[5] - Cz * x[4]); y[1] = M * x[1] - (Cz * x[3] - Cx * x[5]); y[2] = M * x[2] - (Cx * x[4] - Cy * x[3]);
@@ -2010,10 +2015,10 @@ struct Core {
 #pragma unroll
             for (int r = 0; r < 6; r++) { o[r] = Is[r]; o[6 + r] = Z[r]; }
             o[12] = Gy * gz - Gz * gy; o[13] = Gz * gx - Gx * gz; o[14] = Gx * gy - Gy * gx;
-            st6<true>(SW + SWS * lane + 6, wev_w);
+            st6<true>(SU + 6 * lane, wev_w);
             closed_forms(Is, Z);
         }
-        TG_SYNC();
+        TG_RSYNC();
         TG_STAMP(7);
         // ---- phase D: the constant entries (right-hand side, damping, -Dh1' / Dh2) and the config pairs: one lane per pair
         if (on) {
@@ -2032,7 +2037,7 @@ struct Core {
             if (on && lane + u * TEAM < NP) {
                 constexpr bool PKW = tg_static_pk<SP>::value;       // (which form the lane's pair records have, whichever image is written)
                 const int a = PKW ? wpair[u] & 63 : wpair[u] & 0xFFFF, b = PKW ? (wpair[u] >> 6) & 63 : wpair[u] >> 16;
-                const double *sa = SW + SWS * a, *wa = sa + 6, *Is = CZ + 15 * b, *Z = Is + 6, *GG = Is + 12;
+                const double *sa = SW + 6 * a, *wa = SU + 6 * a,*Is = CZ + 15 * b, *Z = Is + 6, *GG = Is + 12;
                 double s_[6], w_[6], i_[6], z_[6];
 #pragma unroll
                 for (int r = 0; r < 6; r++) { s_[r] = sa[r]; w_[r] = wa[r]; i_[r] = Is[r]; z_[r] = Z[r]; }
@@ -2046,7 +2051,7 @@ struct Core {
                 else { A[e_ab] = sym + (a != b ? skew : 0.0); if (a != b) A[e_ba] = sym - skew; }
             }
         }
-        TG_SYNC();
+        TG_RSYNC();
         TG_STAMP(8);
     }
 #endif
@@ -4539,8 +4544,12 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
     int status = TG_OK, total_iters = 0, n_fallback = 0;
     // open-loop inputs and kinematic targets of the NEXT step, requested while this step's Newton loop runs (one value per lane when they
     // fit a team): read at the step's start they are two HBM round trips in a row on every step's critical path
+    // (the target of kinematic config j waits on lane nd + j -- the lane that owns entry nd + j of q1, q2 and the rates -- when the
+    // configs fit a team, on lane j otherwise)
     double pre_u = 0.0, pre_k = 0.0;
     bool pre_ok = false;
+    // the step edge (below, behind the Newton loop) has already done this step's set-up: full-wave teams on the open-loop reference path
+    bool edge_done = false;
     for (int step = 0; step < A.n_steps; step++) {
         PROG &P = tg_rebind(P0);
         ARGS &A = tg_fresh_args(A0);      // per step: nothing of the arguments stays in SGPRs across steps
@@ -4572,7 +4581,7 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                     dx[i] = x - bx[i];
                 }
             }
-            TG_SYNC();
+            TG_RSYNC();
             if (on && step > 0 && mine) {
                 double kv[32];
 #pragma unroll
@@ -4587,14 +4596,14 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 }
                 part[pt * nU + j] = (a0 + a1) + (a2 + a3);
             }
-            TG_SYNC();
+            TG_RSYNC();
             if (on && l < nU) {
                 double acc = A.bU[(t * A.n_steps + step) * nU + l];
                 if (step > 0) for (int q = 0; q < parts; q++) acc -= part[q * nU + l];   // X_0 = bX_0 by definition of the projection: no correction at k = 0
                 S[P.o_nu + l] = acc;
                 if (A.Uout) A.Uout[(t * A.n_steps + step) * nU + l] = acc;
             }
-            TG_SYNC();
+            TG_RSYNC();
             fb_done = true;
         }
 #endif
@@ -4618,9 +4627,13 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 S[P.o_nu + j] = acc;
                 if (A.Uout) A.Uout[(t * A.n_steps + step) * nU + j] = acc;
             }
-            TG_SYNC();
+            TG_RSYNC();
         }
+        const bool edged = edge_done;      // (wave-uniform: only a full-wave team ever sets it)
+        edge_done = false;
+        const int pre_kl = nq <= TEAM ? lane - nd : lane;      // the kinematic config whose prefetched target this lane holds
         // advance: q1 <- q2, (p1 already holds p2), inputs, kinematic targets, hints (midpointvi.py:188-197)
+        if (!edged) {
         if (on) {
             if (A.predictor) {   // opt-in warm start: constant-velocity extrapolation of the dynamic configs
                 // constant velocity, not constant displacement: on a non-uniform time base the last displacement is scaled by
@@ -4641,14 +4654,15 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
             // the momentum entering the last step is the state's p1 afterwards (midpointvi.py:189)
             if (step == A.n_steps - 1) TG_FOR(i, nd) A.p1[t * nd + i] = S[P.o_p1 + i];
         }
-        TG_SYNC();
+        TG_RSYNC();
         if (on) {
-            if (pre_ok) { if (lane < nk) S[P.o_q2 + nd + lane] = pre_k; }
+            if (pre_ok) { if (pre_kl >= 0 && pre_kl < nk) S[P.o_q2 + nd + pre_kl] = pre_k; }
             else TG_FOR(i, nk) S[P.o_q2 + nd + i] = A.Kproj ? S[P.o_nu + nu + i] : A.K[(t * A.n_steps + step) * nk + i];
             if (A.q2_hint && step == 0) TG_FOR(i, nd) S[P.o_q2 + i] = A.q2_hint[t * nd + i];
             if (A.lam_hint && step == 0) TG_FOR(i, nc) S[P.o_lam + i] = A.lam_hint[t * nc + i];
         }
-        TG_SYNC();
+        TG_RSYNC();
+        }
         // Dh at q1, held fixed during the solve (midpointvi.c:705-707).  After the first step it is the
         // Dh2 of the previous step's converged q2 (same point, same inputs), so only step 0 sweeps.
         // rates dq = (q2 - q1) / dt of the first evaluation: here (no reader before the barriers below) and, for the later evaluations, in the
@@ -4659,18 +4673,20 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
         const bool fuse_rates = false;
 #endif
         core.rates_ready = fuse_rates;
+        if (!edged) {
         if (fuse_rates && on) TG_FOR(i, nq) S[P.o_dq + i] = core.over_dt(S[P.o_q2 + i] - S[P.o_q1 + i]);
         if (step == 0) core.eval_constraints(on, 1, false, S + P.o_Dh1);
         else if (nc) {
             if (on) TG_FOR(i, P.n_dh) S[P.o_Dh1 + i] = S[P.o_Dh2 + i];
-            TG_SYNC();
+            TG_RSYNC();
+        }
         }
         int iterations = 0;
         bool done = !on;
         pre_ok = false;
         if (TEAM == 64 && on && !A.Kproj && nu <= TEAM && nk <= TEAM && step + 1 < A.n_steps) {
             if (lane < nu) pre_u = A.U[(t * A.n_steps + step + 1) * nu + lane];
-            if (lane < nk) pre_k = A.K[(t * A.n_steps + step + 1) * nk + lane];
+            if (pre_kl >= 0 && pre_kl < nk) pre_k = A.K[(t * A.n_steps + step + 1) * nk + pre_kl];
             pre_ok = true;
         }
 #if defined(TG_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
@@ -4742,14 +4758,14 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                             const double x = S[P.o_Df + (at >= 0 ? at : 0)];
                             v[u] = at >= 0 ? x : 0.0;
                         }
-                        TG_SYNC();
+                        TG_RSYNC();
                         if constexpr (SP::df_ld > SP::nf + 1) { TG_FOR(i, SP::nf) S[P.o_Df + i * SP::df_ld + SP::nf + 1] = 0.0; }      // (the padding column of an odd row stride)
 #pragma unroll
                         for (int u = 0; u < PER; u++) {
                             const int e = lane + u * TEAM;
                             if (e < NE) S[P.o_Df + (e / (SP::nf + 1)) * SP::df_ld + e % (SP::nf + 1)] = v[u];
                         }
-                        TG_SYNC();
+                        TG_RSYNC();
                     }
                 }
                 __builtin_amdgcn_s_setprio(0);
@@ -4825,19 +4841,54 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
                 }
                 iterations++;
             }
-            TG_SYNC();
+            TG_RSYNC();
         }
+        // The step edge.  Between the converged evaluation of this step and the first evaluation of the next the wave would pass four
+        // fences with a handful of stores between them (p1 | the X row, q1 <- q2, inputs | kinematic targets | rates, Dh1 <- Dh2).  Every
+        // value written there is a function of entry i of the lane's own (or, for kinematic config j, entry nd + j), so a full-wave team
+        // whose configs fit the wave does all of it on lane i in ONE phase: the same expressions on the same operands, in the order a
+        // non-uniform time base needs -- the X row with the finished step's dt, the rates with the next one's.  Open-loop reference path
+        // only (the next step's inputs and targets prefetched, no feedback, no extrapolation); a last, failed or frozen step, step 0 and
+        // every other team take the phases as they were.
+        if (TEAM == 64 && on && !failed && pre_ok && !A.predictor && fuse_rates && nq <= TEAM) {
+            total_iters += iterations;
+            if (A.dt_steps && A.dt_period == 0) { const double dt_next = A.dt_steps[step + 1]; core.dt = dt_next; core.inv_dt = 1.0 / dt_next; }   // (as the head of the next step will)
+            const int i = tg_opaque(lane);
+            if (i < nq) {
+                const double q2i = S[P.o_q2 + i], q1i = S[P.o_q1 + i];
+                // p2 = D2L2 at the converged midpoint; it becomes p1 of the next step (and the state's p1 when that step is the last)
+                const double p = 0.5 * dt * S[P.o_Ldq + (i < nd ? i : 0)] + S[P.o_Lddq + (i < nd ? i : 0)];
+                if (i < nd) {
+                    S[P.o_p1 + i] = p;
+                    if (step + 1 == A.n_steps - 1) A.p1[t * nd + i] = p;
+                }
+                if (A.X) {
+                    double *x = A.X + (t * (size_t)(A.n_steps + 1) + step + 1) * nX;
+                    x[i] = q2i;
+                    x[nq + i] = i < nd ? p : (q2i - q1i) / dt;      // (entry nq + nd + j of the row for kinematic config j = i - nd)
+                }
+                const double q2n = i < nd ? q2i : pre_k;
+                S[P.o_q1 + i] = q2i;
+                if (i >= nd) S[P.o_q2 + i] = q2n;
+                S[P.o_dq + i] = core.over_dt(q2n - q2i);
+            }
+            if (i < nu) S[P.o_u + i] = pre_u;
+            if (nc) TG_FOR(n, P.n_dh) S[P.o_Dh1 + n] = S[P.o_Dh2 + n];
+            TG_RSYNC();
+            edge_done = true;
+        } else {
         if (on && !failed) {
             total_iters += iterations;
             // p2 = D2L2 at the converged midpoint (midpointvi.c:742-743); it becomes p1 of the next step
             TG_FOR(i, nd) S[P.o_p1 + i] = 0.5 * dt * S[P.o_Ldq + i] + S[P.o_Lddq + i];
         }
-        TG_SYNC();
+        TG_RSYNC();
         if (on && !failed && A.X) {
             double *x = A.X + (t * (size_t)(A.n_steps + 1) + step + 1) * nX;
             TG_FOR(i, nq) x[i] = S[P.o_q2 + i];
             TG_FOR(i, nd) x[nq + i] = S[P.o_p1 + i];
             TG_FOR(i, nk) x[nq + nd + i] = (S[P.o_q2 + nd + i] - S[P.o_q1 + nd + i]) / dt;
+        }
         }
     }
     // ---- write back q1, q2, p2, lambda1, u1 (p1 was stored when the last step started) ----------------------
