@@ -689,9 +689,12 @@ struct Core {
                         const int a = rotary ? kind - TG_RX : kind - TG_TX, b = a == 2 ? 0 : a + 1, c = a == 0 ? 2 : a - 1;
                         double *g = (second ? G2 : G) + 12 * j;
                         // translation column of row l: v, or for a run joint's copied row the config itself (one instruction stream: selects)
+                        // (tr_rows: the rows some item of the plan copies at all; a row outside it costs neither the config's read nor the select)
                         auto row_t = [&](int l, double v) {
                             if constexpr (TR) {
-                                if (rollout_lists) { const double e = qval(second ? dsB : dsA, (trw[u] >> (8 * l)) & 0xFF); return (trw[u] >> (24 + l)) & 1 ? e : v; }
+                                typedef typename std::remove_cv<PROG>::type SP;
+                                constexpr int ROWS = tg_static_wev<SP>::value ? SP::tr_rows : 7;
+                                if (rollout_lists && ((ROWS >> l) & 1)) { const double e = qval(second ? dsB : dsA, (trw[u] >> (8 * l)) & 0xFF); return (trw[u] >> (24 + l)) & 1 ? e : v; }
                             }
                             return v;
                         };
@@ -1512,14 +1515,14 @@ struct Core {
                 double acc = 0.0;
 #pragma unroll
                 for (int b = 0; b < NB; b++) if ((P.cmp_gmask[g] >> b) & 1) acc += BW[BWS * b + lane];
-                CMP[16 * g + lane] = acc;
+                CMP[cmp_stride<SP>() * g + lane] = acc;
             }
         }
         TG_RSYNC();
         TG_STAMP(3);
         // ---- E6: L_dq, L_ddq and the residual entry of config k ----
         if (on && lane < nd) {
-            const double *c = CMP + 16 * ((wvl[3] >> 24) & 0x7F);
+            const double *c = CMP + cmp_stride<SP>() * ((wvl[3] >> 24) & 0x7F);
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3];
             const double h0 = c[10], h1 = c[11], h2 = c[12], h3 = c[13], h4 = c[14], h5 = c[15];
             double sk[6];
@@ -1867,7 +1870,7 @@ struct Core {
                 double acc = 0.0;
 #pragma unroll
                 for (int b = 0; b < NB; b++) if ((P.cmp_gmask[g] >> b) & 1) acc += BW[BWS * b + lane];
-                CMP[16 * g + lane] = acc;
+                CMP[cmp_stride<SP>() * g + lane] = acc;
             }
         }
         TG_SYNC();
@@ -1883,7 +1886,7 @@ struct Core {
             if constexpr ((nf * ld) & 1) { if (on && lane == 0) A[nf * ld - 1] = 0.0; }
         }
         if (on && lane < nd) {
-            const double *c = CMP + 16 * (rep[lane] >> 20);
+            const double *c = CMP + cmp_stride<SP>() * (rep[lane] >> 20);
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3], Dxx = c[4], Dxy = c[5], Dxz = c[6], Dyy = c[7], Dyz = c[8], Dzz = c[9];
             const double h0 = c[10], h1 = c[11], h2 = c[12], h3 = c[13], h4 = c[14], h5 = c[15];
             const double *s = SW + SWS * lane, *w = s + 6;
@@ -1989,7 +1992,7 @@ struct Core {
         };
         static_assert(!(SKIPC && FB), "newton_matrix_world: SKIPC has no caller (the pivoting fallback unpacks the packed image through bbd_map); with a translational prefix it would have to store the closed-form entries from the per-config vectors in CZ");
         if (!SKIPC && on && lane < nd) {
-            const double *c = S + P.o_cmp + 16 * ((wvl[3] >> 24) & 0x7F);
+            const double *c = S + P.o_cmp + cmp_stride<SP>() * ((wvl[3] >> 24) & 0x7F);
             const double M = c[0], Cx = c[1], Cy = c[2], Cz = c[3], Dxx = c[4], Dxy = c[5], Dxz = c[6], Dyy = c[7], Dyz = c[8], Dzz = c[9];
             const double h0 = c[10], h1 = c[11], h2 = c[12], h3 = c[13], h4 = c[14], h5 = c[15];
             double s[6];

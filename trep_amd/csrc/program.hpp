@@ -16,6 +16,21 @@ struct DevProg {
 #undef TG_F_TABLE
 };
 
+// Composite records (o_cmp): 16 doubles each.  A config lane reads its group's record as 16-byte words, and on the 64 banks of the
+// LDS array the records of groups g and g' share banks when their starts are equal modulo 32 doubles: 16 doubles apart that is every
+// second group (up to five distinct addresses on four banks for the puppet's nine groups).  kCmpStride = 18 doubles apart the starts
+// are distinct modulo 32 for sixteen groups in a row and stay even, so the words stay 16-byte aligned.  The schedule (composite_form)
+// takes the wide stride where the twist records behind the composites still fit the J area with it -- a system never loses the
+// world-frame evaluation to it -- and 16 otherwise; the kernels read the stride back from the plan, (o_csw - o_cmp) / n_cgroups.
+constexpr int kCmpRecord = 16, kCmpStride = 18;
+static_assert(kCmpStride >= kCmpRecord && kCmpStride % 2 == 0 && kCmpRecord % 2 == 0, "composite records: 16-byte aligned");
+template <class SP> constexpr int cmp_stride() {
+    static_assert(SP::n_cgroups > 0 && (SP::o_csw - SP::o_cmp) % SP::n_cgroups == 0, "composite records: o_csw is not a whole number of strides behind o_cmp");
+    constexpr int stride = (SP::o_csw - SP::o_cmp) / SP::n_cgroups;
+    static_assert((stride == kCmpRecord || stride == kCmpStride) && (SP::o_cmp & 1) == 0, "composite records: stride");
+    return stride;
+}
+
 }  // namespace tg
 
 // A plain host compiler (the emulation of the kernels under tests/) also gets the compiler, whose HostProgram drives the emulated

@@ -102,6 +102,7 @@ struct ScheduleBuilder {
     std::vector<int> anchor;      // nearest variable ancestor-or-self of every frame, as a joint
     std::vector<M34> offset;      // constant transform from it
     std::map<int, int> ep_of_frame;
+    int cmp_stride = kCmpRecord;     // doubles between the composite records (composite_form; the room conditions of world_eval read it)
     std::vector<int> pose_need;      // bit 0: the midpoint pose of joint j is read (a body hangs below it), bit 1: its q2 pose (a constraint end point does)
     int off = 0;      // LDS layout cursor (doubles from the team's base)
     static constexpr int kCompositeMinNd = 8;      // smallest nd the composite form (and with it the world-frame evaluation) takes: composite_form(), and the 16-byte alignment of what it reads (counts_and_step_layout)
@@ -748,11 +749,16 @@ inline void ScheduleBuilder::composite_form() {
             if (a < nd) { H.cmp_pair.push_back(a | (c << 16)); from_cmp[(size_t)a * nd + c] = 1; }
         }
     }
-    const int need = 16 * (int)group_of.size() + 27 * nd;                      // J / W area
+    // the records' stride (program.hpp, kCmpStride): the wide one where everything that may follow them -- the nd + 2 twist records of a
+    // world-frame evaluation with a prefix inside the J area, the per-config vectors inside J and W -- still fits, 16 otherwise
+    const int ng = (int)group_of.size();
+    const bool wide = kCmpStride * ng + 12 * (nd + 2) <= 6 * nitems && kCmpStride * ng + 12 * (nd + 2) + 15 * nd <= 12 * nitems;
+    cmp_stride = wide ? kCmpStride : kCmpRecord;
+    const int need = cmp_stride * ng + 27 * nd;                                // J / W area
     if (all_rep && nd >= kCompositeMinNd && nd <= 64 && nb <= 32 && group_of.size() <= 32 && from_pairs == from_cmp && need <= 12 * nitems && nitems < 4096 &&
         17 * nb <= 2 * nj + std::max(12 * nj, 2 * nitems)) {      // (the per-body entries, 17 doubles apart: sin / cos + joint-pose area, dead by then)
         P.cmp_ok = 1; P.n_cgroups = (int)group_of.size(); P.n_cmpairs = (int)H.cmp_pair.size();
-        P.o_cmp = P.o_J; P.o_csw = P.o_cmp + 16 * P.n_cgroups; P.o_ccz = P.o_csw + 12 * nd;
+        P.o_cmp = P.o_J; P.o_csw = P.o_cmp + cmp_stride * P.n_cgroups; P.o_ccz = P.o_csw + 12 * nd;
         for (auto &g : group_of) for (int b : g.first) P.cmp_gmask[g.second] |= 1 << b;
     }
 }
@@ -760,7 +766,7 @@ inline void ScheduleBuilder::composite_form() {
 // the prefix in use by the world-frame evaluation (lists: its per-lane config lists)
 inline void ScheduleBuilder::floating_base_tables(const std::vector<std::vector<int>> &lists) {
     // the prefix in use: one more record again (the same three room conditions with it), a second lane without a role to write it
-    const int rec2 = 16 * P.n_cgroups + 12 * (nd + 2);
+    const int rec2 = cmp_stride * P.n_cgroups + 12 * (nd + 2);
     if (P.fb_n > 0 && nd + 3 * nb < 63 && rec2 <= 6 * nitems && rec2 + 15 * nd <= 12 * nitems) {
         P.fb_on = 1;
         P.o_ccz = P.o_csw + 12 * (nd + 2);
@@ -826,9 +832,9 @@ inline void ScheduleBuilder::world_eval() {
     H.wev_lane.assign(256, 0);
     bool ok = P.cmp_ok && P.tab_ok && P.sw_ok && P.sched_ok && nd + 3 * nb < 64 && nc > 0 && 6 * nitems >= 12 * nj && ns == 0 && nw == 0 && !P.has_cs;
     for (int it = 0; it < nitems && ok; it++) if (H.it_cfg[it] >= nd) ok = false;
-    if (ok && 16 * P.n_cgroups + 12 * (nd + 1) > 6 * nitems) ok = false;
+    if (ok && cmp_stride * P.n_cgroups + 12 * (nd + 1) > 6 * nitems) ok = false;
     if (ok && 12 * nj + 17 * nb > 6 * nitems + 9 * nb) ok = false;      // per-body world entries behind the q2 poses (W, vB, gam areas)
-    if (ok && 16 * P.n_cgroups + 12 * (nd + 1) + 15 * nd > 12 * nitems) ok = false;
+    if (ok && cmp_stride * P.n_cgroups + 12 * (nd + 1) + 15 * nd > 12 * nitems) ok = false;
     std::vector<std::vector<int>> lists(64);
     if (ok) {
         for (int c = 0; c < nd; c++) {
@@ -985,6 +991,8 @@ inline void ScheduleBuilder::translation_runs() {
             if (c >= 0 && c != H.j_cfg[j]) H.tr_sj[n] |= ((c & 0xFF) << (8 * r)) | (1 << (24 + r));
         }
     }
+    P.tr_rows = 0;
+    for (int w : H.tr_sj) P.tr_rows |= (w >> 24) & 7;
     // the second plan: every chain without its leading run joints, in its own round and slot
     H.tr_sched.assign(32 * (size_t)std::max(P.n_rounds, 1), 0);
     bool on = P.sw_ok && P.wev_ok && P.tr_n > 0 && nq <= 256;
