@@ -479,6 +479,43 @@ int tg_batch_minimize_potential_device(tg_batch *b, const double *q_dev, const i
                                        int32_t max_iterations, double *q_out_dev, double *mu_out_dev, double *v_out_dev,
                                        int32_t *iterations_out_dev, int32_t *status_out_dev);
 
+/* ---- batched inverse dynamics --------------------------------------------------------------------------------------
+ * Given configuration paths Q [B][N + 1][nq] (kinematic configs included; B = the batch size, N = n_steps >= 1), the inputs u_k and
+ * constraint forces lambda_k that make the discrete Euler-Lagrange equations hold on every step, and the impulse rho_k that no
+ * input can supply.  Every (b, k), k = 0 .. N - 1, is an independent linear problem, one team each, all in one launch
+ * (tests/inverse_dynamics_reference.py is the specification):
+ *   p_k = p0[b] for k = 0, else D2L_d(Q_{k-1}, Q_k; dt_{k-1}) (tg_batch_calc_p2's formula: it depends on neither u nor lambda);
+ *   r0 = p_k + D1L_d(Q_k, Q_{k+1}) + fm2(Q_k, Q_{k+1}, u = 0) on the dynamic configs (tg_batch_calc_f with u1 = lambda1 = 0) and
+ *   h = h(Q_{k+1});  A~ = [F_du | -Dh(Q_k)[:, :nd]'], nd x n, n = nu + nc, F_du at the midpoint (the residual is affine in (u, lambda):
+ *   r = r0 + A~ z~ with the impulses z~ = (dt_k u, lambda));
+ *   minimise |rho|^2 + ridge |z~|^2, rho = r0 + A~ z~, through the augmented system [[I, A~], [A~', -ridge I]] (-rho, z~) = (-r0, 0)
+ *   of size nd + n (Gauss-Jordan with implicit-scaled partial pivoting; not the normal equations).
+ * Step sizes: the scalar dt, or the batch's by-step list (tg_batch_set_step_sizes) as tg_batch_rollout reads it: dt_k = list[k].
+ * Outputs, each may be NULL: U [B][N][nu] = z~_u / dt_k; LAM [B][N][nc]; RHO [B][N][nd], zero on a feasible path; H [B][N][nc] =
+ * h(Q_{k+1}); P [B][N + 1][nd] with P[b][k + 1] = D2L_d(Q_k, Q_{k+1}; dt_k) and P[b][0] = p_0; status [B][N]: TG_OK, or TG_SINGULAR
+ * when the solver rejects the image or its answer is not finite -- U, LAM and RHO of that step are then zero, P and H still written.
+ * p0 == NULL: step 0 is not solved; P[b][0] = -r0 evaluated at p = 0, the momentum that makes step 0 force-free, and U, LAM, RHO of
+ * step 0 are zero with TG_OK: initialize_from_state(t_0, Q_0, P_0) followed by a rollout with U then retraces Q.  n == 0: nothing
+ * to solve, rho = r0.
+ * A rank-deficient A~ with n <= nd and ridge == 0 is NOT detected (the pivot guard is 1e-20; the puppet driven by forces on its
+ * string ends has sigma_min ~ 2e-19): such systems need ridge > 0, and the answer is then the ridge solution, not the minimum-norm one.
+ * Generic kernel of its own (mode 11 in tg_batch_info) whatever library the batch has; with a parameter table
+ * (tg_batch_set_parameters) its parameter twin runs (mode 11 in tg_batch_par_info) and trajectory b uses row b / group for masses,
+ * inertias, gravity and damping.  The integrator state of the batch (q1, q2, p, lambda1, status, iterations, times) is not touched.
+ * TG_ERR_INVALID for ridge < 0 or not finite, n_steps < 1, a null Q, a by-trajectory step-size list, a by-step list shorter than
+ * n_steps, a zero or non-finite dt without a list, n > nd with ridge == 0 (the image is structurally singular), and (_device) a
+ * row stride under nq; TG_ERR_UNSUPPORTED for the profiling build and if the workgroup's LDS -- per team the rollout slice plus
+ * (m + 1) m + nd + m doubles, m = nd + n -- exceeds 160 KiB (tg_system_inverse_dynamics_lds: out = team size, doubles per team,
+ * bytes per workgroup, 0; the same refusals, computed without a device).
+ * The _device variant takes device pointers, launches on the batch's stream and does not synchronise; row (b, k) of Q is read at
+ * Q_dev + (b (N + 1) + k) q_row_stride_doubles, so q_row_stride_doubles = nX reads Q straight from a rollout's X [B][N + 1][nX]. */
+int tg_system_inverse_dynamics_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge,
+                              double *U, double *LAM, double *P, double *RHO, double *H, int32_t *status);
+int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                     const double *p0_dev, double ridge, double *U_dev, double *LAM_dev, double *P_dev,
+                                     double *RHO_dev, double *H_dev, int32_t *status_dev);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

@@ -1,0 +1,154 @@
+// mvi_inverse.hpp -- MODE_INVERSE: batched inverse dynamics, one team per (trajectory, step) (tg_batch_inverse_dynamics).
+//
+// Given configuration paths Q [B][N + 1][nq], find for every step k of every path the inputs u_k and constraint forces lambda_k that
+// make the discrete Euler-Lagrange equations hold, and the impulse rho_k that no input can supply.  Two facts make the B x N steps
+// independent linear problems:
+//   (1) p_{k+1} = D2L_d(q_k, q_{k+1}) does not depend on u or lambda (midpointvi.c:491-504), so every p_k of a given path is known
+//       without a sweep;
+//   (2) the residual of a step is affine in (u, lambda): r(u, lambda) = r0 + dt F_du u - Dh(q_k)[:, :nd]' lambda, F_du at the midpoint
+//       (every built-in force has f_dudu = 0).
+// Per team (b, k), tests/inverse_dynamics_reference.py being the specification:
+//   p_k = p0[b] (k = 0) or D2L_d(Q_{k-1}, Q_k; dt_{k-1}): a midpoint evaluation of pair k - 1 (calc_p2's formula);
+//   r0 = p_k + D1L_d(Q_k, Q_{k+1}) + fm2(Q_k, Q_{k+1}, u = 0) on the dynamic configs and h = h(Q_{k+1}): calc_f with u1 = lambda1 = 0;
+//   A~ = [F_du | -Dh(Q_k)[:, :nd]'], nd x n, n = nu + nc: the ConfigForce coefficients and the wrench Jacobians wD through wr_in (what
+//   kkt_rest puts into the u1 columns of deriv1, without their dt);
+//   the unknowns are impulses z~ = (dt_k u, lambda): minimise |rho|^2 + ridge |z~|^2 with rho = r0 + A~ z~, solved in the augmented
+//   form [[I, A~], [A~', -ridge I]] (-rho, z~) = (-r0, 0) by Core::gauss_jordan (not the normal equations: A~'A~ squares the
+//   conditioning).
+// Outputs: U = z~_u / dt_k, LAM, RHO, H = h(Q_{k+1}), P[k + 1] = D2L_d(Q_k, Q_{k+1}; dt_k) from the same evaluation, P[0] = p_0,
+// status TG_OK or TG_SINGULAR (the solver rejected the image or its answer is not finite: U, LAM, RHO of that step are zero, P and H
+// still written).
+// Without p0, step 0 is not solved: P[0] = -r0 evaluated at p = 0 -- the momentum that makes step 0 force-free -- and U, LAM, RHO of
+// step 0 are zero, so that initialize_from_state(t_0, Q_0, P_0) followed by a rollout with U retraces Q.  With n == 0 nothing is
+// solved either: rho = r0.
+// A rank-deficient A~ with n <= nd and ridge == 0 is NOT detected unless a scaled pivot falls to 1e-20 (gauss_jordan's guard): such
+// systems need ridge > 0.
+//
+// No team reads what another writes: a (b, k) result does not depend on B, N or the team's neighbours in the wavefront.
+// LDS of a team: the rollout slice and behind it the image [m][m + 1], m = nd + n, p_k [nd] and the solver's row scales [m].
+// Compiled by hipcc (trepamd_inverse.hip: k_inverse) and, with TEAM = 1, by g++ for the CPU tests (tests/emu_invdyn).
+#pragma once
+#include <cfloat>
+
+#include "mvi_core.hpp"
+
+namespace tg {
+
+constexpr int MODE_INVERSE = 11;
+
+// passed beside RunArgs (whose layout stays), as ParTable is; RunArgs supplies batch = B
+struct InverseArgs {
+    const double *Q;             // configurations: row (b, k) at Q + (b (n_steps + 1) + k) q_stride, k = 0 .. n_steps
+    const double *p0;            // [batch][nd] or null
+    const double *dt_steps;      // [n_steps] step sizes, or null: dt
+    double *U, *LAM, *P, *RHO, *H;   // [batch][n_steps][nu], [..][nc], [batch][n_steps + 1][nd], [batch][n_steps][nd], [..][nc]; each may be null
+    int *status;                 // [batch][n_steps] or null
+    double dt, ridge;
+    size_t q_stride;             // doubles between consecutive rows of Q (nq, or nX to read a rollout's X)
+    int n_steps;
+    int o_kkt, o_pk, o_scal;     // LDS offsets (doubles) behind the rollout slice
+    int lds_per_team;            // doubles per team: what the kernel strides its teams by
+};
+
+// the scratch layout of one team (host; the same numbers for the device launch and the emulation)
+inline void inverse_layout(int rollout_lds_per_team, int nd, int nu, int nc, InverseArgs &J) {
+    const int m = nd + nu + nc;
+    int off = (rollout_lds_per_team + 1) & ~1;
+    J.o_kkt = off; off += m * (m + 1);
+    J.o_pk = off; off += nd;
+    J.o_scal = off; off += m;
+    J.lds_per_team = (off + 1) & ~1;
+}
+
+// team index i = b * n_steps + k; i >= batch * n_steps: an idle team, which still takes part in every TG_SYNC
+template <int TEAM, bool SPRINGS, bool PAR, class PROG, class ARGS>
+TG_HD void run_inverse(PROG &P, ARGS &A, const InverseArgs &J, const ParTable T, double *S, int lane, long long team_index) {
+    const int nq = P.nq, nd = P.nd, nu = P.nu, nc = P.nc, N = J.n_steps;
+    const int n = nu + nc, m = nd + n, ld = m + 1;
+    const bool live = team_index < (long long)A.batch * N;
+    const size_t b = (size_t)(live ? team_index / N : 0);
+    const int k = (int)(live ? team_index % N : 0);
+    const size_t bk = b * (size_t)N + k;
+    const double dt_k = J.dt_steps ? J.dt_steps[k] : J.dt;
+    const double dt_prev = k > 0 && J.dt_steps ? J.dt_steps[k - 1] : J.dt;
+    Core<TEAM, SPRINGS, PROG, double, PAR> core(P, S, lane, dt_prev);
+    if constexpr (PAR) core.par = T.rows + (b / (size_t)T.group) * (size_t)T.stride + 4 * P.n_bodies;
+    else (void)T;
+    core.init_sweep_schedule(false);
+    double *K = S + J.o_kkt, *pk = S + J.o_pk, *scal = S + J.o_scal;
+    const double *rows = J.Q + (b * (size_t)(N + 1) + k) * J.q_stride;     // Q_k; Q_{k-1} and Q_{k+1} one stride before and behind
+
+    // the pair (Q_first, Q_first+1) with p1 = p, no inputs, no multipliers
+    auto load_pair = [&](bool on, const double *q_first, const double *p) {
+        if (on) {
+            TG_FOR(i, nq) { S[P.o_q1 + i] = q_first[i]; S[P.o_q2 + i] = q_first[J.q_stride + i]; }
+            TG_FOR(i, nd) S[P.o_p1 + i] = p ? p[i] : 0.0;
+            TG_FOR(i, nc) S[P.o_lam + i] = 0.0;
+            TG_FOR(i, nu) S[P.o_u + i] = 0.0;
+            TG_FOR(i, P.n_dh) { S[P.o_Dh1 + i] = 0.0; S[P.o_Dh2 + i] = 0.0; }
+        }
+        TG_SYNC();
+    };
+
+    // ---- p_k: the momentum the path arrives with ------------------------------------------------------------------------------
+    const bool arrives = live && k > 0;
+    load_pair(arrives, rows - J.q_stride, nullptr);
+    core.eval_midpoint(arrives);
+    if (live) TG_FOR(i, nd) pk[i] = k > 0 ? 0.5 * dt_prev * S[P.o_Ldq + i] + S[P.o_Lddq + i] : (J.p0 ? J.p0[b * nd + i] : 0.0);
+    TG_SYNC();
+
+    // ---- r0, h, P_{k+1} of the pair (Q_k, Q_{k+1}) ----------------------------------------------------------------------------
+    core.dt = dt_k; core.inv_dt = 1.0 / dt_k;
+    load_pair(live, rows, pk);
+    core.eval_constraints(live, 1, false, S + P.o_Dh1);
+    core.eval_midpoint(live);
+    const bool solve = live && n > 0 && (k > 0 || J.p0);
+    // the image [[I, A~], [A~', -ridge I]] with the right-hand side (-r0, 0): every lane owns rows of [I, A~], then the transpose
+    if (solve) TG_FOR(i, m * ld) K[i] = 0.0;
+    TG_SYNC();
+    if (solve) TG_FOR(i, nd) {
+        double *row = K + i * ld;
+        row[i] = 1.0;
+        for (int f = 0; f < P.n_cf; f++) if (P.cf_cfg[f] == i) row[nd + P.cf_in[f]] += 1.0;
+        if (core.n_wrenches()) {
+            const int m0 = P.n_dh + core.n_sdh(), c0 = nc + core.n_springs();
+            for (int w_ = 0; w_ < core.n_wdh(); w_++) {
+                if (P.dh_cfg[m0 + w_] != i) continue;
+                const int w = P.dh_c[m0 + w_] - c0;
+                for (int s6 = 0; s6 < 6; s6++) { const int in = P.wr_in[6 * w + s6]; if (in >= 0) row[nd + in] += S[P.o_wD + 6 * w_ + s6]; }
+            }
+        }
+        for (int c = 0; c < nc; c++) { const int e = P.dh_lookup[c * nq + i]; if (e >= 0) row[nd + nu + c] = -S[P.o_Dh1 + e]; }
+        row[m] = -S[P.o_f + i];
+    }
+    TG_SYNC();
+    if (solve) {
+        TG_FOR(e, n * nd) { const int j = e / nd, i = e % nd; K[(nd + j) * ld + i] = K[i * ld + nd + j]; }
+        TG_FOR(j, n) K[(nd + j) * ld + nd + j] = -J.ridge;
+    }
+    if (live) {
+        if (J.P) {
+            double *Pb = J.P + b * (size_t)(N + 1) * nd;
+            TG_FOR(i, nd) Pb[(size_t)(k + 1) * nd + i] = 0.5 * dt_k * S[P.o_Ldq + i] + S[P.o_Lddq + i];
+            if (k == 0) TG_FOR(i, nd) Pb[i] = J.p0 ? pk[i] : -S[P.o_f + i];
+        }
+        if (!solve && J.RHO) TG_FOR(i, nd) J.RHO[bk * nd + i] = (k > 0 || J.p0) ? S[P.o_f + i] : 0.0;     // n == 0: rho = r0
+    }
+    TG_SYNC();
+    core.eval_constraints(live, 2, true, S + P.o_Dh2);
+    if (live && J.H) TG_FOR(c, nc) J.H[bk * nc + c] = S[P.o_f + nd + c];
+
+    // ---- the solve ------------------------------------------------------------------------------------------------------------
+    bool ok = true;
+    if (n > 0) ok = core.gauss_jordan(solve, K, m, 1, ld, scal);      // (n is the launch's: every team of the wavefront takes the same way)
+    if (solve && ok) for (int i = 0; i < m; i++) if (!(fabs(K[i * ld + m]) <= DBL_MAX)) ok = false;      // (every lane scans the same words: team-uniform)
+    const bool answer = solve && ok;
+    if (live) {
+        if (J.U) TG_FOR(i, nu) J.U[bk * nu + i] = answer ? K[(nd + i) * ld + m] / dt_k : 0.0;
+        if (J.LAM) TG_FOR(c, nc) J.LAM[bk * nc + c] = answer ? K[(nd + nu + c) * ld + m] : 0.0;
+        if (solve && J.RHO) TG_FOR(i, nd) J.RHO[bk * nd + i] = answer ? -K[i * ld + m] : 0.0;
+        if (lane == 0 && J.status) J.status[bk] = ok ? TG_OK : TG_SINGULAR;
+    }
+}
+
+}  // namespace tg

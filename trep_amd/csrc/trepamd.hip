@@ -19,6 +19,7 @@
 #include "launch_generic.hpp"
 #include "mvi_project.hpp"
 #include "mvi_equilibrium.hpp"
+#include "mvi_inverse.hpp"
 #include "schedule.hpp"
 #include <dlfcn.h>
 
@@ -29,6 +30,8 @@ int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunA
 int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ProjectArgs &J, int grid, size_t lds, hipStream_t stream);
 // the equilibrium-search kernel and its parameter-table twin (trepamd_equilibrium.hip, likewise)
 int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+// the inverse-dynamics kernel and its parameter-table twin (trepamd_inverse.hip, likewise)
+int launch_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -1177,6 +1180,92 @@ int tg_batch_minimize_potential(tg_batch *b, const double *q_host, const int32_t
     if (int rc = tg_batch_minimize_potential_device(b, s.q0, free_host ? s.mask : nullptr, tolerance, max_iterations, s.q, s.mu, s.extra, s.iters, s.status)) return rc;
     if (v_out) HIP_TRY(hipMemcpyAsync(v_out, s.extra, (size_t)b->batch * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     return pose_stage_out(b, s, q_out, mu_out, iterations_out, status_out);
+}
+
+// ---- batched inverse dynamics (mvi_inverse.hpp): one team per (trajectory, step), one launch
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the inverse-dynamics kernel for this system (out[0..2];
+ * out[3] 0): the rollout slice plus the image [m][m + 1], m = nd + nu + nc, p_k [nd] and the solver's row scales [m]
+ * (mvi_inverse.hpp).  TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a workgroup can have, and in the profiling build. */
+int tg_system_inverse_dynamics_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::InverseArgs J{};
+    tg::inverse_layout(sys->H.p.lds_per_team, sys->H.p.nd, sys->H.p.nu, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident inverse-dynamics kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no inverse-dynamics kernel");
+#endif
+    return rc;
+}
+
+// what both entry points refuse, decided on the host before anything is staged or launched
+static int inverse_check(const tg_batch *b, int32_t n_steps, double dt, const double *Q, double ridge) {
+    if (!b || !Q) return fail(TG_ERR_INVALID, "null argument");
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(TG_ERR_INVALID, "ridge must be finite and not negative");
+    if (n_steps < 1) return fail(TG_ERR_INVALID, "n_steps must be at least 1");
+    if (b->dt_by_trajectory) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
+    if (!b->dt_host.empty() && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "path longer than the step-size list");
+    if (b->dt_host.empty() && (dt == 0.0 || !std::isfinite(dt))) return fail(TG_ERR_INVALID, "step size must be finite and not zero");
+    if (b->P.nu + b->P.nc > b->P.nd && ridge == 0.0)
+        return fail(TG_ERR_INVALID, "more unknowns (nu + nc) than dynamic configs: the least-squares image is singular without a ridge");
+    return TG_SUCCESS;
+}
+
+int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                     const double *p0_dev, double ridge, double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev,
+                                     double *H_dev, int32_t *status_dev) {
+    if (int rc = inverse_check(b, n_steps, dt, Q_dev, ridge)) return rc;
+    if (q_row_stride_doubles < (uint64_t)b->P.nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
+    int32_t geo[4];
+    if (int rc = tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
+    const long long teams = (long long)b->batch * n_steps, per_block = 64 / b->sys->team;
+    if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many steps for one launch");
+    HIP_TRY(hipSetDevice(b->device));
+    // the path is an argument of the call: nothing of the integrator (q1, q2, p, lambda1, status, times) is read or written, and a
+    // loaded specialised library has no say; a parameter table has (masses, gravity and damping move momenta and residuals)
+    tg::RunArgs A = base_args(b, tg::MODE_INVERSE);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.iters = A.status = nullptr;
+    A.n_steps = n_steps; A.dt = dt;
+    tg::InverseArgs J{};
+    tg::inverse_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    J.Q = Q_dev; J.p0 = p0_dev; J.dt_steps = b->dt_host.empty() ? nullptr : b->dt_dev.get();
+    J.U = U_dev; J.LAM = LAM_dev; J.P = P_dev; J.RHO = RHO_dev; J.H = H_dev; J.status = status_dev;
+    J.dt = dt; J.ridge = ridge; J.q_stride = (size_t)q_row_stride_doubles; J.n_steps = n_steps;
+    const bool par = b->par_rows > 0;
+    int rc = tg_detail::launch_inverse(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+                                       tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0},
+                                       (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[par][0].add(tg::MODE_INVERSE);      // a refused launch (the profiling build) is not counted
+    return rc;
+}
+
+int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge,
+                              double *U, double *LAM, double *P, double *RHO, double *H, int32_t *status) {
+    if (int rc = inverse_check(b, n_steps, dt, Q_host, ridge)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    // staging of this call alone (its size follows n_steps): Q, p0 in; U, LAM, P, RHO, H and the status words out
+    const size_t B = (size_t)b->batch, N = (size_t)n_steps, nq = b->P.nq, nd = b->P.nd, nu = b->P.nu, nc = b->P.nc;
+    const size_t n_q = B * (N + 1) * nq, n_p0 = B * nd, n_u = B * N * nu, n_l = B * N * nc, n_p = B * (N + 1) * nd, n_r = B * N * nd;
+    tg::DeviceBuffer<double> stage;
+    tg::DeviceBuffer<int> words;
+    HIP_TRY(stage.ensure(n_q + n_p0 + n_u + n_l + n_p + n_r + n_l));
+    HIP_TRY(words.ensure(B * N));
+    double *q = stage.get(), *p0 = q + n_q, *u = p0 + n_p0, *lam = u + n_u, *p = lam + n_l, *rho = p + n_p, *h = rho + n_r;
+    HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (p0_host && n_p0) HIP_TRY(hipMemcpyAsync(p0, p0_host, n_p0 * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    int rc = tg_batch_inverse_dynamics_device(b, n_steps, dt, q, nq, p0_host ? p0 : nullptr, ridge, u, lam, p, rho, h, words.get());
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
+            rc = fail(TG_ERR_HIP, "copy of the results failed");
+    };
+    back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(P, p, n_p * sizeof(double));
+    back(RHO, rho, n_r * sizeof(double)); back(H, h, n_l * sizeof(double)); back(status, words.get(), B * N * sizeof(int));
+    if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
+    return rc;
 }
 
 // z and hz in device memory; horizon > 0: only steps k_begin .. k_end - 1 of every seed of a seeds x horizon batch

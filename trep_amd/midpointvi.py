@@ -22,6 +22,7 @@ from .errors import ConvergenceError
 
 Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")      # BatchMidpointVI.satisfy_constraints
 Equilibrium = collections.namedtuple("Equilibrium", "Q mu V iterations status")     # BatchMidpointVI.minimize_potential_energy
+InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h status")     # BatchMidpointVI.inverse_dynamics
 
 
 class BatchMidpointVI(object):
@@ -243,7 +244,7 @@ class BatchMidpointVI(object):
         `spec_library` the loaded file.  The par_* keys: the same for the per-trajectory parameter kernels (set_parameters),
         over all kernel modes (ALL_MODES), with `par_spec_launch_mask` / `par_generic_launch_mask` the raw mode bits as
         `spec_launch_mask` / `generic_launch_mask` are for the default kernels (bit 9: the projection, bit 10: the equilibrium search,
-        which have no name in ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
+        bit 11: inverse dynamics, which have no name in ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
         out = np.zeros(8, dtype=np.int32)
         _lib.check(self._L.tg_batch_info(self._h, out.ctypes.data_as(_lib._c_ip)))
         names = lambda bits: sorted(n for n, m in self.MODES.items() if (int(bits) >> m) & 1)
@@ -546,6 +547,75 @@ class BatchMidpointVI(object):
                                                        int(max_iterations), _lib.ptr(q), _lib.ptr(mu), _lib.ptr(v), iters.ctypes.data,
                                                        status.ctypes.data))
         return Equilibrium(q, mu, v, iters, status)
+
+    def _with_step_sizes(self, dts, call):
+        """call() under the by-step list dts (None: as the batch stands); the list set before is put back."""
+        if dts is None:
+            return call()
+        saved = getattr(self, "_step_sizes", None)
+        self.set_step_sizes(dts)
+        try:
+            return call()
+        finally:
+            self.set_step_sizes(*(saved if saved is not None else (None,)))
+
+    def inverse_dynamics(self, Q, dt, p0=None, ridge=0.0):
+        """Inputs and constraint forces of given paths (include/trep_amd.h, tg_batch_inverse_dynamics): Q [B][N+1][nq], kinematic
+        configs included; `dt` a scalar or one step size per step; p0 [B][nd], optional.  Every step (b, k) is one least-squares
+        solve for the impulses (dt_k u_k, lambda_k), all B x N of them in one launch.  Returns the namedtuple (U [B][N][nu], lam
+        [B][N][nc], P [B][N+1][nd], rho [B][N][nd], h [B][N][nc], status [B][N]): rho is the impulse no input can supply (zero on a
+        feasible path), h = h(Q[k+1]), P[k+1] = D2L_d(Q[k], Q[k+1]) and P[0] = p0.  Without p0 step 0 is not solved: P[0] is the
+        momentum that makes it force-free and U[0] = 0, so that initialize_from_state(t0, Q[:, 0], P[:, 0]) and rollout(N, dt, U, K)
+        retrace Q (inverse_dynamics_trajectory packs that).  status: TG_OK, or TG_SINGULAR where the solver rejected the step (U,
+        lam, rho zero there).  ridge >= 0 weighs |(dt u, lambda)|^2 against |rho|^2; it is required (ValueError) when nu + nc > nd,
+        and a rank-deficient system needs it too -- that is not detected.  With a parameter table each trajectory uses its row.
+        The integrator state of the batch is left alone."""
+        self.refresh()
+        B = self._batch
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        if Q.ndim != 3 or Q.shape[0] != B or Q.shape[1] < 2 or Q.shape[2] != self.nq:
+            raise ValueError("expected Q of shape (%d, N + 1, %d) with N >= 1, got %r" % (B, self.nq, Q.shape))
+        N = Q.shape[1] - 1
+        dt, dts = self._dt_argument(dt, N)
+        p0 = None if p0 is None else _lib.as_f64(np.broadcast_to(np.asarray(p0, dtype=float), (B, self.nd)), (B, self.nd))
+        U, lam, P = np.zeros((B, N, self.nu)), np.zeros((B, N, self.nc)), np.zeros((B, N + 1, self.nd))
+        rho, h, status = np.zeros((B, N, self.nd)), np.zeros((B, N, self.nc)), np.zeros((B, N), dtype=np.int32)
+
+        def call():
+            rc = self._L.tg_batch_inverse_dynamics(self._h, N, dt, Q.ctypes.data, None if p0 is None else p0.ctypes.data, float(ridge),
+                                                   _lib.ptr(U), _lib.ptr(lam), _lib.ptr(P), _lib.ptr(rho), _lib.ptr(h), status.ctypes.data)
+            if rc == _lib.ERR_INVALID:
+                raise ValueError(self._L.tg_last_error().decode())
+            _lib.check(rc)
+        self._with_step_sizes(dts, call)
+        return InverseDynamics(U, lam, P, rho, h, status)
+
+    def inverse_dynamics_device(self, n_steps, dt, Q_dev, q_row_stride=None, p0_dev=None, ridge=0.0, U_dev=None, lam_dev=None,
+                                P_dev=None, rho_dev=None, h_dev=None, status_dev=None):
+        """inverse_dynamics on device pointers, asynchronous on the batch's stream (tg_batch_inverse_dynamics_device).  Row (b, k) of
+        the path is read at Q_dev + (b (n_steps + 1) + k) q_row_stride doubles: the default nq for a packed Q, nX to read the
+        configurations straight from a rollout's X [B][N+1][nX].  Any output may be None.  The step sizes are the scalar dt or the
+        by-step list the batch has (set_step_sizes)."""
+        self.refresh()
+        rc = self._L.tg_batch_inverse_dynamics_device(self._h, int(n_steps), float(dt), Q_dev, int(self.nq if q_row_stride is None else q_row_stride),
+                                                      p0_dev, float(ridge), U_dev, lam_dev, P_dev, rho_dev, h_dev, status_dev)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+
+    def inverse_dynamics_trajectory(self, Q, dt, p0=None, ridge=0.0):
+        """inverse_dynamics packed for rollout_closed_loop and discopt: returns (X [B][N+1][nX], U_full [B][N][nU], result) with
+        X[k] = [Q[k]; P[k]; v[k]], v[k] = (Q[k][nd:] - Q[k-1][nd:]) / dt[k-1] (v[0] = 0: DSystem's state, dsystem.py:276-281) and
+        U_full[k] = [U[k]; Q[k+1][nd:]] (its input: the forces and the kinematic configs' targets)."""
+        r = self.inverse_dynamics(Q, dt, p0=p0, ridge=ridge)
+        Q = np.asarray(Q, dtype=float)
+        N = Q.shape[1] - 1
+        dts = np.broadcast_to(np.asarray(dt, dtype=float).reshape(-1), (N,)) if np.ndim(dt) else np.full(N, float(dt))
+        v = np.zeros((self._batch, N + 1, self.nk))
+        v[:, 1:] = (Q[:, 1:, self.nd:] - Q[:, :-1, self.nd:]) / dts[None, :, None]
+        X = np.concatenate([Q, r.P, v], axis=2)
+        U_full = np.concatenate([r.U, Q[:, 1:, self.nd:]], axis=2)
+        return X, U_full, r
 
     def _seeds(self, seeds, most):
         """(seed1,) or (seed1, seed2) -> contiguous int32 [B] arrays: the input variable each trajectory's direction follows, numbered
