@@ -516,6 +516,41 @@ int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, co
                                      const double *p0_dev, double ridge, double *U_dev, double *LAM_dev, double *P_dev,
                                      double *RHO_dev, double *H_dev, int32_t *status_dev);
 
+/* ---- batched frame kinematics ------------------------------------------------------------------------------------------
+ * Where the frames are: for configurations Q [B][n_states][nq] (B = the batch size; kinematic configs included) and rates dQ of the
+ * same shape, the world pose, the body velocity and the two Jacobians of every selected frame of every state, one team per state,
+ * all in one launch (tests/frame_kinematics_reference.py is the specification; reference frame.py: g(), p(), vb(), p_dq(), vb_ddq()).
+ * frames_host [n_frames]: indices into the descriptor's frame list (System.frames, 0 = the world), a host array in both variants;
+ * repeats and any order are allowed.  With g_F = (R_F | p_F) the world pose of frame F, K the frame config k drives, a_k the world
+ * direction of K's joint axis (column x / y / z of R_K) and o_k = p_K:
+ *   G  [B][n_states][F][12]     rows 0..2 of Frame.g(), row-major 3 x 4 (Frame.p() is its fourth column);
+ *   JP [B][n_states][F][nq][3]  Frame.p_dq(k)[:3]: a_k x (p_F - o_k) for a rotary k on F's path, a_k for a prismatic one, 0 off it;
+ *   JB [B][n_states][F][nq][6]  Frame.vb_ddq(k) as (v, omega), v = M[0:3, 3], omega = (M[2][1], M[0][2], M[1][0]) of the 4 x 4 matrix
+ *                               the accessor returns: (R_F' JP_k, R_F' a_k), omega = 0 for a prismatic k, 0 off the path;
+ *   VB [B][n_states][F][6]      Frame.vb() likewise, sum_k JB_k dq_k; it needs dQ.
+ * Any output may be NULL; every entry of a requested output is written, zeros included.  A state's answer does not depend on B,
+ * n_states or its neighbours in the launch.
+ * Kinematics do not depend on masses, gravity, damping, a loaded specialised library or the time base: one generic kernel (mode 12
+ * in tg_batch_info) whatever the batch has set.  The integrator state of the batch (q1, q2, p, lambda1, status, iterations, times)
+ * is not touched.
+ * TG_ERR_INVALID, decided before a device is touched, for n_states < 1, a null Q, n_frames < 1 or a null frame list, a frame index
+ * outside the system, VB without dQ, all four outputs null, and (_device) a row stride under nq; TG_ERR_UNSUPPORTED for the
+ * profiling build and if the workgroup's LDS -- per team the rollout slice plus 144 doubles (eight staged frames: pose [12] and
+ * world twist [6]; it does not grow with n_frames) -- exceeds 160 KiB (tg_system_frame_kinematics_lds: out = team size, doubles per
+ * team, bytes per workgroup, 0; the same refusal, computed without a device).
+ * The _device variant takes device pointers, launches on the batch's stream and does not synchronise; row (b, m) is read at
+ * Q_dev + (b n_states + m) q_row_stride_doubles (dQ_dev likewise), so q_row_stride_doubles = nX reads the configurations straight
+ * from a rollout's X [B][n_states][nX].  The frame table of a selection lives in a buffer of the batch: a call with the selection
+ * of the call before allocates nothing; another selection waits for the stream once and rebuilds it. */
+int tg_system_frame_kinematics_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_frame_kinematics(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host,
+                              int32_t n_frames, const int32_t *frames_host,
+                              double *G, double *VB, double *JP, double *JB);
+int tg_batch_frame_kinematics_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                     const double *dQ_dev, uint64_t dq_row_stride_doubles,
+                                     int32_t n_frames, const int32_t *frames_host,
+                                     double *G_dev, double *VB_dev, double *JP_dev, double *JB_dev);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

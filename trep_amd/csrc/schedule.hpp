@@ -37,6 +37,10 @@ struct HostProgram {
 #undef TG_F_TABLE
     std::vector<unsigned char> newton_pattern;   // [nf * nf] structural non-zeros of the Newton matrix (symmetrised), host side only
     int max_depth = 0;
+    // every frame of the descriptor, host side only (frame kinematics: mvi_frames.hpp): its anchor joint (nearest variable
+    // ancestor-or-self; -1: fixed to the world) and the constant 3 x 4 transform from it
+    std::vector<int> frame_anchor;
+    std::vector<double> frame_offset;   // [n_frames][12]
     // all tables packed into two pools, in the order of the field list; bind() points a DevProg's table pointers into (copies of) them
     std::vector<int> ipool;
     std::vector<double> dpool;
@@ -204,6 +208,9 @@ inline void ScheduleBuilder::joint_tables() {
             offset[f] = mul(offset[p], fixed_local(d, f));
         }
     }
+    H.frame_anchor = anchor;
+    H.frame_offset.resize(12 * (size_t)nfr);
+    for (int f = 0; f < nfr; f++) std::memcpy(&H.frame_offset[12 * (size_t)f], offset[f].m, sizeof(offset[f].m));
     nj = (int)jorder.size();
     H.j_parent.resize(nj); H.j_kind.resize(nj); H.j_cfg.resize(nj); H.j_pre_ident.resize(nj); H.j_pre.resize(12 * (size_t)nj);
     for (int j = 0; j < nj; j++) {

@@ -20,6 +20,7 @@
 #include "mvi_project.hpp"
 #include "mvi_equilibrium.hpp"
 #include "mvi_inverse.hpp"
+#include "mvi_frames.hpp"
 #include "schedule.hpp"
 #include <dlfcn.h>
 
@@ -32,6 +33,8 @@ int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::
 int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the inverse-dynamics kernel and its parameter-table twin (trepamd_inverse.hip, likewise)
 int launch_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+// the frame-kinematics kernel (trepamd_frames.hip, likewise)
+int launch_frames(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::FrameArgs &J, int grid, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -130,6 +133,13 @@ struct tg_batch {
     tg::DeviceBuffer<double> pose;    // staging of the host-facing pose solvers (stream-ordered, one call at a time): q0 in, q, mu out, and
                                       // the projection's dq0 in, dq out or the equilibrium search's V out
     tg::DeviceBuffer<int> pose_ints;  // their free mask [nq], iteration [batch] and status [batch] words
+    // frame table of tg_batch_frame_kinematics (mvi_frames.hpp, FrameArgs::tab / ::off) for the selection frames_sel: rebuilt only
+    // when a call's selection differs from it, reallocated only when it grows
+    std::vector<int32_t> frames_sel;
+    std::vector<int> frames_tab_host;
+    std::vector<double> frames_off_host;
+    tg::DeviceBuffer<int> frames_tab;
+    tg::DeviceBuffer<double> frames_off;
     tg::DeviceBuffer<int> seeds;      // [2][batch] direction variables of the forward-mode calls
     tg::DeviceBuffer<double> d1[12];
     bool have_d1 = false;
@@ -242,30 +252,45 @@ int launch_team(tg_batch *b, const tg::RunArgs &A, int grid, size_t lds) {
     }
 }
 
+// HIP-event timing is opt-in (the first tg_batch_timing call switches it on): a plain MidpointVI.step() loop creates
+// no events.  When on, at most TIMING_CAP launches are kept; older pairs are recycled (their time is folded into
+// the running totals), and every error path hands the pair back to the pool.  timing_begin before a launch, timing_end(rc) behind it.
+struct LaunchTiming { tg::Event e0, e1; };
+int timing_begin(tg_batch *b, LaunchTiming &t) {
+    if (!b->timing) return TG_SUCCESS;
+    tg::Event &e0 = t.e0, &e1 = t.e1;
+    auto recycle = [&] { b->pool.push_back(std::move(e0)); b->pool.push_back(std::move(e1)); };
+    if (b->events.size() >= tg_batch::TIMING_CAP) {
+        float ms = 0.f;
+        e0 = std::move(b->events.front().first); e1 = std::move(b->events.front().second);
+        if (hipEventSynchronize(e1.get()) == hipSuccess && hipEventElapsedTime(&ms, e0.get(), e1.get()) == hipSuccess) { b->folded_ms += ms; b->folded_n++; }
+        b->events.erase(b->events.begin());
+    } else if (b->pool.size() >= 2) { e0 = std::move(b->pool.back()); b->pool.pop_back(); e1 = std::move(b->pool.back()); b->pool.pop_back(); }
+    else {
+        HIP_TRY(e0.create());
+        if (e1.create() != hipSuccess) { b->pool.push_back(std::move(e0)); return fail(TG_ERR_HIP, "hipEventCreate failed"); }
+    }
+    if (hipEventRecord(e0.get(), b->stream) != hipSuccess) { recycle(); return fail(TG_ERR_HIP, "hipEventRecord failed"); }
+    return TG_SUCCESS;
+}
+int timing_end(tg_batch *b, LaunchTiming &t, int rc) {
+    if (!b->timing) return rc;
+    if (rc != TG_SUCCESS || hipEventRecord(t.e1.get(), b->stream) != hipSuccess) {
+        b->pool.push_back(std::move(t.e0)); b->pool.push_back(std::move(t.e1));
+        return rc != TG_SUCCESS ? rc : fail(TG_ERR_HIP, "hipEventRecord failed");
+    }
+    b->events.emplace_back(std::move(t.e0), std::move(t.e1));
+    return rc;
+}
+
 int launch(tg_batch *b, tg::RunArgs &A) {
     b->mirror_valid = false;
     const int team = b->sys->team, per_block = 64 / team;
     const int grid = ((A.remap_len > 0 ? A.remap_count : A.batch) + per_block - 1) / per_block;
     const size_t lds = (size_t)per_block * lds_per_team(b->P, A.mode) * sizeof(double);
     if (lds > 160 * 1024) return fail(TG_ERR_UNSUPPORTED, "system too large for the LDS-resident kernel");
-    // HIP-event timing is opt-in (the first tg_batch_timing call switches it on): a plain MidpointVI.step() loop creates
-    // no events.  When on, at most TIMING_CAP launches are kept; older pairs are recycled (their time is folded into
-    // the running totals), and every error path hands the pair back to the pool.
-    tg::Event e0, e1;
-    auto recycle = [&] { b->pool.push_back(std::move(e0)); b->pool.push_back(std::move(e1)); };
-    if (b->timing) {
-        if (b->events.size() >= tg_batch::TIMING_CAP) {
-            float t = 0.f;
-            e0 = std::move(b->events.front().first); e1 = std::move(b->events.front().second);
-            if (hipEventSynchronize(e1.get()) == hipSuccess && hipEventElapsedTime(&t, e0.get(), e1.get()) == hipSuccess) { b->folded_ms += t; b->folded_n++; }
-            b->events.erase(b->events.begin());
-        } else if (b->pool.size() >= 2) { e0 = std::move(b->pool.back()); b->pool.pop_back(); e1 = std::move(b->pool.back()); b->pool.pop_back(); }
-        else {
-            HIP_TRY(e0.create());
-            if (e1.create() != hipSuccess) { b->pool.push_back(std::move(e0)); return fail(TG_ERR_HIP, "hipEventCreate failed"); }
-        }
-        if (hipEventRecord(e0.get(), b->stream) != hipSuccess) { recycle(); return fail(TG_ERR_HIP, "hipEventRecord failed"); }
-    }
+    LaunchTiming timed;
+    if (int trc = timing_begin(b, timed)) return trc;
     int rc;
     // a parameter table selects the PAR kernels: the library's specialised one of the mode if it has it, else the generic one
     const bool par = b->par_rows > 0;
@@ -290,14 +315,7 @@ int launch(tg_batch *b, tg::RunArgs &A) {
                  : tg_detail::dispatch_team(team, [&](auto team_tag) { return launch_team<decltype(team_tag)::value>(b, A, grid, lds); });
     }
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
-    if (b->timing) {
-        if (rc != TG_SUCCESS || hipEventRecord(e1.get(), b->stream) != hipSuccess) {
-            recycle();
-            return rc != TG_SUCCESS ? rc : fail(TG_ERR_HIP, "hipEventRecord failed");
-        }
-        b->events.emplace_back(std::move(e0), std::move(e1));
-    }
-    return rc;
+    return timing_end(b, timed, rc);
 }
 
 #if !defined(TG_PROFILE)
@@ -1264,6 +1282,111 @@ int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const dou
     };
     back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(P, p, n_p * sizeof(double));
     back(RHO, rho, n_r * sizeof(double)); back(H, h, n_l * sizeof(double)); back(status, words.get(), B * N * sizeof(int));
+    if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
+    return rc;
+}
+
+// ---- batched frame kinematics (mvi_frames.hpp): one team per state, one launch
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the frame-kinematics kernel for this system (out[0..2];
+ * out[3] 0): the rollout slice plus one pass of staged frames, kFramePass poses [12] and world twists [6], whatever the selection
+ * (mvi_frames.hpp).  TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a workgroup can have, and in the profiling build. */
+int tg_system_frame_kinematics_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::FrameArgs J{};
+    tg::frames_layout(sys->H.p.lds_per_team, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident frame-kinematics kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no frame-kinematics kernel");
+#endif
+    return rc;
+}
+
+// what both entry points refuse, decided on the host before a device is touched: first what the arguments alone show, then what
+// needs the system (the strides are nq for the host variant)
+static int frames_check(const tg_batch *b, int32_t n_states, const double *Q, const double *dQ, uint64_t q_stride, uint64_t dq_stride,
+                        int32_t n_frames, const int32_t *frames, const double *G, const double *VB, const double *JP, const double *JB) {
+    if (n_states < 1) return fail(TG_ERR_INVALID, "n_states must be at least 1");
+    if (!Q) return fail(TG_ERR_INVALID, "null Q");
+    if (n_frames < 1 || !frames) return fail(TG_ERR_INVALID, "no frames selected");
+    if (VB && !dQ) return fail(TG_ERR_INVALID, "VB without dQ");
+    if (!G && !VB && !JP && !JB) return fail(TG_ERR_INVALID, "no output asked for");
+    if (!b || !b->sys) return fail(TG_ERR_INVALID, "null argument");
+    const int32_t nfr = (int32_t)b->sys->H.frame_anchor.size();
+    for (int32_t s = 0; s < n_frames; s++)
+        if (frames[s] < 0 || frames[s] >= nfr) return fail(TG_ERR_INVALID, "frame index outside the system");
+    if (q_stride < (uint64_t)b->sys->H.p.nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
+    if (dQ && dq_stride < (uint64_t)b->sys->H.p.nq) return fail(TG_ERR_INVALID, "row stride of dQ shorter than a configuration");
+    return TG_SUCCESS;
+}
+
+int tg_batch_frame_kinematics_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                                     uint64_t dq_row_stride_doubles, int32_t n_frames, const int32_t *frames_host, double *G_dev,
+                                     double *VB_dev, double *JP_dev, double *JB_dev) {
+    if (int rc = frames_check(b, n_states, Q_dev, dQ_dev, q_row_stride_doubles, dq_row_stride_doubles, n_frames, frames_host, G_dev, VB_dev, JP_dev, JB_dev)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_frame_kinematics_lds(b->sys, geo)) return rc;
+    const long long teams = (long long)b->batch * n_states, per_block = 64 / b->sys->team;
+    if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many states for one launch");
+    HIP_TRY(hipSetDevice(b->device));
+    // the cached table serves while the selection stays; a new selection waits for the launches that read the old one (once), then
+    // overwrites it, on a larger buffer only if it grew
+    if (!b->frames_tab || b->frames_sel.size() != (size_t)n_frames || !std::equal(b->frames_sel.begin(), b->frames_sel.end(), frames_host)) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        b->frames_sel.clear();
+        tg::frames_table(b->sys->H, n_frames, frames_host, b->frames_tab_host, b->frames_off_host);
+        if (b->frames_tab_host.size() > b->frames_tab.count() || b->frames_off_host.size() > b->frames_off.count()) {
+            b->frames_tab.reset(); b->frames_off.reset();
+            HIP_TRY(b->frames_tab.ensure(b->frames_tab_host.size()));
+            HIP_TRY(b->frames_off.ensure(b->frames_off_host.size()));
+        }
+        HIP_TRY(hipMemcpyAsync(b->frames_tab.get(), b->frames_tab_host.data(), b->frames_tab_host.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->frames_off.get(), b->frames_off_host.data(), b->frames_off_host.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        b->frames_sel.assign(frames_host, frames_host + n_frames);
+    }
+    // the states are arguments of the call: nothing of the integrator (q1, q2, p, lambda1, status, times) is read or written, and
+    // neither a loaded specialised library nor a parameter table has a say (poses and twists know no masses or forces)
+    tg::RunArgs A = base_args(b, tg::MODE_FRAMES);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.iters = A.status = nullptr;
+    A.n_steps = n_states;
+    tg::FrameArgs J{};
+    tg::frames_layout(b->P.lds_per_team, J);
+    J.Q = Q_dev; J.dQ = dQ_dev; J.G = G_dev; J.VB = VB_dev; J.JP = JP_dev; J.JB = JB_dev;
+    J.tab = b->frames_tab.get(); J.off = b->frames_off.get();
+    J.q_stride = (size_t)q_row_stride_doubles; J.dq_stride = (size_t)dq_row_stride_doubles;
+    J.n_states = n_states; J.n_frames = n_frames;
+    LaunchTiming timed;
+    if (int rc = timing_begin(b, timed)) return rc;
+    int rc = tg_detail::launch_frames(b->sys->team, b->d_prog.get(), A, J, (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[0][0].add(tg::MODE_FRAMES);      // a refused launch (the profiling build) is not counted
+    return timing_end(b, timed, rc);
+}
+
+int tg_batch_frame_kinematics(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, int32_t n_frames,
+                              const int32_t *frames_host, double *G, double *VB, double *JP, double *JB) {
+    const uint64_t nq_ = b && b->sys ? (uint64_t)b->sys->H.p.nq : 0;
+    if (int rc = frames_check(b, n_states, Q_host, dQ_host, nq_, nq_, n_frames, frames_host, G, VB, JP, JB)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_frame_kinematics_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    // staging of this call alone (its size follows n_states and the selection): Q, dQ in; the outputs asked for out
+    const size_t rows = (size_t)b->batch * n_states, nq = b->P.nq, F = (size_t)n_frames;
+    const size_t n_q = rows * nq, n_dq = dQ_host ? n_q : 0, n_g = G ? rows * F * 12 : 0, n_vb = VB ? rows * F * 6 : 0;
+    const size_t n_jp = JP ? rows * F * nq * 3 : 0, n_jb = JB ? rows * F * nq * 6 : 0;
+    tg::DeviceBuffer<double> stage;
+    HIP_TRY(stage.ensure(n_q + n_dq + n_g + n_vb + n_jp + n_jb));
+    double *q = stage.get(), *dq = q + n_q, *g = dq + n_dq, *vb = g + n_g, *jp = vb + n_vb, *jb = jp + n_jp;
+    HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (n_dq) HIP_TRY(hipMemcpyAsync(dq, dQ_host, n_dq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    int rc = tg_batch_frame_kinematics_device(b, n_states, q, nq, dQ_host ? dq : nullptr, nq, n_frames, frames_host, G ? g : nullptr,
+                                              VB ? vb : nullptr, JP ? jp : nullptr, JB ? jb : nullptr);
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
+            rc = fail(TG_ERR_HIP, "copy of the results failed");
+    };
+    back(G, g, n_g * sizeof(double)); back(VB, vb, n_vb * sizeof(double)); back(JP, jp, n_jp * sizeof(double)); back(JB, jb, n_jb * sizeof(double));
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
 }

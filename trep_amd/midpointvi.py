@@ -23,6 +23,7 @@ from .errors import ConvergenceError
 Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")      # BatchMidpointVI.satisfy_constraints
 Equilibrium = collections.namedtuple("Equilibrium", "Q mu V iterations status")     # BatchMidpointVI.minimize_potential_energy
 InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h status")     # BatchMidpointVI.inverse_dynamics
+FrameKinematics = collections.namedtuple("FrameKinematics", "g vb p_dq vb_ddq")         # BatchMidpointVI.frame_kinematics
 
 
 class BatchMidpointVI(object):
@@ -244,7 +245,7 @@ class BatchMidpointVI(object):
         `spec_library` the loaded file.  The par_* keys: the same for the per-trajectory parameter kernels (set_parameters),
         over all kernel modes (ALL_MODES), with `par_spec_launch_mask` / `par_generic_launch_mask` the raw mode bits as
         `spec_launch_mask` / `generic_launch_mask` are for the default kernels (bit 9: the projection, bit 10: the equilibrium search,
-        bit 11: inverse dynamics, which have no name in ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
+        bit 11: inverse dynamics, bit 12: frame kinematics, which have no name in ALL_MODES); `parameter_rows` / `parameter_group` the current table (0: none)."""
         out = np.zeros(8, dtype=np.int32)
         _lib.check(self._L.tg_batch_info(self._h, out.ctypes.data_as(_lib._c_ip)))
         names = lambda bits: sorted(n for n, m in self.MODES.items() if (int(bits) >> m) & 1)
@@ -616,6 +617,75 @@ class BatchMidpointVI(object):
         X = np.concatenate([Q, r.P, v], axis=2)
         U_full = np.concatenate([r.U, Q[:, 1:, self.nd:]], axis=2)
         return X, U_full, r
+
+    def _frame_indices(self, frames):
+        """frames (Frame objects, names or indices into system.frames; None: all of them) -> contiguous int32 indices."""
+        all_frames = self._system.frames
+        if frames is None:
+            return np.arange(len(all_frames), dtype=np.int32)
+        place = {id(f): i for i, f in enumerate(all_frames)}
+        out = []
+        for f in frames:
+            if isinstance(f, (int, np.integer)):
+                if not 0 <= int(f) < len(all_frames):
+                    raise ValueError("frame index %d outside the system's %d frames" % (int(f), len(all_frames)))
+                out.append(int(f))
+            else:
+                out.append(place[id(self._system.get_frame(f))])
+        if not out:
+            raise ValueError("no frames selected")
+        return np.array(out, dtype=np.int32)
+
+    def frame_kinematics(self, Q, dQ=None, frames=None, jacobians=False):
+        """Where the frames are (include/trep_amd.h, tg_batch_frame_kinematics): Q [B][nq] or [B][M][nq], kinematic configs included,
+        dQ of the same shape or None; `frames` a list of Frame objects, names or indices into system.frames (default: all of them;
+        repeats and any order allowed).  Every state is one team, all B x M of them in one launch.  Returns the namedtuple (g
+        [B][M][F][3][4], vb [B][M][F][6], p_dq [B][M][F][nq][3], vb_ddq [B][M][F][nq][6]): rows 0..2 of Frame.g() (g[..., 3] is
+        Frame.p()), Frame.vb() as (v, omega), Frame.p_dq(k)[:3] and Frame.vb_ddq(k) as (v, omega) for every config k (zero off the
+        frame's path).  vb is None without dQ, the Jacobians are None without jacobians=True; for Q [B][nq] the M axis is dropped.
+        Masses, parameters, a specialised library and the time base have no say; the integrator state of the batch is left alone."""
+        self.refresh()
+        B, nq = self._batch, self.nq
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        flat = Q.ndim == 2
+        if flat:
+            Q = Q[:, None, :]
+        if Q.ndim != 3 or Q.shape[0] != B or Q.shape[1] < 1 or Q.shape[2] != nq:
+            raise ValueError("expected Q of shape (%d, %d) or (%d, M, %d) with M >= 1, got %r" % (B, nq, B, nq, Q.shape))
+        M = Q.shape[1]
+        if dQ is not None:
+            dQ = np.ascontiguousarray(dQ, dtype=np.float64)
+            dQ = _lib.as_f64(dQ[:, None, :] if flat and dQ.ndim == 2 else dQ, (B, M, nq))
+        idx = self._frame_indices(frames)
+        F = len(idx)
+        g = np.zeros((B, M, F, 3, 4))
+        vb = None if dQ is None else np.zeros((B, M, F, 6))
+        p_dq = np.zeros((B, M, F, nq, 3)) if jacobians else None
+        vb_ddq = np.zeros((B, M, F, nq, 6)) if jacobians else None
+        rc = self._L.tg_batch_frame_kinematics(self._h, M, Q.ctypes.data, None if dQ is None else dQ.ctypes.data, F, idx.ctypes.data,
+                                               g.ctypes.data, None if vb is None else vb.ctypes.data,
+                                               None if p_dq is None else p_dq.ctypes.data, None if vb_ddq is None else vb_ddq.ctypes.data)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        drop = (lambda a: None if a is None else a[:, 0]) if flat else (lambda a: a)
+        return FrameKinematics(drop(g), drop(vb), drop(p_dq), drop(vb_ddq))
+
+    def frame_kinematics_device(self, n_states, Q_dev, q_row_stride=None, dQ_dev=None, dq_row_stride=None, frames=None, g_dev=None,
+                                vb_dev=None, p_dq_dev=None, vb_ddq_dev=None):
+        """frame_kinematics on device pointers, asynchronous on the batch's stream (tg_batch_frame_kinematics_device).  Row (b, m) is
+        read at Q_dev + (b n_states + m) q_row_stride doubles (dQ_dev likewise with dq_row_stride): the default nq for packed
+        arrays, nX to read the configurations straight from a rollout's X [B][n_states][nX].  The outputs are laid out as
+        frame_kinematics returns them ([B][n_states][F]...); any may be None, not all.  `frames` as for frame_kinematics; while it
+        stays the same from call to call nothing is allocated."""
+        self.refresh()
+        idx = self._frame_indices(frames)
+        rc = self._L.tg_batch_frame_kinematics_device(self._h, int(n_states), Q_dev, int(self.nq if q_row_stride is None else q_row_stride),
+                                                      dQ_dev, int(self.nq if dq_row_stride is None else dq_row_stride), len(idx),
+                                                      idx.ctypes.data, g_dev, vb_dev, p_dq_dev, vb_ddq_dev)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
 
     def _seeds(self, seeds, most):
         """(seed1,) or (seed1, seed2) -> contiguous int32 [B] arrays: the input variable each trajectory's direction follows, numbered
