@@ -551,6 +551,44 @@ int tg_batch_frame_kinematics_device(tg_batch *b, int32_t n_states, const double
                                      int32_t n_frames, const int32_t *frames_host,
                                      double *G_dev, double *VB_dev, double *JP_dev, double *JB_dev);
 
+/* ---- batched tape measures ---------------------------------------------------------------------------------------------
+ * Lengths of broken lines through frame origins (reference tapemeasure.py; the host class trep_amd.TapeMeasure is the
+ * specification): for configurations Q [B][n_states][nq] (kinematic configs included) and rates dQ of the same shape, the length,
+ * its rate and their config derivatives of every selected measure of every state, one team per state, all in one launch.
+ * Measure t is the frames frames_host[measure_start_host[t] .. measure_start_host[t + 1]) (indices into System.frames, host arrays
+ * in both variants): at least two, consecutive ones different, repeats allowed.  Its segments join consecutive frames.  For a
+ * segment from a to b: d = p_b - p_a, l = |d|; only the configs on exactly one of the two paths move it (a common ancestor moves
+ * both ends rigidly); for those d_k = JP_b[k] - JP_a[k] (JP of tg_batch_frame_kinematics), d_jk = P_b[j,k] - P_a[j,k] with
+ * P_F[j,k] = a_j x JP_F[k] for j, k on F's path, j rotary and the one nearer the world (or j == k), else 0, and
+ *   l_k = d . d_k / l,   l_jk = (d_j . d_k + d . d_jk - l_j l_k) / l,   v = d . (sum_k d_k dq_k) / l,   v_k = sum_j l_jk dq_j.
+ * Outputs, sums over the segments of a measure (segments ascending, configs ascending within a sum):
+ *   L   [B][n_states][T]          TapeMeasure.length();
+ *   V   [B][n_states][T]          velocity(); it needs dQ;
+ *   LQ  [B][n_states][T][nq]      length_dq(k) = velocity_ddq(k);
+ *   VQ  [B][n_states][T][nq]      velocity_dq(k); it needs dQ;
+ *   LQQ [B][n_states][T][nq][nq]  length_dqdq(j, k) = velocity_ddqdq(j, k).
+ * Any output may be NULL; every entry of a requested output is written, and a derivative entry that no segment's exclusive configs
+ * reach is an exact 0.0.  A segment of zero length divides by zero, as on the host: that measure's outputs are then not finite, and
+ * there is no status array.  Third derivatives stay on the host.  A state's answer does not depend on B, n_states or its neighbours.
+ * One generic kernel (mode 13 in tg_batch_info) whatever masses, parameters, a specialised library or the time base the batch has
+ * set; the integrator state of the batch is not touched.
+ * TG_ERR_INVALID, decided before a device is touched, for n_states < 1, a null Q, n_measures < 1 or null tables, a measure with
+ * fewer than two frames, two equal consecutive frames in a measure, a frame index outside the system, V or VQ without dQ, all five
+ * outputs null, and (_device) a row stride under nq; TG_ERR_UNSUPPORTED for the profiling build and if the workgroup's LDS -- per
+ * team the rollout slice plus 14 doubles for each of max(16, segments of the longest measure) staged segments -- exceeds 160 KiB
+ * (tg_system_tape_measures_lds: out = team size, doubles per team, bytes per workgroup, 0; the same refusal without a device).
+ * The _device variant takes device pointers, launches on the batch's stream and does not synchronise; row strides as for
+ * tg_batch_frame_kinematics_device (nX reads a rollout's X in place).  The table of a selection lives in buffers of the batch: a
+ * call with the selection of the call before allocates nothing; another selection waits for the stream once and rebuilds it. */
+int tg_system_tape_measures_lds(const tg_system *sys, int32_t longest_measure_segments, int32_t out[4]);
+int tg_batch_tape_measures(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host,
+                           int32_t n_measures, const int32_t *measure_start_host, const int32_t *frames_host,
+                           double *L, double *V, double *LQ, double *VQ, double *LQQ);
+int tg_batch_tape_measures_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                  const double *dQ_dev, uint64_t dq_row_stride_doubles,
+                                  int32_t n_measures, const int32_t *measure_start_host, const int32_t *frames_host,
+                                  double *L_dev, double *V_dev, double *LQ_dev, double *VQ_dev, double *LQQ_dev);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

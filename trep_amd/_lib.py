@@ -172,6 +172,13 @@ _FRAMES_SIGNATURES = {
     "tg_batch_frame_kinematics_device": (ctypes.c_int, [_vp, _i32, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# Batched tape measures: likewise.
+_TAPE_SIGNATURES = {
+    "tg_system_tape_measures_lds": (ctypes.c_int, [_vp, _i32, _c_ip]),
+    "tg_batch_tape_measures": (ctypes.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_tape_measures_device": (ctypes.c_int, [_vp, _i32, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class LibraryError(RuntimeError):
     pass
@@ -191,7 +198,7 @@ def lib():
         # and it must be in the environment before the HIP runtime initialises, i.e. before the library that links it is loaded.
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()) + list(_INVERSE_SIGNATURES.items()) + list(_FRAMES_SIGNATURES.items()):
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()) + list(_INVERSE_SIGNATURES.items()) + list(_FRAMES_SIGNATURES.items()) + list(_TAPE_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -200,7 +207,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES) + list(_INVERSE_SIGNATURES) + list(_FRAMES_SIGNATURES))
+    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES) + list(_INVERSE_SIGNATURES) + list(_FRAMES_SIGNATURES) + list(_TAPE_SIGNATURES))
 
 
 def check(rc):

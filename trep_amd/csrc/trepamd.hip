@@ -21,6 +21,7 @@
 #include "mvi_equilibrium.hpp"
 #include "mvi_inverse.hpp"
 #include "mvi_frames.hpp"
+#include "mvi_tape.hpp"
 #include "schedule.hpp"
 #include <dlfcn.h>
 
@@ -35,6 +36,8 @@ int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_pr
 int launch_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the frame-kinematics kernel (trepamd_frames.hip, likewise)
 int launch_frames(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::FrameArgs &J, int grid, size_t lds, hipStream_t stream);
+// the tape-measure kernel (trepamd_tape.hip, likewise)
+int launch_tape(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::TapeArgs &J, int grid, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -140,6 +143,11 @@ struct tg_batch {
     std::vector<double> frames_off_host;
     tg::DeviceBuffer<int> frames_tab;
     tg::DeviceBuffer<double> frames_off;
+    // table of tg_batch_tape_measures (mvi_tape.hpp, tape_table) for the selection (tape_start, tape_sel), cached likewise
+    std::vector<int32_t> tape_start, tape_sel;
+    tg::TapeTable tape_host;
+    tg::DeviceBuffer<int> tape_words;
+    tg::DeviceBuffer<double> tape_off;
     tg::DeviceBuffer<int> seeds;      // [2][batch] direction variables of the forward-mode calls
     tg::DeviceBuffer<double> d1[12];
     bool have_d1 = false;
@@ -1387,6 +1395,132 @@ int tg_batch_frame_kinematics(tg_batch *b, int32_t n_states, const double *Q_hos
             rc = fail(TG_ERR_HIP, "copy of the results failed");
     };
     back(G, g, n_g * sizeof(double)); back(VB, vb, n_vb * sizeof(double)); back(JP, jp, n_jp * sizeof(double)); back(JB, jb, n_jb * sizeof(double));
+    if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
+    return rc;
+}
+
+// ---- batched tape measures (mvi_tape.hpp): one team per state, one launch
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the tape-measure kernel for this system and a selection whose
+ * longest measure has longest_measure_segments segments (out[0..2]; out[3] 0): the rollout slice plus kTapeStage doubles for each of
+ * max(kTapePass, longest_measure_segments) staged segments (mvi_tape.hpp).  TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a
+ * workgroup can have, and in the profiling build. */
+int tg_system_tape_measures_lds(const tg_system *sys, int32_t longest_measure_segments, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    if (longest_measure_segments < 1) return fail(TG_ERR_INVALID, "a measure has at least one segment");
+    tg::TapeArgs J{};
+    tg::tape_layout(sys->H.p.lds_per_team, (int)std::min<int32_t>(longest_measure_segments, 1 << 24), J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system or measure too large for the LDS-resident tape-measure kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no tape-measure kernel");
+#endif
+    return rc;
+}
+
+// what both entry points refuse, decided on the host before a device is touched: first what the arguments alone show, then what
+// needs the system (the strides are nq for the host variant); longest: the segments of the longest measure
+static int tape_check(const tg_batch *b, int32_t n_states, const double *Q, const double *dQ, uint64_t q_stride, uint64_t dq_stride,
+                      int32_t n_measures, const int32_t *start, const int32_t *frames, const double *L, const double *V, const double *LQ,
+                      const double *VQ, const double *LQQ, int32_t &longest) {
+    if (n_states < 1) return fail(TG_ERR_INVALID, "n_states must be at least 1");
+    if (!Q) return fail(TG_ERR_INVALID, "null Q");
+    if (n_measures < 1 || !start || !frames) return fail(TG_ERR_INVALID, "no measures selected");
+    longest = 0;
+    for (int32_t t = 0; t < n_measures; t++) {
+        if (start[t] < 0 || (int64_t)start[t + 1] - start[t] < 2) return fail(TG_ERR_INVALID, "a measure needs at least two frames");
+        longest = std::max(longest, start[t + 1] - start[t] - 1);
+        for (int32_t i = start[t]; i + 1 < start[t + 1]; i++)
+            if (frames[i] == frames[i + 1]) return fail(TG_ERR_INVALID, "two equal consecutive frames in a measure");
+    }
+    if ((V || VQ) && !dQ) return fail(TG_ERR_INVALID, "V or VQ without dQ");
+    if (!L && !V && !LQ && !VQ && !LQQ) return fail(TG_ERR_INVALID, "no output asked for");
+    if (!b || !b->sys) return fail(TG_ERR_INVALID, "null argument");
+    const int32_t nfr = (int32_t)b->sys->H.frame_anchor.size();
+    for (int32_t i = start[0]; i < start[n_measures]; i++)
+        if (frames[i] < 0 || frames[i] >= nfr) return fail(TG_ERR_INVALID, "frame index outside the system");
+    if (q_stride < (uint64_t)b->sys->H.p.nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
+    if (dQ && dq_stride < (uint64_t)b->sys->H.p.nq) return fail(TG_ERR_INVALID, "row stride of dQ shorter than a configuration");
+    return TG_SUCCESS;
+}
+
+int tg_batch_tape_measures_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                                  uint64_t dq_row_stride_doubles, int32_t n_measures, const int32_t *measure_start_host,
+                                  const int32_t *frames_host, double *L_dev, double *V_dev, double *LQ_dev, double *VQ_dev, double *LQQ_dev) {
+    int32_t longest = 0;
+    if (int rc = tape_check(b, n_states, Q_dev, dQ_dev, q_row_stride_doubles, dq_row_stride_doubles, n_measures, measure_start_host, frames_host,
+                            L_dev, V_dev, LQ_dev, VQ_dev, LQQ_dev, longest)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_tape_measures_lds(b->sys, longest, geo)) return rc;
+    const long long teams = (long long)b->batch * n_states, per_block = 64 / b->sys->team;
+    if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many states for one launch");
+    HIP_TRY(hipSetDevice(b->device));
+    // the cached table serves while the selection stays; a new selection waits for the launches that read the old one (once), then
+    // overwrites it, on a larger buffer only if it grew
+    const int32_t *f0 = frames_host + measure_start_host[0];
+    const size_t n_fr = (size_t)(measure_start_host[n_measures] - measure_start_host[0]);
+    bool same = b->tape_words && b->tape_start.size() == (size_t)n_measures + 1 && b->tape_sel.size() == n_fr && std::equal(b->tape_sel.begin(), b->tape_sel.end(), f0);
+    for (int32_t t = 0; same && t <= n_measures; t++) same = b->tape_start[t] == measure_start_host[t] - measure_start_host[0];
+    if (!same) {
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        b->tape_start.clear(); b->tape_sel.clear();
+        tg::tape_table(b->sys->H, n_measures, measure_start_host, frames_host, b->tape_host);
+        if (b->tape_host.words.size() > b->tape_words.count() || b->tape_host.off.size() > b->tape_off.count()) {
+            b->tape_words.reset(); b->tape_off.reset();
+            HIP_TRY(b->tape_words.ensure(b->tape_host.words.size()));
+            HIP_TRY(b->tape_off.ensure(b->tape_host.off.size()));
+        }
+        HIP_TRY(hipMemcpyAsync(b->tape_words.get(), b->tape_host.words.data(), b->tape_host.words.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->tape_off.get(), b->tape_host.off.data(), b->tape_host.off.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        b->tape_sel.assign(f0, f0 + n_fr);
+        for (int32_t t = 0; t <= n_measures; t++) b->tape_start.push_back(measure_start_host[t] - measure_start_host[0]);
+    }
+    // the states are arguments of the call: nothing of the integrator (q1, q2, p, lambda1, status, times) is read or written, and
+    // neither a loaded specialised library nor a parameter table has a say (lengths know no masses or forces)
+    tg::RunArgs A = base_args(b, tg::MODE_TAPE);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.iters = A.status = nullptr;
+    A.n_steps = n_states;
+    tg::TapeArgs J{};
+    tg::tape_layout(b->P.lds_per_team, longest, J);
+    J.Q = Q_dev; J.dQ = dQ_dev; J.L = L_dev; J.V = V_dev; J.LQ = LQ_dev; J.VQ = VQ_dev; J.LQQ = LQQ_dev;
+    const int *words = b->tape_words.get();
+    J.ftab = words; J.off = b->tape_off.get();
+    J.seg = words + b->tape_host.o_seg; J.mstart = words + b->tape_host.o_mstart; J.cuts = words + b->tape_host.o_cuts;
+    J.q_stride = (size_t)q_row_stride_doubles; J.dq_stride = (size_t)dq_row_stride_doubles;
+    J.n_states = n_states; J.n_measures = n_measures; J.n_pass = b->tape_host.n_pass;
+    LaunchTiming timed;
+    if (int rc = timing_begin(b, timed)) return rc;
+    int rc = tg_detail::launch_tape(b->sys->team, b->d_prog.get(), A, J, (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[0][0].add(tg::MODE_TAPE);      // a refused launch (the profiling build) is not counted
+    return timing_end(b, timed, rc);
+}
+
+int tg_batch_tape_measures(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, int32_t n_measures,
+                           const int32_t *measure_start_host, const int32_t *frames_host, double *L, double *V, double *LQ, double *VQ, double *LQQ) {
+    const uint64_t nq_ = b && b->sys ? (uint64_t)b->sys->H.p.nq : 0;
+    int32_t longest = 0;
+    if (int rc = tape_check(b, n_states, Q_host, dQ_host, nq_, nq_, n_measures, measure_start_host, frames_host, L, V, LQ, VQ, LQQ, longest)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_tape_measures_lds(b->sys, longest, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    // staging of this call alone (its size follows n_states and the selection): Q, dQ in; the outputs asked for out
+    const size_t rows = (size_t)b->batch * n_states, nq = b->P.nq, T = (size_t)n_measures;
+    const size_t n_q = rows * nq, n_dq = dQ_host ? n_q : 0, n_l = L ? rows * T : 0, n_v = V ? rows * T : 0;
+    const size_t n_lq = LQ ? rows * T * nq : 0, n_vq = VQ ? rows * T * nq : 0, n_lqq = LQQ ? rows * T * nq * nq : 0;
+    tg::DeviceBuffer<double> stage;
+    HIP_TRY(stage.ensure(n_q + n_dq + n_l + n_v + n_lq + n_vq + n_lqq));
+    double *q = stage.get(), *dq = q + n_q, *l = dq + n_dq, *v = l + n_l, *lq = v + n_v, *vq = lq + n_lq, *lqq = vq + n_vq;
+    HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (n_dq) HIP_TRY(hipMemcpyAsync(dq, dQ_host, n_dq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    int rc = tg_batch_tape_measures_device(b, n_states, q, nq, dQ_host ? dq : nullptr, nq, n_measures, measure_start_host, frames_host,
+                                           L ? l : nullptr, V ? v : nullptr, LQ ? lq : nullptr, VQ ? vq : nullptr, LQQ ? lqq : nullptr);
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
+            rc = fail(TG_ERR_HIP, "copy of the results failed");
+    };
+    back(L, l, n_l * sizeof(double)); back(V, v, n_v * sizeof(double)); back(LQ, lq, n_lq * sizeof(double));
+    back(VQ, vq, n_vq * sizeof(double)); back(LQQ, lqq, n_lqq * sizeof(double));
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
 }

@@ -24,6 +24,7 @@ Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")  
 Equilibrium = collections.namedtuple("Equilibrium", "Q mu V iterations status")     # BatchMidpointVI.minimize_potential_energy
 InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h status")     # BatchMidpointVI.inverse_dynamics
 FrameKinematics = collections.namedtuple("FrameKinematics", "g vb p_dq vb_ddq")         # BatchMidpointVI.frame_kinematics
+TapeMeasures = collections.namedtuple("TapeMeasures", "length velocity length_dq velocity_dq length_dqdq")      # BatchMidpointVI.tape_measures
 
 
 class BatchMidpointVI(object):
@@ -683,6 +684,86 @@ class BatchMidpointVI(object):
         rc = self._L.tg_batch_frame_kinematics_device(self._h, int(n_states), Q_dev, int(self.nq if q_row_stride is None else q_row_stride),
                                                       dQ_dev, int(self.nq if dq_row_stride is None else dq_row_stride), len(idx),
                                                       idx.ctypes.data, g_dev, vb_dev, p_dq_dev, vb_ddq_dev)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+
+    def _measure_tables(self, measures):
+        """measures (each a TapeMeasure of this system or a sequence of frames by name, object or index) -> (start [T + 1], frames)
+        as contiguous int32, the layout of tg_batch_tape_measures.  Raises ValueError for what the library would refuse."""
+        from .tapemeasure import TapeMeasure
+        if measures is None or isinstance(measures, (TapeMeasure, str)) or len(measures) == 0:
+            raise ValueError("measures: a non-empty list of TapeMeasure objects or frame sequences")
+        start, flat = [0], []
+        for m in measures:
+            if isinstance(m, TapeMeasure):
+                if m.system is not self._system:
+                    raise ValueError("a TapeMeasure of another system")
+                m = m.frames
+            elif isinstance(m, str):
+                raise ValueError("a measure is a sequence of frames, not one name")
+            try:
+                idx = [] if len(m) == 0 else [int(i) for i in self._frame_indices(m)]
+            except (KeyError, TypeError) as e:          # an unknown name, a frame of another system, not a frame at all
+                raise ValueError("not a frame of this system in a measure: %s" % (e,))
+            if len(idx) < 2:
+                raise ValueError("a measure needs at least two frames")
+            if any(a == b for a, b in zip(idx[:-1], idx[1:])):
+                raise ValueError("two equal consecutive frames in a measure")
+            flat += idx
+            start.append(len(flat))
+        return np.array(start, dtype=np.int32), np.array(flat, dtype=np.int32)
+
+    def tape_measures(self, Q, dQ=None, measures=None, gradients=False, hessians=False):
+        """Lengths of broken lines through frame origins (include/trep_amd.h, tg_batch_tape_measures): Q [B][nq] or [B][M][nq], kinematic
+        configs included, dQ of the same shape or None; `measures` a list whose items are trep_amd.TapeMeasure objects of this system
+        or sequences of frames (names, Frame objects or indices into system.frames; at least two, consecutive ones different).  Every
+        state is one team, all B x M of them in one launch.  Returns the namedtuple (length [B][M][T], velocity [B][M][T], length_dq
+        [B][M][T][nq], velocity_dq [B][M][T][nq], length_dqdq [B][M][T][nq][nq]): what TapeMeasure.length(), velocity(), length_dq(k)
+        (= velocity_ddq(k)), velocity_dq(k) and length_dqdq(j, k) (= velocity_ddqdq(j, k)) return at each state.  velocity and
+        velocity_dq are None without dQ, the two gradients without gradients=True, the Hessian without hessians=True; for Q [B][nq]
+        the M axis is dropped.  A config that moves no segment of a measure has exact zeros there.  A segment of zero length gives
+        non-finite values for its measure, as on the host.  The integrator state of the batch is left alone."""
+        self.refresh()
+        B, nq = self._batch, self.nq
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        flat = Q.ndim == 2
+        if flat:
+            Q = Q[:, None, :]
+        if Q.ndim != 3 or Q.shape[0] != B or Q.shape[1] < 1 or Q.shape[2] != nq:
+            raise ValueError("expected Q of shape (%d, %d) or (%d, M, %d) with M >= 1, got %r" % (B, nq, B, nq, Q.shape))
+        M = Q.shape[1]
+        if dQ is not None:
+            dQ = np.ascontiguousarray(dQ, dtype=np.float64)
+            dQ = _lib.as_f64(dQ[:, None, :] if flat and dQ.ndim == 2 else dQ, (B, M, nq))
+        start, frames = self._measure_tables(measures)
+        T = len(start) - 1
+        length = np.zeros((B, M, T))
+        velocity = None if dQ is None else np.zeros((B, M, T))
+        length_dq = np.zeros((B, M, T, nq)) if gradients else None
+        velocity_dq = np.zeros((B, M, T, nq)) if gradients and dQ is not None else None
+        length_dqdq = np.zeros((B, M, T, nq, nq)) if hessians else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self._L.tg_batch_tape_measures(self._h, M, Q.ctypes.data, ptr(dQ), T, start.ctypes.data, frames.ctypes.data, ptr(length),
+                                            ptr(velocity), ptr(length_dq), ptr(velocity_dq), ptr(length_dqdq))
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        drop = (lambda a: None if a is None else a[:, 0]) if flat else (lambda a: a)
+        return TapeMeasures(drop(length), drop(velocity), drop(length_dq), drop(velocity_dq), drop(length_dqdq))
+
+    def tape_measures_device(self, n_states, Q_dev, q_row_stride=None, dQ_dev=None, dq_row_stride=None, measures=None, length_dev=None,
+                             velocity_dev=None, length_dq_dev=None, velocity_dq_dev=None, length_dqdq_dev=None):
+        """tape_measures on device pointers, asynchronous on the batch's stream (tg_batch_tape_measures_device).  Row (b, m) is read at
+        Q_dev + (b n_states + m) q_row_stride doubles (dQ_dev likewise with dq_row_stride): the default nq for packed arrays, nX to
+        read the configurations straight from a rollout's X [B][n_states][nX].  The outputs are laid out as tape_measures returns them ([B][n_states][T]...); any may be None, not all; the two
+        velocity outputs need dQ_dev.  `measures` as for tape_measures; while it stays the same from call to call nothing is allocated."""
+        self.refresh()
+        start, frames = self._measure_tables(measures)
+        rc = self._L.tg_batch_tape_measures_device(self._h, int(n_states), Q_dev, int(self.nq if q_row_stride is None else q_row_stride),
+                                                   dQ_dev, int(self.nq if dq_row_stride is None else dq_row_stride), len(start) - 1,
+                                                   start.ctypes.data, frames.ctypes.data, length_dev, velocity_dev, length_dq_dev,
+                                                   velocity_dq_dev, length_dqdq_dev)
         if rc == _lib.ERR_INVALID:
             raise ValueError(self._L.tg_last_error().decode())
         _lib.check(rc)

@@ -2,7 +2,8 @@
 config derivatives (reference: trep/tapemeasure.py:14-70, 125-195; _trep/tapemeasure.c).
 
 Host-side numpy queries for modelling and checks (e.g. tendon lengths); sums of the two-frame segment formulas of
-``element_queries`` (the same ones behind LinearSpring / LinearDamper).  Nothing here runs on the device.
+``element_queries`` (the same ones behind LinearSpring / LinearDamper).  For many states at once -- lengths, rates, gradients and
+Hessians of any number of measures in one launch on the device -- see ``BatchMidpointVI.tape_measures``, which takes these objects.
 """
 from . import element_queries as _eq
 
