@@ -589,6 +589,44 @@ int tg_batch_tape_measures_device(tg_batch *b, int32_t n_states, const double *Q
                                   int32_t n_measures, const int32_t *measure_start_host, const int32_t *frames_host,
                                   double *L_dev, double *V_dev, double *LQ_dev, double *VQ_dev, double *LQQ_dev);
 
+/* ---- batched computed torque ---------------------------------------------------------------------------------------------
+ * The continuous inverse of tg_batch_dynamics: for states Q, dQ, ddQ [B][n_states][nq] each (B = the batch size; kinematic configs
+ * included -- the kinematic part of ddQ is what tg_batch_dynamics calls ddqk) the inputs u and constraint forces lambda that produce
+ * those accelerations, the generalized force the motion needs in total and the part of it no input can supply.  One team per state,
+ * all in one launch (tests/dynamics_inverse_reference.py is the specification).  With Ad = Dh(q)[:, :nd], Ak = Dh(q)[:, nd:], M the
+ * dynamic block of L_ddqddq, the continuous equations M ddq_d - Ad' lambda = D0(q, dq, ddq_k) + F_du u:
+ *   r0 = D0 - M ddq_d, summed per (body, joint) item as tg_batch_dynamics sums its bias but with the accelerations of every config
+ *   (no M is formed, nothing is factored, M may be singular);
+ *   A = [F_du | +Ad'], nd x n, n = nu + nc, F_du at (q, dq); the multiplier columns carry a plus, unlike tg_batch_inverse_dynamics;
+ *   minimise |rho|^2 + ridge |z|^2, rho = r0 + A z, z = (u, lambda), through the augmented system
+ *   [[I, A], [A', -ridge I]] (-rho, z) = (-r0, 0) of size nd + n (Gauss-Jordan with implicit-scaled partial pivoting).  The unknowns
+ *   are forces: no step size takes part, and the batch's time base has no say.
+ * Outputs, each may be NULL: U [B][n_states][nu]; LAM [..][nc]; RHO [..][nd], zero where inputs and constraints can supply the
+ * motion; TAU [..][nd] = -r0 = F_du u + Ad' lambda - rho, the recursive-Newton-Euler answer (with one ConfigForce per config: the joint
+ * torques); ACC [..][nc] = Ad ddq_d + Ak ddq_k + sum_ij h_dqdq(i, j) dq_i dq_j, zero for accelerations consistent with the
+ * constraints (those tg_batch_dynamics returns); status [B][n_states]: TG_OK, or TG_SINGULAR when the solver rejects the image or
+ * its answer is not finite -- U, LAM and RHO of that state are then zero, TAU and ACC still written.  n == 0: nothing to solve,
+ * rho = r0.  A state's answer does not depend on B, n_states or its neighbours in the launch.
+ * A rank-deficient A with n <= nd and ridge == 0 is NOT detected (the pivot guard is 1e-20): such systems need ridge > 0, and the
+ * answer is then the ridge solution, not the minimum-norm one.
+ * Generic kernel of its own (mode 14 in tg_batch_info) whatever library the batch has; with a parameter table
+ * (tg_batch_set_parameters) its parameter twin runs (mode 14 in tg_batch_par_info) and trajectory b uses row b / group for masses,
+ * inertias, gravity and damping.  The integrator state of the batch (q1, q2, p, lambda1, status, iterations, times) is not touched.
+ * TG_ERR_INVALID, decided before a device is touched, for ridge < 0 or not finite, n_states < 1, a null Q, dQ or ddQ, n > nd with
+ * ridge == 0 (the image is structurally singular), and (_device) a row stride under nq; TG_ERR_UNSUPPORTED for the profiling build
+ * and if the workgroup's LDS -- per team the rollout slice plus (m + 1) m + nq + m doubles, m = nd + n -- exceeds 160 KiB
+ * (tg_system_dynamics_inverse_lds: out = team size, doubles per team, bytes per workgroup, 0; the same refusal without a device).
+ * The _device variant takes device pointers, launches on the batch's stream and does not synchronise; row (b, s) of Q is read at
+ * Q_dev + (b n_states + s) q_row_stride_doubles, dQ_dev and ddQ_dev likewise with their own strides (nX reads Q from a rollout's X). */
+int tg_system_dynamics_inverse_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_dynamics_inverse(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host,
+                              double ridge, double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *status);
+int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                     const double *dQ_dev, uint64_t dq_row_stride_doubles,
+                                     const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
+                                     double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev,
+                                     int32_t *status_dev);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

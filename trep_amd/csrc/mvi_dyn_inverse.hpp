@@ -1,0 +1,184 @@
+// mvi_dyn_inverse.hpp -- MODE_DYN_INVERSE: batched computed torque, one team per state (tg_batch_dynamics_inverse).
+//
+// The continuous counterpart of mvi_inverse.hpp.  Given states (q, dq, ddq) [B][M] with the accelerations of ALL configs, find the
+// inputs u and constraint forces lambda that produce them, the generalized force the motion needs in total, and the part of it no input
+// can supply.  In the notation of Core::dynamics (Ad = Dh(q)[:, :nd], Ak = Dh(q)[:, nd:], M the dynamic block of L_ddqddq) the
+// continuous equations are M ddq_d - Ad' lambda = D(q, dq, ddq_k, u), and every built-in force is affine in u: D = D0 + F_du u.
+// Per team (b, s), tests/dynamics_inverse_reference.py being the specification:
+//   r0 = D0 - M ddq_d: Core::dynamics' right-hand side with S_F = sum_k (W_k dq_k + J_k ddq_k) taken over EVERY config k, not only the
+//   kinematic ones, evaluated at u = 0 -- no M is formed, nothing is factored;
+//   TAU = -r0: what inputs and constraints have to supply together (the recursive-Newton-Euler answer);
+//   A = [F_du | +Ad'], nd x n, n = nu + nc: the ConfigForce coefficients, the wrench Jacobians wD through wr_in and the Dh items.  The
+//   multiplier columns carry a PLUS (TAU = F_du u + Ad' lambda; the discrete kernel has -Dh' there);
+//   z = (u, lambda) minimises |rho|^2 + ridge |z|^2 with rho = r0 + A z, solved in the augmented form
+//   [[I, A], [A', -ridge I]] (-rho, z) = (-r0, 0) by Core::gauss_jordan (not the normal equations: A'A squares the conditioning).  The
+//   unknowns are forces, not impulses: no step size appears anywhere in this kernel;
+//   ACC = Ad ddq_d + Ak ddq_k + sum_ij h_dq_i dq_j dq_i dq_j: how far the accelerations are from consistent with the constraints (zero for
+//   accelerations that dynamics() returned), from the Dh items and the cpair4 table as Core::dynamics builds its constraint rows, over
+//   all configs.
+// Outputs: U, LAM, RHO, TAU, ACC, status TG_OK or TG_SINGULAR (the solver rejected the image or its answer is not finite: U, LAM, RHO of
+// that state are zero, TAU and ACC still written).  With n == 0 nothing is solved: rho = r0.
+// A rank-deficient A with n <= nd and ridge == 0 is NOT detected unless a scaled pivot falls to 1e-20 (gauss_jordan's guard): such
+// systems need ridge > 0.
+//
+// No team reads what another writes and every sum runs in an order the team's own lanes fix (LDS only, no global atomics): a state's
+// result does not depend on B, M or the team's neighbours in the wavefront.
+// LDS of a team: the rollout slice and behind it the image [m][m + 1], m = nd + n, the given accelerations [nq] (the slice's own
+// place for them holds the kinematic ones alone) and the solver's row scales [m].
+// Compiled by hipcc (trepamd_dyn_inverse.hip: k_dyn_inverse) and, with TEAM = 1, by g++ for the CPU tests (tests/emu_dyn_inverse).
+#pragma once
+#include <cfloat>
+
+#include "mvi_core.hpp"
+
+namespace tg {
+
+constexpr int MODE_DYN_INVERSE = 14;
+
+// passed beside RunArgs (whose layout stays), as InverseArgs is; RunArgs supplies batch = B
+struct DynInverseArgs {
+    const double *Q, *dQ, *ddQ;  // states: row (b, s) at X + (b n_states + s) x_stride, [nq] each; ddQ = (ddq_d [nd] | ddq_k [nk])
+    double *U, *LAM, *RHO, *TAU, *ACC;   // [batch][n_states][nu], [..][nc], [..][nd], [..][nd], [..][nc]; each may be null
+    int *status;                 // [batch][n_states] or null
+    double ridge;
+    size_t q_stride, dq_stride, ddq_stride;      // doubles between consecutive rows (nq or more)
+    int n_states;
+    int o_kkt, o_ddq, o_scal;    // LDS offsets (doubles) behind the rollout slice
+    int lds_per_team;            // doubles per team: what the kernel strides its teams by
+};
+
+// the scratch layout of one team (host; the same numbers for the device launch and the emulation)
+inline void dyn_inverse_layout(int rollout_lds_per_team, int nq, int nd, int nu, int nc, DynInverseArgs &J) {
+    const int m = nd + nu + nc;
+    int off = (rollout_lds_per_team + 1) & ~1;
+    J.o_kkt = off; off += m * (m + 1);
+    J.o_ddq = off; off += nq;
+    J.o_scal = off; off += m;
+    J.lds_per_team = (off + 1) & ~1;
+}
+
+// team index i = b * n_states + s; i >= batch * n_states: an idle team, which still takes part in every TG_SYNC
+template <int TEAM, bool SPRINGS, bool PAR, class PROG, class ARGS>
+TG_HD void run_dyn_inverse(PROG &P, ARGS &A, const DynInverseArgs &J, const ParTable T, double *S, int lane, long long team_index) {
+    const int nq = P.nq, nd = P.nd, nu = P.nu, nc = P.nc, nf = P.nf, M = J.n_states;
+    const int n = nu + nc, m = nd + n, ld = m + 1;
+    const bool live = team_index < (long long)A.batch * M;
+    const size_t bs = (size_t)(live ? team_index : 0), b = bs / (size_t)M;
+    Core<TEAM, SPRINGS, PROG, double, PAR> core(P, S, lane, 1.0);      // (the step size takes no part)
+    if constexpr (PAR) core.par = T.rows + (b / (size_t)T.group) * (size_t)T.stride + 4 * P.n_bodies;
+    else (void)T;
+    core.init_sweep_schedule(false);
+    double *K = S + J.o_kkt, *ddq = S + J.o_ddq, *scal = S + J.o_scal, *rhs = S + P.o_f;
+
+    // ---- the state: q in q1 = q2, no inputs, no multipliers ------------------------------------------------------------------------
+    if (live) {
+        const double *q = J.Q + bs * J.q_stride, *dq = J.dQ + bs * J.dq_stride, *acc = J.ddQ + bs * J.ddq_stride;
+        TG_FOR(i, nq) { S[P.o_q1 + i] = q[i]; S[P.o_q2 + i] = q[i]; S[P.o_dq + i] = dq[i]; ddq[i] = acc[i]; }
+        TG_FOR(i, nd) S[P.o_p1 + i] = 0.0;
+        TG_FOR(i, nc) S[P.o_lam + i] = 0.0;
+        TG_FOR(i, nu) S[P.o_u + i] = 0.0;
+        TG_FOR(i, P.n_dh) { S[P.o_Dh1 + i] = 0.0; S[P.o_Dh2 + i] = 0.0; }
+        TG_FOR(i, nf) rhs[i] = 0.0;
+    }
+    TG_SYNC();
+
+    // ---- r0 and ACC: Core::dynamics' evaluation with the accelerations of all configs ----------------------------------------------
+    core.pose_sweep(live, 2);
+    core.attach_points(live, true, true);
+    core.spring_terms(live);
+    core.wrench_terms(live);
+    if (nc) {
+        core.constraints(live, 2, false, S + P.o_Dh2, 0);
+        if (live) {
+            TG_FOR(e, P.n_dh) {
+                const int c = P.dh_pack[8 * (size_t)e], k = P.dh_pack[8 * (size_t)e + 1];
+                lds_add(&rhs[nd + c], S[P.o_Dh2 + e] * ddq[k]);
+            }
+            TG_FOR(pp, P.n_cpair) {
+                const int *pw = P.cpair4 + 4 * (size_t)pp;
+                const int c = pw[0], na = pw[1], nb = pw[2], ka = pw[3] & 0xFFFF, kb = pw[3] >> 16;
+                const double h = core.con_d2(c, na, nb) * S[P.o_dq + ka] * S[P.o_dq + kb];
+                lds_add(&rhs[nd + c], na != nb ? 2.0 * h : h);
+            }
+        }
+        TG_SYNC();
+    }
+    core.jacobians(live);
+    core.velocities(live);
+    double *SF = S + P.o_G;      // S_F per body, in the (now dead) joint pose area
+    if (live) TG_FOR(idx, 6 * P.n_bodies) {
+        const int body = idx / 6, c6 = idx % 6;
+        double acc = 0.0;
+        for (int k = P.b_item_off[body]; k < P.b_item_off[body + 1]; k++) {
+            const int cfg = P.it_pack[4 * (size_t)k + 3] & 0xFFFF;
+            acc += S[P.o_W + 6 * k + c6] * S[P.o_dq + cfg] + S[P.o_J + 6 * k + c6] * ddq[cfg];
+        }
+        SF[idx] = acc;
+    }
+    TG_SYNC();
+    if (live) {
+        TG_FOR(it, P.n_items) {
+            const int body = P.it_pack[4 * (size_t)it], cfg = P.it_pack[4 * (size_t)it + 3] & 0xFFFF;
+            const double *I = S + P.o_I + 4 * body, *v = S + P.o_vB + 6 * body, *gam = S + P.o_gam + 3 * body;
+            const double *Jt = S + P.o_J + 6 * it;
+            double jv[6];
+            bracket(Jt, v, jv);
+            const double term = I[0] * (gam[0] * Jt[0] + gam[1] * Jt[1] + gam[2] * Jt[2]) - inner6(I, Jt, SF + 6 * body) - inner6(I, jv, v);
+            if (cfg < nd) lds_add(&rhs[cfg], term);
+        }
+        TG_FOR(i, nd) {      // the forces at u = 0 (the constant components of the wrenches are in wF)
+            double force = -core.damp_of(P, i) * S[P.o_dq + i];
+            if (core.has_cs()) force -= core.cs_d1(i, S[P.o_q2 + i]);
+            if (core.n_springs()) force -= S[P.o_sV + i];
+            if (core.n_wrenches()) force += S[P.o_wF + i];
+            if (core.has_damper()) force += S[P.o_sF + i];
+            lds_add(&rhs[i], force);
+        }
+    }
+    TG_SYNC();
+    if (live) {
+        if (J.TAU) TG_FOR(i, nd) J.TAU[bs * nd + i] = -rhs[i];
+        if (J.ACC) TG_FOR(c, nc) J.ACC[bs * nc + c] = rhs[nd + c];
+    }
+
+    // ---- the image [[I, A], [A', -ridge I]] with the right-hand side (-r0, 0): every lane owns rows of [I, A], then the transpose ----
+    const bool solve = live && n > 0;
+    if (solve) TG_FOR(i, m * ld) K[i] = 0.0;
+    TG_SYNC();
+    if (solve) TG_FOR(i, nd) {
+        double *row = K + i * ld;
+        row[i] = 1.0;
+        for (int f = 0; f < P.n_cf; f++) if (P.cf_cfg[f] == i) row[nd + P.cf_in[f]] += 1.0;
+        if (core.n_wrenches()) {
+            const int m0 = P.n_dh + core.n_sdh(), c0 = nc + core.n_springs();
+            for (int w_ = 0; w_ < core.n_wdh(); w_++) {
+                if (P.dh_cfg[m0 + w_] != i) continue;
+                const int w = P.dh_c[m0 + w_] - c0;
+                for (int s6 = 0; s6 < 6; s6++) { const int in = P.wr_in[6 * w + s6]; if (in >= 0) row[nd + in] += S[P.o_wD + 6 * w_ + s6]; }
+            }
+        }
+        for (int c = 0; c < nc; c++) { const int e = P.dh_lookup[c * nq + i]; if (e >= 0) row[nd + nu + c] = S[P.o_Dh2 + e]; }
+        row[m] = -rhs[i];
+    }
+    TG_SYNC();
+    if (solve) {
+        TG_FOR(e, n * nd) { const int j = e / nd, i = e % nd; K[(nd + j) * ld + i] = K[i * ld + nd + j]; }
+        TG_FOR(j, n) K[(nd + j) * ld + nd + j] = -J.ridge;
+    }
+    if (live && !solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = rhs[i];      // n == 0: rho = r0
+    TG_SYNC();
+
+    // ---- the solve -----------------------------------------------------------------------------------------------------------------
+    bool ok = true;
+    if (n > 0) ok = core.gauss_jordan(solve, K, m, 1, ld, scal);      // (n is the launch's: every team of the wavefront takes the same way)
+    if (solve && ok) for (int i = 0; i < m; i++) if (!(fabs(K[i * ld + m]) <= DBL_MAX)) ok = false;      // (every lane scans the same words: team-uniform)
+    const bool answer = solve && ok;
+    if (live) {
+        if (J.U) TG_FOR(i, nu) J.U[bs * nu + i] = answer ? K[(nd + i) * ld + m] : 0.0;
+        if (J.LAM) TG_FOR(c, nc) J.LAM[bs * nc + c] = answer ? K[(nd + nu + c) * ld + m] : 0.0;
+        if (solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = answer ? -K[i * ld + m] : 0.0;
+        if (lane == 0 && J.status) J.status[bs] = ok ? TG_OK : TG_SINGULAR;
+    }
+}
+
+}  // namespace tg

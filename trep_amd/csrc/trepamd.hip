@@ -22,6 +22,7 @@
 #include "mvi_inverse.hpp"
 #include "mvi_frames.hpp"
 #include "mvi_tape.hpp"
+#include "mvi_dyn_inverse.hpp"
 #include "schedule.hpp"
 #include <dlfcn.h>
 
@@ -38,6 +39,8 @@ int launch_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, 
 int launch_frames(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::FrameArgs &J, int grid, size_t lds, hipStream_t stream);
 // the tape-measure kernel (trepamd_tape.hip, likewise)
 int launch_tape(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::TapeArgs &J, int grid, size_t lds, hipStream_t stream);
+// the computed-torque kernel and its parameter-table twin (trepamd_dyn_inverse.hip, likewise)
+int launch_dyn_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -1521,6 +1524,104 @@ int tg_batch_tape_measures(tg_batch *b, int32_t n_states, const double *Q_host, 
     };
     back(L, l, n_l * sizeof(double)); back(V, v, n_v * sizeof(double)); back(LQ, lq, n_lq * sizeof(double));
     back(VQ, vq, n_vq * sizeof(double)); back(LQQ, lqq, n_lqq * sizeof(double));
+    if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
+    return rc;
+}
+
+// ---- batched computed torque (mvi_dyn_inverse.hpp): one team per state, one launch
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the computed-torque kernel for this system (out[0..2];
+ * out[3] 0): the rollout slice plus the image [m][m + 1], m = nd + nu + nc, the given accelerations [nq] and the solver's row scales
+ * [m] (mvi_dyn_inverse.hpp).  TG_ERR_UNSUPPORTED, with out filled, above the 160 KiB a workgroup can have, and in the profiling build. */
+int tg_system_dynamics_inverse_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::DynInverseArgs J{};
+    tg::dyn_inverse_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nd, sys->H.p.nu, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident computed-torque kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no computed-torque kernel");
+#endif
+    return rc;
+}
+
+// what both entry points refuse, decided on the host before a device is touched: first what the arguments alone show, then what
+// needs the system (the strides are nq for the host variant)
+static int dyn_inverse_check(const tg_batch *b, int32_t n_states, const double *Q, const double *dQ, const double *ddQ, uint64_t q_stride,
+                             uint64_t dq_stride, uint64_t ddq_stride, double ridge) {
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(TG_ERR_INVALID, "ridge must be finite and not negative");
+    if (n_states < 1) return fail(TG_ERR_INVALID, "n_states must be at least 1");
+    if (!Q) return fail(TG_ERR_INVALID, "null Q");
+    if (!dQ) return fail(TG_ERR_INVALID, "null dQ");
+    if (!ddQ) return fail(TG_ERR_INVALID, "null ddQ");
+    if (!b || !b->sys) return fail(TG_ERR_INVALID, "null argument");
+    const uint64_t nq = (uint64_t)b->sys->H.p.nq;
+    if (q_stride < nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
+    if (dq_stride < nq) return fail(TG_ERR_INVALID, "row stride of dQ shorter than a configuration");
+    if (ddq_stride < nq) return fail(TG_ERR_INVALID, "row stride of ddQ shorter than a configuration");
+    if (b->P.nu + b->P.nc > b->P.nd && ridge == 0.0)
+        return fail(TG_ERR_INVALID, "more unknowns (nu + nc) than dynamic configs: the least-squares image is singular without a ridge");
+    return TG_SUCCESS;
+}
+
+int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                                     uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
+                                     double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev, int32_t *status_dev) {
+    if (int rc = dyn_inverse_check(b, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride_doubles, dq_row_stride_doubles, ddq_row_stride_doubles, ridge)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
+    const long long teams = (long long)b->batch * n_states, per_block = 64 / b->sys->team;
+    if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many states for one launch");
+    HIP_TRY(hipSetDevice(b->device));
+    // the states are arguments of the call: nothing of the integrator (q1, q2, p, lambda1, status, times) is read or written, and a
+    // loaded specialised library has no say; a parameter table has (masses, gravity and damping move the residual)
+    tg::RunArgs A = base_args(b, tg::MODE_DYN_INVERSE);
+    A.q1 = A.q2 = A.p1 = A.p2 = A.lam = A.u1 = nullptr;
+    A.iters = A.status = nullptr;
+    A.n_steps = n_states;
+    tg::DynInverseArgs J{};
+    tg::dyn_inverse_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    J.Q = Q_dev; J.dQ = dQ_dev; J.ddQ = ddQ_dev;
+    J.U = U_dev; J.LAM = LAM_dev; J.RHO = RHO_dev; J.TAU = TAU_dev; J.ACC = ACC_dev; J.status = status_dev;
+    J.ridge = ridge; J.n_states = n_states;
+    J.q_stride = (size_t)q_row_stride_doubles; J.dq_stride = (size_t)dq_row_stride_doubles; J.ddq_stride = (size_t)ddq_row_stride_doubles;
+    const bool par = b->par_rows > 0;
+    LaunchTiming timed;
+    if (int rc = timing_begin(b, timed)) return rc;
+    int rc = tg_detail::launch_dyn_inverse(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+                                           tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0},
+                                           (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[par][0].add(tg::MODE_DYN_INVERSE);      // a refused launch (the profiling build) is not counted
+    return timing_end(b, timed, rc);
+}
+
+int tg_batch_dynamics_inverse(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
+                              double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *status) {
+    const uint64_t nq_ = b && b->sys ? (uint64_t)b->sys->H.p.nq : 0;
+    if (int rc = dyn_inverse_check(b, n_states, Q_host, dQ_host, ddQ_host, nq_, nq_, nq_, ridge)) return rc;
+    int32_t geo[4];
+    if (int rc = tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    // staging of this call alone (its size follows n_states): Q, dQ, ddQ in; the outputs asked for and the status words out
+    const size_t rows = (size_t)b->batch * n_states, nq = b->P.nq, nd = b->P.nd, nu = b->P.nu, nc = b->P.nc;
+    const size_t n_q = rows * nq, n_u = U ? rows * nu : 0, n_l = LAM ? rows * nc : 0, n_r = RHO ? rows * nd : 0, n_t = TAU ? rows * nd : 0;
+    const size_t n_a = ACC ? rows * nc : 0;
+    tg::DeviceBuffer<double> stage;
+    tg::DeviceBuffer<int> words;
+    HIP_TRY(stage.ensure(3 * n_q + n_u + n_l + n_r + n_t + n_a));
+    if (status) HIP_TRY(words.ensure(rows));
+    double *q = stage.get(), *dq = q + n_q, *ddq = dq + n_q, *u = ddq + n_q, *lam = u + n_u, *rho = lam + n_l, *tau = rho + n_r, *acc = tau + n_t;
+    HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dq, dQ_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(ddq, ddQ_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    int rc = tg_batch_dynamics_inverse_device(b, n_states, q, nq, dq, nq, ddq, nq, ridge, n_u ? u : nullptr, n_l ? lam : nullptr,
+                                              n_r ? rho : nullptr, n_t ? tau : nullptr, n_a ? acc : nullptr, status ? words.get() : nullptr);
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
+            rc = fail(TG_ERR_HIP, "copy of the results failed");
+    };
+    back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(RHO, rho, n_r * sizeof(double));
+    back(TAU, tau, n_t * sizeof(double)); back(ACC, acc, n_a * sizeof(double)); back(status, words.get(), rows * sizeof(int));
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
 }

@@ -25,6 +25,7 @@ Equilibrium = collections.namedtuple("Equilibrium", "Q mu V iterations status") 
 InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h status")     # BatchMidpointVI.inverse_dynamics
 FrameKinematics = collections.namedtuple("FrameKinematics", "g vb p_dq vb_ddq")         # BatchMidpointVI.frame_kinematics
 TapeMeasures = collections.namedtuple("TapeMeasures", "length velocity length_dq velocity_dq length_dqdq")      # BatchMidpointVI.tape_measures
+DynamicsInverse = collections.namedtuple("DynamicsInverse", "U lam rho tau acc status")     # BatchMidpointVI.dynamics_inverse
 
 
 class BatchMidpointVI(object):
@@ -494,6 +495,58 @@ class BatchMidpointVI(object):
         _lib.check(self._L.tg_batch_dynamics(self._h, _lib.ptr(Q), _lib.ptr(dQ), _lib.ptr(U), _lib.ptr(K),
                                              _lib.ptr(ddq), _lib.ptr(lam), status.ctypes.data))
         return ddq, lam, status
+
+    def dynamics_inverse(self, Q, dQ, ddQ, ridge=0.0):
+        """Computed torque, the inverse of dynamics() (include/trep_amd.h, tg_batch_dynamics_inverse): Q, dQ, ddQ [B][nq] or
+        [B][M][nq], kinematic configs included (the kinematic part of ddQ is what dynamics() calls ddQk).  Every state is one
+        least-squares solve for (u, lambda), all B x M of them in one launch.  Returns the namedtuple (U [B][M][nu], lam [B][M][nc],
+        rho [B][M][nd], tau [B][M][nd], acc [B][M][nc], status [B][M]): tau is the generalized force the motion needs from inputs and
+        constraints together, rho the part of it they cannot supply (zero for accelerations dynamics() returned), acc how far ddQ is
+        from consistent with the constraints.  status: TG_OK, or TG_SINGULAR where the solver rejected the state (U, lam, rho zero
+        there).  ridge >= 0 weighs |(u, lambda)|^2 against |rho|^2; it is required (ValueError) when nu + nc > nd, and a
+        rank-deficient system needs it too -- that is not detected.  For inputs [B][nq] the M axis is dropped.  With a parameter
+        table each trajectory uses its row; the time base has no say.  The integrator state of the batch is left alone."""
+        self.refresh()
+        B, nq = self._batch, self.nq
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        flat = Q.ndim == 2
+        if flat:
+            Q = Q[:, None, :]
+        if Q.ndim != 3 or Q.shape[0] != B or Q.shape[1] < 1 or Q.shape[2] != nq:
+            raise ValueError("expected Q of shape (%d, %d) or (%d, M, %d) with M >= 1, got %r" % (B, nq, B, nq, Q.shape))
+        M = Q.shape[1]
+
+        def like_q(a, name):
+            if a is None:
+                raise ValueError("%s is required" % name)
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            return _lib.as_f64(a[:, None, :] if flat and a.ndim == 2 else a, (B, M, nq))
+        dQ, ddQ = like_q(dQ, "dQ"), like_q(ddQ, "ddQ")
+        U, lam, rho = np.zeros((B, M, self.nu)), np.zeros((B, M, self.nc)), np.zeros((B, M, self.nd))
+        tau, acc, status = np.zeros((B, M, self.nd)), np.zeros((B, M, self.nc)), np.zeros((B, M), dtype=np.int32)
+        rc = self._L.tg_batch_dynamics_inverse(self._h, M, Q.ctypes.data, dQ.ctypes.data, ddQ.ctypes.data, float(ridge), _lib.ptr(U),
+                                               _lib.ptr(lam), _lib.ptr(rho), _lib.ptr(tau), _lib.ptr(acc), status.ctypes.data)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        drop = (lambda a: a[:, 0]) if flat else (lambda a: a)
+        return DynamicsInverse(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status))
+
+    def dynamics_inverse_device(self, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride=None, dq_row_stride=None, ddq_row_stride=None,
+                                ridge=0.0, U_dev=None, lam_dev=None, rho_dev=None, tau_dev=None, acc_dev=None, status_dev=None):
+        """dynamics_inverse on device pointers, asynchronous on the batch's stream (tg_batch_dynamics_inverse_device).  Row (b, m) is
+        read at Q_dev + (b n_states + m) q_row_stride doubles (dQ_dev and ddQ_dev likewise with their own strides): the default nq
+        for packed arrays, nX to read the configurations straight from a rollout's X [B][n_states][nX].  The outputs are laid out as
+        dynamics_inverse returns them ([B][n_states]...); any may be None."""
+        self.refresh()
+        nq = self.nq
+        rc = self._L.tg_batch_dynamics_inverse_device(self._h, int(n_states), Q_dev, int(nq if q_row_stride is None else q_row_stride),
+                                                      dQ_dev, int(nq if dq_row_stride is None else dq_row_stride), ddQ_dev,
+                                                      int(nq if ddq_row_stride is None else ddq_row_stride), float(ridge), U_dev, lam_dev,
+                                                      rho_dev, tau_dev, acc_dev, status_dev)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
 
     def free_mask(self, keep_kinematic=False, constant_q_list=None):
         """int32 [nq], 1 = free: the configs System.satisfy_constraints would move (reference trep/system.py:176-186) -- everything
