@@ -516,6 +516,28 @@ int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, co
                                      const double *p0_dev, double ridge, double *U_dev, double *LAM_dev, double *P_dev,
                                      double *RHO_dev, double *H_dev, int32_t *status_dev);
 
+/* The same question answered by rank-revealing least squares (csrc/lsq_solve.hpp; tests/min_norm_reference.py is the
+ * specification): column-pivoted Householder QR of the stacked block W = [A~; sqrt(ridge) I] (W = A~ at ridge == 0) with a
+ * minimum-norm completion, in place of the augmented image.  z~ = (dt_k u, lambda) is argmin |r0 + A~ z~|^2 + ridge |z~|^2 and, where
+ * A~ loses rank, the minimiser of least |z~| -- numpy.linalg.lstsq(W, c, rcond)'s answer --, so it does not depend on a ridge, and
+ * n > nd is accepted at ridge == 0.  rcond after ridge: a pivot column norm <= rcond * the first pivot's ends the factorisation;
+ * rank [B][N] before status (nullable): the number of pivots accepted, 0 for a step that is not solved (n == 0, step 0 without p0) or
+ * whose status is TG_SINGULAR.  With ridge > 0 the rank test runs on the STACKED block, whose singular values are
+ * sqrt(sigma^2 + ridge): it then reports n unless rcond^2 sigma_1^2 exceeds the ridge.  TG_SINGULAR only for an answer that is not
+ * finite -- z~, rho, or an A~ or r0 with an entry that is not finite (a configuration that is not a number) -- with U, LAM, RHO zero
+ * and rank 0; a zero A~ is rank 0 with z~ = 0 and TG_OK.  rho = r0 + A~ z~ is formed from r0 and A~ themselves.  Column norms are
+ * plain sums of squares: entries of A~ of scale 1e-160 and below count as zero, 1e154 and above overflow into TG_SINGULAR.
+ * Everything else -- outputs, strides, the parameter twin, mode 11 in tg_batch_info -- is the sibling's.  TG_ERR_INVALID, before
+ * a device is touched, for rcond negative, >= 1 or not finite and for everything the sibling refuses EXCEPT n > nd with
+ * ridge == 0; the LDS refusal is tg_system_inverse_dynamics_lsq_lds's: per team the rollout slice plus (nd + n)(n + 1) + nd + 4 n
+ * doubles, never more than 4 n above the sibling's. */
+int tg_system_inverse_dynamics_lsq_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_inverse_dynamics_lsq(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge,
+                                  double rcond, double *U, double *LAM, double *P, double *RHO, double *H, int32_t *rank, int32_t *status);
+int tg_batch_inverse_dynamics_lsq_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                         const double *p0_dev, double ridge, double rcond, double *U_dev, double *LAM_dev, double *P_dev,
+                                         double *RHO_dev, double *H_dev, int32_t *rank_dev, int32_t *status_dev);
+
 /* ---- batched frame kinematics ------------------------------------------------------------------------------------------
  * Where the frames are: for configurations Q [B][n_states][nq] (B = the batch size; kinematic configs included) and rates dQ of the
  * same shape, the world pose, the body velocity and the two Jacobians of every selected frame of every state, one team per state,
@@ -626,6 +648,29 @@ int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double
                                      const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
                                      double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev,
                                      int32_t *status_dev);
+
+/* Computed torque by rank-revealing least squares: as tg_batch_inverse_dynamics_lsq is to tg_batch_inverse_dynamics.  z = (u, lambda)
+ * is numpy.linalg.lstsq(W, c, rcond)'s answer on W = [A; sqrt(ridge) I], c = (-r0; 0) -- of minimum norm where A loses rank, whatever
+ * the ridge --, n > nd is accepted at ridge == 0, rcond follows ridge and rank [B][n_states] (nullable) precedes status; with
+ * ridge > 0 the rank test runs on the stacked block.  n == 0: rank = 0, rho = r0, nothing is solved.  TG_SINGULAR only for an answer
+ * that is not finite (z, rho, or a state that is not a number: U, LAM, RHO zero and rank 0, as the sibling answers); the range of
+ * the column norms is tg_batch_inverse_dynamics_lsq's.  TG_ERR_INVALID, before a device is touched, for rcond negative, >= 1 or not finite and for everything the
+ * sibling refuses except n > nd with ridge == 0; the LDS refusal is tg_system_dynamics_inverse_lsq_lds's: per team the rollout slice
+ * plus (nd + n)(n + 1) + nq + 4 n doubles.
+ * tg_batch_debug_lsq_solve (test hook) runs the solver alone on `count` caller-supplied problems of one shape, A [count][rows][cols]
+ * and c [count][rows] on the host, one team of `team` lanes (1, 4, 16 or 64) on each, in one launch: z [count][cols] = argmin
+ * |c - A z| of minimum norm, rank and status [count].  Only here do teams of different rank share a wavefront. */
+int tg_system_dynamics_inverse_lsq_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_dynamics_inverse_lsq(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host,
+                                  double ridge, double rcond, double *U, double *LAM, double *RHO, double *TAU, double *ACC,
+                                  int32_t *rank, int32_t *status);
+int tg_batch_dynamics_inverse_lsq_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                         const double *dQ_dev, uint64_t dq_row_stride_doubles,
+                                         const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge, double rcond,
+                                         double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev,
+                                         int32_t *rank_dev, int32_t *status_dev);
+int tg_batch_debug_lsq_solve(tg_batch *b, int32_t team, int32_t count, int32_t rows, int32_t cols, const double *A_host,
+                             const double *c_host, double rcond, double *z_host, int32_t *rank_host, int32_t *status_host);
 
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,

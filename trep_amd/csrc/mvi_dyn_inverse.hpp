@@ -19,7 +19,12 @@
 // Outputs: U, LAM, RHO, TAU, ACC, status TG_OK or TG_SINGULAR (the solver rejected the image or its answer is not finite: U, LAM, RHO of
 // that state are zero, TAU and ACC still written).  With n == 0 nothing is solved: rho = r0.
 // A rank-deficient A with n <= nd and ridge == 0 is NOT detected unless a scaled pivot falls to 1e-20 (gauss_jordan's guard): such
-// systems need ridge > 0.
+// systems need ridge > 0 -- or the LSQ instantiation (tg_batch_dynamics_inverse_lsq): the same evaluation, and in place of the image
+// the stacked block [A; sqrt(ridge) I] with (-r0; 0) through the rank-revealing least squares of lsq_solve.hpp (inverse_lsq_stage in
+// mvi_inverse_rows.hpp).  z is then the minimum-norm minimiser whatever the ridge, n > nd needs none, the rank of every state is
+// returned (J.rank), rho = r0 + A z is formed from r0 and rows of A assembled a second time, and TG_SINGULAR means only an answer that
+// is not finite.  LDS of a team there: the block [nd + n][n + 1] in place of the image and 4 n doubles in place of the row scales
+// (dyn_inverse_lsq_layout).
 //
 // No team reads what another writes and every sum runs in an order the team's own lanes fix (LDS only, no global atomics): a state's
 // result does not depend on B, M or the team's neighbours in the wavefront.
@@ -29,7 +34,7 @@
 #pragma once
 #include <cfloat>
 
-#include "mvi_core.hpp"
+#include "mvi_inverse_rows.hpp"
 
 namespace tg {
 
@@ -45,6 +50,8 @@ struct DynInverseArgs {
     int n_states;
     int o_kkt, o_ddq, o_scal;    // LDS offsets (doubles) behind the rollout slice
     int lds_per_team;            // doubles per team: what the kernel strides its teams by
+    double rcond;                // the LSQ kernels alone: pivot norms <= rcond * the first one end the factorisation
+    int *rank;                   // the LSQ kernels alone: [batch][n_states] or null
 };
 
 // the scratch layout of one team (host; the same numbers for the device launch and the emulation)
@@ -57,8 +64,20 @@ inline void dyn_inverse_layout(int rollout_lds_per_team, int nq, int nd, int nu,
     J.lds_per_team = (off + 1) & ~1;
 }
 
+// ... and of the LSQ kernels: o_kkt the stacked block [nd + n][n + 1] (sized for a ridge), o_scal the solver's 4 n doubles (lsq_solve.hpp).
+// Against the layout above that is m (n + 1) + 4 n for m (m + 1) + m, m = nd + n: never more than 4 n doubles larger.
+inline void dyn_inverse_lsq_layout(int rollout_lds_per_team, int nq, int nd, int nu, int nc, DynInverseArgs &J) {
+    const int n = nu + nc;
+    int off = (rollout_lds_per_team + 1) & ~1;
+    J.o_kkt = off; off += (nd + n) * (n + 1);
+    J.o_ddq = off; off += nq;
+    J.o_scal = off; off += lsq_scratch_doubles(n);
+    J.lds_per_team = (off + 1) & ~1;
+}
+
 // team index i = b * n_states + s; i >= batch * n_states: an idle team, which still takes part in every TG_SYNC
-template <int TEAM, bool SPRINGS, bool PAR, class PROG, class ARGS>
+// LSQ: the solve is lsq_solve.hpp's on [A; sqrt(ridge) I] (inverse_lsq_stage) in place of the augmented image, and J.rank is written
+template <int TEAM, bool SPRINGS, bool PAR, bool LSQ = false, class PROG, class ARGS>
 TG_HD void run_dyn_inverse(PROG &P, ARGS &A, const DynInverseArgs &J, const ParTable T, double *S, int lane, long long team_index) {
     const int nq = P.nq, nd = P.nd, nu = P.nu, nc = P.nc, nf = P.nf, M = J.n_states;
     const int n = nu + nc, m = nd + n, ld = m + 1;
@@ -141,23 +160,32 @@ TG_HD void run_dyn_inverse(PROG &P, ARGS &A, const DynInverseArgs &J, const ParT
         if (J.ACC) TG_FOR(c, nc) J.ACC[bs * nc + c] = rhs[nd + c];
     }
 
-    // ---- the image [[I, A], [A', -ridge I]] with the right-hand side (-r0, 0): every lane owns rows of [I, A], then the transpose ----
     const bool solve = live && n > 0;
+    if (live && !solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = rhs[i];      // n == 0: rho = r0
+    if constexpr (LSQ) {
+        // ---- the stacked block [A; sqrt(ridge) I] with (-r0; 0), its rank-revealing solve, rho from r0 and A ----------------------------
+        bool ok = true;
+        int r = 0;
+        if (n > 0) r = inverse_lsq_stage<TEAM>(core, P, S, lane, solve, rhs, S + P.o_Dh2, false, J.ridge, J.rcond, K, scal, ok);
+        const bool answer = solve && ok;
+        const double *z = scal + 2 * n;
+        if (live) {
+            if (J.U) TG_FOR(i, nu) J.U[bs * nu + i] = answer ? z[i] : 0.0;
+            if (J.LAM) TG_FOR(c, nc) J.LAM[bs * nc + c] = answer ? z[nu + c] : 0.0;
+            if (solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = answer ? K[i * (n + 1) + n] : 0.0;
+            if (lane == 0 && J.rank) J.rank[bs] = answer ? r : 0;
+            if (lane == 0 && J.status) J.status[bs] = ok ? TG_OK : TG_SINGULAR;
+        }
+        return;
+    }
+
+    // ---- the image [[I, A], [A', -ridge I]] with the right-hand side (-r0, 0): every lane owns rows of [I, A], then the transpose ----
     if (solve) TG_FOR(i, m * ld) K[i] = 0.0;
     TG_SYNC();
     if (solve) TG_FOR(i, nd) {
         double *row = K + i * ld;
         row[i] = 1.0;
-        for (int f = 0; f < P.n_cf; f++) if (P.cf_cfg[f] == i) row[nd + P.cf_in[f]] += 1.0;
-        if (core.n_wrenches()) {
-            const int m0 = P.n_dh + core.n_sdh(), c0 = nc + core.n_springs();
-            for (int w_ = 0; w_ < core.n_wdh(); w_++) {
-                if (P.dh_cfg[m0 + w_] != i) continue;
-                const int w = P.dh_c[m0 + w_] - c0;
-                for (int s6 = 0; s6 < 6; s6++) { const int in = P.wr_in[6 * w + s6]; if (in >= 0) row[nd + in] += S[P.o_wD + 6 * w_ + s6]; }
-            }
-        }
-        for (int c = 0; c < nc; c++) { const int e = P.dh_lookup[c * nq + i]; if (e >= 0) row[nd + nu + c] = S[P.o_Dh2 + e]; }
+        inverse_row(core, P, S, i, row + nd, S + P.o_Dh2, false);
         row[m] = -rhs[i];
     }
     TG_SYNC();
@@ -165,7 +193,6 @@ TG_HD void run_dyn_inverse(PROG &P, ARGS &A, const DynInverseArgs &J, const ParT
         TG_FOR(e, n * nd) { const int j = e / nd, i = e % nd; K[(nd + j) * ld + i] = K[i * ld + nd + j]; }
         TG_FOR(j, n) K[(nd + j) * ld + nd + j] = -J.ridge;
     }
-    if (live && !solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = rhs[i];      // n == 0: rho = r0
     TG_SYNC();
 
     // ---- the solve -----------------------------------------------------------------------------------------------------------------

@@ -22,7 +22,13 @@
 // step 0 are zero, so that initialize_from_state(t_0, Q_0, P_0) followed by a rollout with U retraces Q.  With n == 0 nothing is
 // solved either: rho = r0.
 // A rank-deficient A~ with n <= nd and ridge == 0 is NOT detected unless a scaled pivot falls to 1e-20 (gauss_jordan's guard): such
-// systems need ridge > 0.
+// systems need ridge > 0 -- or the LSQ instantiation (tg_batch_inverse_dynamics_lsq): the same evaluation, and in place of the image
+// the stacked block [A~; sqrt(ridge) I] with (-r0; 0) through the rank-revealing least squares of lsq_solve.hpp (inverse_lsq_stage in
+// mvi_inverse_rows.hpp), the unknowns still the impulses z~ = (dt_k u, lambda) and the multiplier columns still -Dh'.  z~ is then the
+// minimum-norm minimiser whatever the ridge, n > nd needs none, the rank of every step is returned (J.rank; 0 for a step that is not
+// solved), rho = r0 + A~ z~ is formed from r0 and rows of A~ assembled a second time -- the solve therefore runs before h(Q_{k+1}) is
+// evaluated --, and TG_SINGULAR means only an answer that is not finite.  LDS of a team there: the block [nd + n][n + 1] in place of
+// the image and 4 n doubles in place of the row scales (inverse_lsq_layout).
 //
 // No team reads what another writes: a (b, k) result does not depend on B, N or the team's neighbours in the wavefront.
 // LDS of a team: the rollout slice and behind it the image [m][m + 1], m = nd + n, p_k [nd] and the solver's row scales [m].
@@ -30,7 +36,7 @@
 #pragma once
 #include <cfloat>
 
-#include "mvi_core.hpp"
+#include "mvi_inverse_rows.hpp"
 
 namespace tg {
 
@@ -48,6 +54,8 @@ struct InverseArgs {
     int n_steps;
     int o_kkt, o_pk, o_scal;     // LDS offsets (doubles) behind the rollout slice
     int lds_per_team;            // doubles per team: what the kernel strides its teams by
+    double rcond;                // the LSQ kernels alone: pivot norms <= rcond * the first one end the factorisation
+    int *rank;                   // the LSQ kernels alone: [batch][n_steps] or null
 };
 
 // the scratch layout of one team (host; the same numbers for the device launch and the emulation)
@@ -60,8 +68,21 @@ inline void inverse_layout(int rollout_lds_per_team, int nd, int nu, int nc, Inv
     J.lds_per_team = (off + 1) & ~1;
 }
 
+// ... and of the LSQ kernels: o_kkt the stacked block [nd + n][n + 1] (sized for a ridge), o_scal the solver's 4 n doubles (lsq_solve.hpp).
+// Against the layout above that is m (n + 1) + 4 n for m (m + 1) + m, m = nd + n: never more than 4 n doubles larger.
+inline void inverse_lsq_layout(int rollout_lds_per_team, int nd, int nu, int nc, InverseArgs &J) {
+    const int n = nu + nc;
+    int off = (rollout_lds_per_team + 1) & ~1;
+    J.o_kkt = off; off += (nd + n) * (n + 1);
+    J.o_pk = off; off += nd;
+    J.o_scal = off; off += lsq_scratch_doubles(n);
+    J.lds_per_team = (off + 1) & ~1;
+}
+
 // team index i = b * n_steps + k; i >= batch * n_steps: an idle team, which still takes part in every TG_SYNC
-template <int TEAM, bool SPRINGS, bool PAR, class PROG, class ARGS>
+// LSQ: the solve is lsq_solve.hpp's on [A~; sqrt(ridge) I] (inverse_lsq_stage) in place of the augmented image, run BEFORE the
+// constraints of Q_{k+1} are evaluated (r0, o_wD and Dh(Q_k) are then still in place for rho), and J.rank is written
+template <int TEAM, bool SPRINGS, bool PAR, bool LSQ = false, class PROG, class ARGS>
 TG_HD void run_inverse(PROG &P, ARGS &A, const InverseArgs &J, const ParTable T, double *S, int lane, long long team_index) {
     const int nq = P.nq, nd = P.nd, nu = P.nu, nc = P.nc, N = J.n_steps;
     const int n = nu + nc, m = nd + n, ld = m + 1;
@@ -103,22 +124,45 @@ TG_HD void run_inverse(PROG &P, ARGS &A, const InverseArgs &J, const ParTable T,
     core.eval_constraints(live, 1, false, S + P.o_Dh1);
     core.eval_midpoint(live);
     const bool solve = live && n > 0 && (k > 0 || J.p0);
+    // what both solves share behind the evaluation of the pair: P_{k+1} (and P_0), rho = r0 where nothing is solved, then h(Q_{k+1}),
+    // which overwrites the poses and Dh2 -- the LSQ stage runs before it, the augmented image is assembled before it
+    auto momenta_and_h = [&]() {
+        if (live) {
+            if (J.P) {
+                double *Pb = J.P + b * (size_t)(N + 1) * nd;
+                TG_FOR(i, nd) Pb[(size_t)(k + 1) * nd + i] = 0.5 * dt_k * S[P.o_Ldq + i] + S[P.o_Lddq + i];
+                if (k == 0) TG_FOR(i, nd) Pb[i] = J.p0 ? pk[i] : -S[P.o_f + i];
+            }
+            if (!solve && J.RHO) TG_FOR(i, nd) J.RHO[bk * nd + i] = (k > 0 || J.p0) ? S[P.o_f + i] : 0.0;     // n == 0: rho = r0
+        }
+        TG_SYNC();
+        core.eval_constraints(live, 2, true, S + P.o_Dh2);
+        if (live && J.H) TG_FOR(c, nc) J.H[bk * nc + c] = S[P.o_f + nd + c];
+    };
+    if constexpr (LSQ) {
+        // the stacked block [A~; sqrt(ridge) I] with (-r0; 0), its rank-revealing solve, rho from r0 and A~
+        bool ok = true;
+        int r = 0;
+        if (n > 0) r = inverse_lsq_stage<TEAM>(core, P, S, lane, solve, S + P.o_f, S + P.o_Dh1, true, J.ridge, J.rcond, K, scal, ok);
+        const bool answer = solve && ok;
+        const double *z = scal + 2 * n;
+        if (live) {
+            if (J.U) TG_FOR(i, nu) J.U[bk * nu + i] = answer ? z[i] / dt_k : 0.0;
+            if (J.LAM) TG_FOR(c, nc) J.LAM[bk * nc + c] = answer ? z[nu + c] : 0.0;
+            if (solve && J.RHO) TG_FOR(i, nd) J.RHO[bk * nd + i] = answer ? K[i * (n + 1) + n] : 0.0;
+            if (lane == 0 && J.rank) J.rank[bk] = answer ? r : 0;
+            if (lane == 0 && J.status) J.status[bk] = ok ? TG_OK : TG_SINGULAR;
+        }
+        momenta_and_h();
+        return;
+    }
     // the image [[I, A~], [A~', -ridge I]] with the right-hand side (-r0, 0): every lane owns rows of [I, A~], then the transpose
     if (solve) TG_FOR(i, m * ld) K[i] = 0.0;
     TG_SYNC();
     if (solve) TG_FOR(i, nd) {
         double *row = K + i * ld;
         row[i] = 1.0;
-        for (int f = 0; f < P.n_cf; f++) if (P.cf_cfg[f] == i) row[nd + P.cf_in[f]] += 1.0;
-        if (core.n_wrenches()) {
-            const int m0 = P.n_dh + core.n_sdh(), c0 = nc + core.n_springs();
-            for (int w_ = 0; w_ < core.n_wdh(); w_++) {
-                if (P.dh_cfg[m0 + w_] != i) continue;
-                const int w = P.dh_c[m0 + w_] - c0;
-                for (int s6 = 0; s6 < 6; s6++) { const int in = P.wr_in[6 * w + s6]; if (in >= 0) row[nd + in] += S[P.o_wD + 6 * w_ + s6]; }
-            }
-        }
-        for (int c = 0; c < nc; c++) { const int e = P.dh_lookup[c * nq + i]; if (e >= 0) row[nd + nu + c] = -S[P.o_Dh1 + e]; }
+        inverse_row(core, P, S, i, row + nd, S + P.o_Dh1, true);
         row[m] = -S[P.o_f + i];
     }
     TG_SYNC();
@@ -126,17 +170,7 @@ TG_HD void run_inverse(PROG &P, ARGS &A, const InverseArgs &J, const ParTable T,
         TG_FOR(e, n * nd) { const int j = e / nd, i = e % nd; K[(nd + j) * ld + i] = K[i * ld + nd + j]; }
         TG_FOR(j, n) K[(nd + j) * ld + nd + j] = -J.ridge;
     }
-    if (live) {
-        if (J.P) {
-            double *Pb = J.P + b * (size_t)(N + 1) * nd;
-            TG_FOR(i, nd) Pb[(size_t)(k + 1) * nd + i] = 0.5 * dt_k * S[P.o_Ldq + i] + S[P.o_Lddq + i];
-            if (k == 0) TG_FOR(i, nd) Pb[i] = J.p0 ? pk[i] : -S[P.o_f + i];
-        }
-        if (!solve && J.RHO) TG_FOR(i, nd) J.RHO[bk * nd + i] = (k > 0 || J.p0) ? S[P.o_f + i] : 0.0;     // n == 0: rho = r0
-    }
-    TG_SYNC();
-    core.eval_constraints(live, 2, true, S + P.o_Dh2);
-    if (live && J.H) TG_FOR(c, nc) J.H[bk * nc + c] = S[P.o_f + nd + c];
+    momenta_and_h();
 
     // ---- the solve ------------------------------------------------------------------------------------------------------------
     bool ok = true;

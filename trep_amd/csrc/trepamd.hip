@@ -34,13 +34,15 @@ int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::
 // the equilibrium-search kernel and its parameter-table twin (trepamd_equilibrium.hip, likewise)
 int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the inverse-dynamics kernel and its parameter-table twin (trepamd_inverse.hip, likewise)
-int launch_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+int launch_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the frame-kinematics kernel (trepamd_frames.hip, likewise)
 int launch_frames(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::FrameArgs &J, int grid, size_t lds, hipStream_t stream);
 // the tape-measure kernel (trepamd_tape.hip, likewise)
 int launch_tape(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::TapeArgs &J, int grid, size_t lds, hipStream_t stream);
 // the computed-torque kernel and its parameter-table twin (trepamd_dyn_inverse.hip, likewise)
-int launch_dyn_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+int launch_dyn_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+int launch_lsq_debug(int team, int per_block, int count, int rows, int cols, int per_team, const double *A, const double *c, double rcond, double *z,
+                     int *rank, int *status, size_t lds, hipStream_t stream);
 }
 
 namespace {
@@ -1227,26 +1229,47 @@ int tg_system_inverse_dynamics_lds(const tg_system *sys, int32_t out[4]) {
     return rc;
 }
 
-// what both entry points refuse, decided on the host before anything is staged or launched
-static int inverse_check(const tg_batch *b, int32_t n_steps, double dt, const double *Q, double ridge) {
+/* The same for the kernel whose solve is the rank-revealing least squares (tg_batch_inverse_dynamics_lsq): the stacked block
+ * [nd + n][n + 1], n = nu + nc, in place of the image and the solver's 4 n doubles in place of the row scales (inverse_lsq_layout). */
+int tg_system_inverse_dynamics_lsq_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::InverseArgs J{};
+    tg::inverse_lsq_layout(sys->H.p.lds_per_team, sys->H.p.nd, sys->H.p.nu, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident inverse-dynamics kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no inverse-dynamics kernel");
+#endif
+    return rc;
+}
+
+// what the least-squares entry points refuse on top of their siblings' refusals
+static int rcond_check(double rcond) {
+    if (!(rcond >= 0.0) || !(rcond < 1.0)) return fail(TG_ERR_INVALID, "rcond must be finite, not negative and below 1");
+    return TG_SUCCESS;
+}
+
+// what both entry points refuse, decided on the host before anything is staged or launched (lsq: n > nd needs no ridge)
+static int inverse_check(const tg_batch *b, int32_t n_steps, double dt, const double *Q, double ridge, bool lsq = false) {
     if (!b || !Q) return fail(TG_ERR_INVALID, "null argument");
     if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(TG_ERR_INVALID, "ridge must be finite and not negative");
     if (n_steps < 1) return fail(TG_ERR_INVALID, "n_steps must be at least 1");
     if (b->dt_by_trajectory) return fail(TG_ERR_INVALID, "a by-trajectory step-size list takes one-step launches only");
     if (!b->dt_host.empty() && (size_t)n_steps > b->dt_host.size()) return fail(TG_ERR_INVALID, "path longer than the step-size list");
     if (b->dt_host.empty() && (dt == 0.0 || !std::isfinite(dt))) return fail(TG_ERR_INVALID, "step size must be finite and not zero");
-    if (b->P.nu + b->P.nc > b->P.nd && ridge == 0.0)
+    if (!lsq && b->P.nu + b->P.nc > b->P.nd && ridge == 0.0)
         return fail(TG_ERR_INVALID, "more unknowns (nu + nc) than dynamic configs: the least-squares image is singular without a ridge");
     return TG_SUCCESS;
 }
 
-int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
-                                     const double *p0_dev, double ridge, double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev,
-                                     double *H_dev, int32_t *status_dev) {
-    if (int rc = inverse_check(b, n_steps, dt, Q_dev, ridge)) return rc;
+// both device entry points: lsq selects the least-squares kernel, its layout, rcond and the rank words
+static int inverse_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles, const double *p0_dev,
+                          double ridge, bool lsq, double rcond, double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev, double *H_dev,
+                          int32_t *rank_dev, int32_t *status_dev) {
+    if (lsq) if (int rc = rcond_check(rcond)) return rc;
+    if (int rc = inverse_check(b, n_steps, dt, Q_dev, ridge, lsq)) return rc;
     if (q_row_stride_doubles < (uint64_t)b->P.nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
     int32_t geo[4];
-    if (int rc = tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
+    if (int rc = lsq ? tg_system_inverse_dynamics_lsq_lds(b->sys, geo) : tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
     const long long teams = (long long)b->batch * n_steps, per_block = 64 / b->sys->team;
     if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many steps for one launch");
     HIP_TRY(hipSetDevice(b->device));
@@ -1257,12 +1280,14 @@ int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, co
     A.iters = A.status = nullptr;
     A.n_steps = n_steps; A.dt = dt;
     tg::InverseArgs J{};
-    tg::inverse_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    if (lsq) tg::inverse_lsq_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    else tg::inverse_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    J.rcond = rcond; J.rank = rank_dev;
     J.Q = Q_dev; J.p0 = p0_dev; J.dt_steps = b->dt_host.empty() ? nullptr : b->dt_dev.get();
     J.U = U_dev; J.LAM = LAM_dev; J.P = P_dev; J.RHO = RHO_dev; J.H = H_dev; J.status = status_dev;
     J.dt = dt; J.ridge = ridge; J.q_stride = (size_t)q_row_stride_doubles; J.n_steps = n_steps;
     const bool par = b->par_rows > 0;
-    int rc = tg_detail::launch_inverse(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+    int rc = tg_detail::launch_inverse(b->sys->team, launch_springs(b), par, lsq, b->d_prog.get(), A, J,
                                        tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0},
                                        (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
@@ -1270,11 +1295,25 @@ int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, co
     return rc;
 }
 
-int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge,
-                              double *U, double *LAM, double *P, double *RHO, double *H, int32_t *status) {
-    if (int rc = inverse_check(b, n_steps, dt, Q_host, ridge)) return rc;
+int tg_batch_inverse_dynamics_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                     const double *p0_dev, double ridge, double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev,
+                                     double *H_dev, int32_t *status_dev) {
+    return inverse_device(b, n_steps, dt, Q_dev, q_row_stride_doubles, p0_dev, ridge, false, 0.0, U_dev, LAM_dev, P_dev, RHO_dev, H_dev, nullptr, status_dev);
+}
+
+int tg_batch_inverse_dynamics_lsq_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                         const double *p0_dev, double ridge, double rcond, double *U_dev, double *LAM_dev, double *P_dev,
+                                         double *RHO_dev, double *H_dev, int32_t *rank_dev, int32_t *status_dev) {
+    return inverse_device(b, n_steps, dt, Q_dev, q_row_stride_doubles, p0_dev, ridge, true, rcond, U_dev, LAM_dev, P_dev, RHO_dev, H_dev, rank_dev, status_dev);
+}
+
+// both host entry points
+static int inverse_host(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge, bool lsq, double rcond,
+                        double *U, double *LAM, double *P, double *RHO, double *H, int32_t *rank, int32_t *status) {
+    if (lsq) if (int rc = rcond_check(rcond)) return rc;
+    if (int rc = inverse_check(b, n_steps, dt, Q_host, ridge, lsq)) return rc;
     int32_t geo[4];
-    if (int rc = tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
+    if (int rc = lsq ? tg_system_inverse_dynamics_lsq_lds(b->sys, geo) : tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
     HIP_TRY(hipSetDevice(b->device));
     // staging of this call alone (its size follows n_steps): Q, p0 in; U, LAM, P, RHO, H and the status words out
     const size_t B = (size_t)b->batch, N = (size_t)n_steps, nq = b->P.nq, nd = b->P.nd, nu = b->P.nu, nc = b->P.nc;
@@ -1282,19 +1321,30 @@ int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const dou
     tg::DeviceBuffer<double> stage;
     tg::DeviceBuffer<int> words;
     HIP_TRY(stage.ensure(n_q + n_p0 + n_u + n_l + n_p + n_r + n_l));
-    HIP_TRY(words.ensure(B * N));
+    HIP_TRY(words.ensure(2 * B * N));      // (status, then rank)
     double *q = stage.get(), *p0 = q + n_q, *u = p0 + n_p0, *lam = u + n_u, *p = lam + n_l, *rho = p + n_p, *h = rho + n_r;
     HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     if (p0_host && n_p0) HIP_TRY(hipMemcpyAsync(p0, p0_host, n_p0 * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    int rc = tg_batch_inverse_dynamics_device(b, n_steps, dt, q, nq, p0_host ? p0 : nullptr, ridge, u, lam, p, rho, h, words.get());
+    int rc = inverse_device(b, n_steps, dt, q, nq, p0_host ? p0 : nullptr, ridge, lsq, rcond, u, lam, p, rho, h, lsq ? words.get() + B * N : nullptr, words.get());
     auto back = [&](void *dst, const void *src, size_t bytes) {
         if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
             rc = fail(TG_ERR_HIP, "copy of the results failed");
     };
     back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(P, p, n_p * sizeof(double));
     back(RHO, rho, n_r * sizeof(double)); back(H, h, n_l * sizeof(double)); back(status, words.get(), B * N * sizeof(int));
+    if (lsq) back(rank, words.get() + B * N, B * N * sizeof(int));
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
+}
+
+int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge,
+                              double *U, double *LAM, double *P, double *RHO, double *H, int32_t *status) {
+    return inverse_host(b, n_steps, dt, Q_host, p0_host, ridge, false, 0.0, U, LAM, P, RHO, H, nullptr, status);
+}
+
+int tg_batch_inverse_dynamics_lsq(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge, double rcond,
+                                  double *U, double *LAM, double *P, double *RHO, double *H, int32_t *rank, int32_t *status) {
+    return inverse_host(b, n_steps, dt, Q_host, p0_host, ridge, true, rcond, U, LAM, P, RHO, H, rank, status);
 }
 
 // ---- batched frame kinematics (mvi_frames.hpp): one team per state, one launch
@@ -1544,10 +1594,23 @@ int tg_system_dynamics_inverse_lds(const tg_system *sys, int32_t out[4]) {
     return rc;
 }
 
+/* The same for the kernel whose solve is the rank-revealing least squares (tg_batch_dynamics_inverse_lsq): the stacked block
+ * [nd + n][n + 1], n = nu + nc, in place of the image and the solver's 4 n doubles in place of the row scales (dyn_inverse_lsq_layout). */
+int tg_system_dynamics_inverse_lsq_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::DynInverseArgs J{};
+    tg::dyn_inverse_lsq_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nd, sys->H.p.nu, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident computed-torque kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no computed-torque kernel");
+#endif
+    return rc;
+}
+
 // what both entry points refuse, decided on the host before a device is touched: first what the arguments alone show, then what
-// needs the system (the strides are nq for the host variant)
+// needs the system (the strides are nq for the host variant; lsq: n > nd needs no ridge)
 static int dyn_inverse_check(const tg_batch *b, int32_t n_states, const double *Q, const double *dQ, const double *ddQ, uint64_t q_stride,
-                             uint64_t dq_stride, uint64_t ddq_stride, double ridge) {
+                             uint64_t dq_stride, uint64_t ddq_stride, double ridge, bool lsq = false) {
     if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(TG_ERR_INVALID, "ridge must be finite and not negative");
     if (n_states < 1) return fail(TG_ERR_INVALID, "n_states must be at least 1");
     if (!Q) return fail(TG_ERR_INVALID, "null Q");
@@ -1558,17 +1621,20 @@ static int dyn_inverse_check(const tg_batch *b, int32_t n_states, const double *
     if (q_stride < nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
     if (dq_stride < nq) return fail(TG_ERR_INVALID, "row stride of dQ shorter than a configuration");
     if (ddq_stride < nq) return fail(TG_ERR_INVALID, "row stride of ddQ shorter than a configuration");
-    if (b->P.nu + b->P.nc > b->P.nd && ridge == 0.0)
+    if (!lsq && b->P.nu + b->P.nc > b->P.nd && ridge == 0.0)
         return fail(TG_ERR_INVALID, "more unknowns (nu + nc) than dynamic configs: the least-squares image is singular without a ridge");
     return TG_SUCCESS;
 }
 
-int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
-                                     uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
-                                     double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev, int32_t *status_dev) {
-    if (int rc = dyn_inverse_check(b, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride_doubles, dq_row_stride_doubles, ddq_row_stride_doubles, ridge)) return rc;
+// both device entry points: lsq selects the least-squares kernel, its layout, rcond and the rank words
+static int dyn_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                              uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge, bool lsq,
+                              double rcond, double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev, int32_t *rank_dev,
+                              int32_t *status_dev) {
+    if (lsq) if (int rc = rcond_check(rcond)) return rc;
+    if (int rc = dyn_inverse_check(b, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride_doubles, dq_row_stride_doubles, ddq_row_stride_doubles, ridge, lsq)) return rc;
     int32_t geo[4];
-    if (int rc = tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
+    if (int rc = lsq ? tg_system_dynamics_inverse_lsq_lds(b->sys, geo) : tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
     const long long teams = (long long)b->batch * n_states, per_block = 64 / b->sys->team;
     if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many states for one launch");
     HIP_TRY(hipSetDevice(b->device));
@@ -1579,7 +1645,9 @@ int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double
     A.iters = A.status = nullptr;
     A.n_steps = n_states;
     tg::DynInverseArgs J{};
-    tg::dyn_inverse_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    if (lsq) tg::dyn_inverse_lsq_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    else tg::dyn_inverse_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    J.rcond = rcond; J.rank = rank_dev;
     J.Q = Q_dev; J.dQ = dQ_dev; J.ddQ = ddQ_dev;
     J.U = U_dev; J.LAM = LAM_dev; J.RHO = RHO_dev; J.TAU = TAU_dev; J.ACC = ACC_dev; J.status = status_dev;
     J.ridge = ridge; J.n_states = n_states;
@@ -1587,7 +1655,7 @@ int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double
     const bool par = b->par_rows > 0;
     LaunchTiming timed;
     if (int rc = timing_begin(b, timed)) return rc;
-    int rc = tg_detail::launch_dyn_inverse(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+    int rc = tg_detail::launch_dyn_inverse(b->sys->team, launch_springs(b), par, lsq, b->d_prog.get(), A, J,
                                            tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0},
                                            (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
@@ -1595,12 +1663,29 @@ int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double
     return timing_end(b, timed, rc);
 }
 
-int tg_batch_dynamics_inverse(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
-                              double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *status) {
+int tg_batch_dynamics_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                                     uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
+                                     double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev, int32_t *status_dev) {
+    return dyn_inverse_device(b, n_states, Q_dev, q_row_stride_doubles, dQ_dev, dq_row_stride_doubles, ddQ_dev, ddq_row_stride_doubles, ridge, false,
+                              0.0, U_dev, LAM_dev, RHO_dev, TAU_dev, ACC_dev, nullptr, status_dev);
+}
+
+int tg_batch_dynamics_inverse_lsq_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                                         uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
+                                         double rcond, double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev,
+                                         int32_t *rank_dev, int32_t *status_dev) {
+    return dyn_inverse_device(b, n_states, Q_dev, q_row_stride_doubles, dQ_dev, dq_row_stride_doubles, ddQ_dev, ddq_row_stride_doubles, ridge, true,
+                              rcond, U_dev, LAM_dev, RHO_dev, TAU_dev, ACC_dev, rank_dev, status_dev);
+}
+
+// both host entry points
+static int dyn_inverse_host(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
+                            bool lsq, double rcond, double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *rank, int32_t *status) {
+    if (lsq) if (int rc = rcond_check(rcond)) return rc;
     const uint64_t nq_ = b && b->sys ? (uint64_t)b->sys->H.p.nq : 0;
-    if (int rc = dyn_inverse_check(b, n_states, Q_host, dQ_host, ddQ_host, nq_, nq_, nq_, ridge)) return rc;
+    if (int rc = dyn_inverse_check(b, n_states, Q_host, dQ_host, ddQ_host, nq_, nq_, nq_, ridge, lsq)) return rc;
     int32_t geo[4];
-    if (int rc = tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
+    if (int rc = lsq ? tg_system_dynamics_inverse_lsq_lds(b->sys, geo) : tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
     HIP_TRY(hipSetDevice(b->device));
     // staging of this call alone (its size follows n_states): Q, dQ, ddQ in; the outputs asked for and the status words out
     const size_t rows = (size_t)b->batch * n_states, nq = b->P.nq, nd = b->P.nd, nu = b->P.nu, nc = b->P.nc;
@@ -1609,19 +1694,64 @@ int tg_batch_dynamics_inverse(tg_batch *b, int32_t n_states, const double *Q_hos
     tg::DeviceBuffer<double> stage;
     tg::DeviceBuffer<int> words;
     HIP_TRY(stage.ensure(3 * n_q + n_u + n_l + n_r + n_t + n_a));
-    if (status) HIP_TRY(words.ensure(rows));
+    if (status || rank) HIP_TRY(words.ensure(2 * rows));      // (status, then rank)
     double *q = stage.get(), *dq = q + n_q, *ddq = dq + n_q, *u = ddq + n_q, *lam = u + n_u, *rho = lam + n_l, *tau = rho + n_r, *acc = tau + n_t;
     HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(dq, dQ_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(ddq, ddQ_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    int rc = tg_batch_dynamics_inverse_device(b, n_states, q, nq, dq, nq, ddq, nq, ridge, n_u ? u : nullptr, n_l ? lam : nullptr,
-                                              n_r ? rho : nullptr, n_t ? tau : nullptr, n_a ? acc : nullptr, status ? words.get() : nullptr);
+    int rc = dyn_inverse_device(b, n_states, q, nq, dq, nq, ddq, nq, ridge, lsq, rcond, n_u ? u : nullptr, n_l ? lam : nullptr, n_r ? rho : nullptr,
+                                n_t ? tau : nullptr, n_a ? acc : nullptr, rank ? words.get() + rows : nullptr, status ? words.get() : nullptr);
     auto back = [&](void *dst, const void *src, size_t bytes) {
         if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
             rc = fail(TG_ERR_HIP, "copy of the results failed");
     };
     back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(RHO, rho, n_r * sizeof(double));
     back(TAU, tau, n_t * sizeof(double)); back(ACC, acc, n_a * sizeof(double)); back(status, words.get(), rows * sizeof(int));
+    if (rank) back(rank, words.get() + rows, rows * sizeof(int));
+    if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
+    return rc;
+}
+
+int tg_batch_dynamics_inverse(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
+                              double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *status) {
+    return dyn_inverse_host(b, n_states, Q_host, dQ_host, ddQ_host, ridge, false, 0.0, U, LAM, RHO, TAU, ACC, nullptr, status);
+}
+
+int tg_batch_dynamics_inverse_lsq(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
+                                  double rcond, double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *rank, int32_t *status) {
+    return dyn_inverse_host(b, n_states, Q_host, dQ_host, ddQ_host, ridge, true, rcond, U, LAM, RHO, TAU, ACC, rank, status);
+}
+
+/* Test hook (tests/test_gpu_min_norm.py): the rank-revealing least-squares solver of the _lsq kernels (lsq_solve.hpp) alone, on `count`
+ * caller-supplied problems of one shape, A [count][rows][cols] and c [count][rows] (host), one team of `team` lanes (1, 4, 16 or 64,
+ * whatever the batch's own team size) on each, in one launch: z [count][cols], rank [count], status [count] (TG_OK, or TG_SINGULAR with
+ * z = 0 and rank 0 for an answer that is not finite).  Only here do teams of different rank share a wavefront. */
+int tg_batch_debug_lsq_solve(tg_batch *b, int32_t team, int32_t count, int32_t rows, int32_t cols, const double *A_host, const double *c_host,
+                             double rcond, double *z_host, int32_t *rank_host, int32_t *status_host) {
+    if (!b || !A_host || !c_host || !z_host || !rank_host || !status_host) return fail(TG_ERR_INVALID, "null argument");
+    if (team != 1 && team != 4 && team != 16 && team != 64) return fail(TG_ERR_INVALID, "team must be 1, 4, 16 or 64");
+    if (count < 1 || rows < 1 || cols < 1 || rows > 1024 || cols > 1024) return fail(TG_ERR_INVALID, "count, rows and cols must be positive (rows, cols at most 1024)");
+    if (int rc = rcond_check(rcond)) return rc;
+    const int per_team = (rows * (cols + 1) + tg::lsq_scratch_doubles(cols) + 1) & ~1;
+    // 64 / team teams to a workgroup as in the kernels, or as many as its 160 KiB of LDS take
+    const int per_block = (int)std::min<size_t>(64 / team, (160 * 1024) / (per_team * sizeof(double)));
+    if (per_block < 1) return fail(TG_ERR_UNSUPPORTED, "problem too large for the LDS of a workgroup");
+    const size_t lds = (size_t)per_block * per_team * sizeof(double);
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t cA = (size_t)count * rows * cols, cc = (size_t)count * rows, cz = (size_t)count * cols;
+    tg::DeviceBuffer<double> buf;
+    tg::DeviceBuffer<int> words;
+    HIP_TRY(buf.ensure(cA + cc + cz));
+    HIP_TRY(words.ensure(2 * (size_t)count));
+    double *dA = buf.get(), *dc = dA + cA, *dz = dc + cc;
+    HIP_TRY(hipMemcpyAsync(dA, A_host, cA * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dc, c_host, cc * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    int rc = tg_detail::launch_lsq_debug(team, per_block, count, rows, cols, per_team, dA, dc, rcond, dz, words.get(), words.get() + count, lds, b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == TG_SUCCESS && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess) rc = fail(TG_ERR_HIP, "copy of the results failed");
+    };
+    back(z_host, dz, cz * sizeof(double)); back(rank_host, words.get(), count * sizeof(int)); back(status_host, words.get() + count, count * sizeof(int));
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
 }

@@ -5,6 +5,8 @@
 // (DynInverseArgs::lds_per_team).  Generic only, with a parameter-table twin (PAR): the residual depends on masses, gravity and
 // damping, so a set table is honoured, trajectory b using row b / group.  A translation unit of its own so that it compiles beside
 // trepamd.hip.
+// LSQ: the instantiations whose solve is the rank-revealing least squares of lsq_solve.hpp (tg_batch_dynamics_inverse_lsq), and
+// k_lsq_debug, that solver alone on caller-supplied problems, one team each (tg_batch_debug_lsq_solve).
 #include <hip/hip_runtime.h>
 
 #include "launch_generic.hpp"
@@ -12,29 +14,75 @@
 
 namespace {
 
-template <int TEAM, bool SPRINGS, bool PAR>
+template <int TEAM, bool SPRINGS, bool PAR, bool LSQ>
 __global__ __launch_bounds__(64, 1) void k_dyn_inverse(const tg::DevProg *__restrict__ Pg, const tg::RunArgs A, const tg::DynInverseArgs J, const tg::ParTable T) {
     double *lds = tg_lds_base();
     tg::CProg &P = *(tg::CProg *)Pg;
     const int team = threadIdx.x / TEAM, lane = threadIdx.x % TEAM;
     const long long index = (long long)blockIdx.x * (64 / TEAM) + team;
-    tg::run_dyn_inverse<TEAM, SPRINGS, PAR>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, index);
+    tg::run_dyn_inverse<TEAM, SPRINGS, PAR, LSQ>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, index);
+}
+
+// problem p = blockIdx.x * (blockDim.x / TEAM) + team of `count`: A [rows][cols] and c [rows] into the team's block W [rows][cols + 1],
+// the solve, z [cols], rank and status out.  per_team: doubles of LDS per team (the block and the solver's scratch).  The workgroup
+// holds 64 / TEAM teams, or as many as the LDS takes (blockDim.x a multiple of TEAM, at most 64)
+template <int TEAM>
+__global__ __launch_bounds__(64, 1) void k_lsq_debug(int count, int rows, int cols, int per_team, const double *__restrict__ Ag,
+                                                     const double *__restrict__ cg, double rcond, double *__restrict__ zg, int *__restrict__ rank,
+                                                     int *__restrict__ status) {
+    double *lds = tg_lds_base();
+    const int team = threadIdx.x / TEAM, lane = threadIdx.x % TEAM;
+    const long long p = (long long)blockIdx.x * (blockDim.x / TEAM) + team;
+    const bool on = p < count;
+    const int ld = cols + 1;
+    double *W = lds + (size_t)team * per_team, *scr = W + (size_t)rows * ld;
+    if (on) {
+        const double *a = Ag + (size_t)p * rows * cols, *c = cg + (size_t)p * rows;
+        for (int e = lane; e < rows * cols; e += TEAM) W[(e / cols) * ld + e % cols] = a[e];
+        for (int i = lane; i < rows; i += TEAM) W[i * ld + cols] = c[i];
+    }
+    TG_SYNC();
+    bool ok = true;
+    const int r = tg::lsq_solve<TEAM>(on, W, rows, cols, ld, rcond, (int *)scr, scr + cols, scr + 2 * cols, scr + 3 * cols, lane, ok);
+    if (on) {
+        for (int j = lane; j < cols; j += TEAM) zg[(size_t)p * cols + j] = ok ? scr[2 * cols + j] : 0.0;
+        if (lane == 0) { rank[p] = ok ? r : 0; status[p] = ok ? TG_OK : TG_SINGULAR; }
+    }
 }
 
 }  // namespace
 
 namespace tg_detail {
-int launch_dyn_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
+int launch_dyn_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
 #if defined(TG_PROFILE)   // the diagnostic build instruments the default kernels only
-    (void)team; (void)springs; (void)par; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
+    (void)team; (void)springs; (void)par; (void)lsq; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
     return fail(TG_ERR_UNSUPPORTED, "the profiling build has no computed-torque kernel");
 #else
     return dispatch_team(team, [&](auto team_tag) {
         constexpr int TEAM = decltype(team_tag)::value;
-        auto kernel = par ? (springs ? &k_dyn_inverse<TEAM, true, true> : &k_dyn_inverse<TEAM, false, true>)
-                          : (springs ? &k_dyn_inverse<TEAM, true, false> : &k_dyn_inverse<TEAM, false, false>);
-        return launch_kernel(kernel, grid, lds, stream, d_prog, A, J, T);
+        auto pick = [&](auto lsq_tag) {
+            constexpr bool LSQ = decltype(lsq_tag)::value != 0;
+            return par ? (springs ? &k_dyn_inverse<TEAM, true, true, LSQ> : &k_dyn_inverse<TEAM, false, true, LSQ>)
+                       : (springs ? &k_dyn_inverse<TEAM, true, false, LSQ> : &k_dyn_inverse<TEAM, false, false, LSQ>);
+        };
+        return launch_kernel(lsq ? pick(tg::IntTag<1>()) : pick(tg::IntTag<0>()), grid, lds, stream, d_prog, A, J, T);
     });
 #endif
+}
+
+// the solver alone: `count` problems of one shape, one team of `team` lanes each, per_block teams to a workgroup
+int launch_lsq_debug(int team, int per_block, int count, int rows, int cols, int per_team, const double *A, const double *c, double rcond, double *z,
+                     int *rank, int *status, size_t lds, hipStream_t stream) {
+    return dispatch_team(team, [&](auto team_tag) {
+        constexpr int TEAM = decltype(team_tag)::value;
+        auto kernel = &k_lsq_debug<TEAM>;
+        if (lds > 64 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return fail(TG_ERR_HIP, std::string("hipFuncSetAttribute failed: ") + hipGetErrorString(e));
+        }
+        hipLaunchKernelGGL(kernel, dim3((count + per_block - 1) / per_block), dim3(per_block * TEAM), lds, stream, count, rows, cols, per_team, A, c,
+                           rcond, z, rank, status);
+        return (int)TG_SUCCESS;
+    });
 }
 }  // namespace tg_detail

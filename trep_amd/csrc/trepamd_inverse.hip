@@ -12,28 +12,31 @@
 
 namespace {
 
-template <int TEAM, bool SPRINGS, bool PAR>
+template <int TEAM, bool SPRINGS, bool PAR, bool LSQ>
 __global__ __launch_bounds__(64, 1) void k_inverse(const tg::DevProg *__restrict__ Pg, const tg::RunArgs A, const tg::InverseArgs J, const tg::ParTable T) {
     double *lds = tg_lds_base();
     tg::CProg &P = *(tg::CProg *)Pg;
     const int team = threadIdx.x / TEAM, lane = threadIdx.x % TEAM;
     const long long index = (long long)blockIdx.x * (64 / TEAM) + team;
-    tg::run_inverse<TEAM, SPRINGS, PAR>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, index);
+    tg::run_inverse<TEAM, SPRINGS, PAR, LSQ>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, index);
 }
 
 }  // namespace
 
 namespace tg_detail {
-int launch_inverse(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
+int launch_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
 #if defined(TG_PROFILE)   // the diagnostic build instruments the default kernels only
-    (void)team; (void)springs; (void)par; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
+    (void)team; (void)springs; (void)par; (void)lsq; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
     return fail(TG_ERR_UNSUPPORTED, "the profiling build has no inverse-dynamics kernel");
 #else
     return dispatch_team(team, [&](auto team_tag) {
         constexpr int TEAM = decltype(team_tag)::value;
-        auto kernel = par ? (springs ? &k_inverse<TEAM, true, true> : &k_inverse<TEAM, false, true>)
-                          : (springs ? &k_inverse<TEAM, true, false> : &k_inverse<TEAM, false, false>);
-        return launch_kernel(kernel, grid, lds, stream, d_prog, A, J, T);
+        auto pick = [&](auto lsq_tag) {      // LSQ: the solve is lsq_solve.hpp's (tg_batch_inverse_dynamics_lsq)
+            constexpr bool LSQ = decltype(lsq_tag)::value != 0;
+            return par ? (springs ? &k_inverse<TEAM, true, true, LSQ> : &k_inverse<TEAM, false, true, LSQ>)
+                       : (springs ? &k_inverse<TEAM, true, false, LSQ> : &k_inverse<TEAM, false, false, LSQ>);
+        };
+        return launch_kernel(lsq ? pick(tg::IntTag<1>()) : pick(tg::IntTag<0>()), grid, lds, stream, d_prog, A, J, T);
     });
 #endif
 }

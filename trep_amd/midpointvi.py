@@ -26,6 +26,9 @@ InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h statu
 FrameKinematics = collections.namedtuple("FrameKinematics", "g vb p_dq vb_ddq")         # BatchMidpointVI.frame_kinematics
 TapeMeasures = collections.namedtuple("TapeMeasures", "length velocity length_dq velocity_dq length_dqdq")      # BatchMidpointVI.tape_measures
 DynamicsInverse = collections.namedtuple("DynamicsInverse", "U lam rho tau acc status")     # BatchMidpointVI.dynamics_inverse
+# ... and what the two inverse questions return with rcond=: the rank of every state or step as one more field
+InverseDynamicsRank = collections.namedtuple("InverseDynamicsRank", "U lam P rho h status rank")
+DynamicsInverseRank = collections.namedtuple("DynamicsInverseRank", "U lam rho tau acc status rank")
 
 
 class BatchMidpointVI(object):
@@ -496,7 +499,7 @@ class BatchMidpointVI(object):
                                              _lib.ptr(ddq), _lib.ptr(lam), status.ctypes.data))
         return ddq, lam, status
 
-    def dynamics_inverse(self, Q, dQ, ddQ, ridge=0.0):
+    def dynamics_inverse(self, Q, dQ, ddQ, ridge=0.0, rcond=None):
         """Computed torque, the inverse of dynamics() (include/trep_amd.h, tg_batch_dynamics_inverse): Q, dQ, ddQ [B][nq] or
         [B][M][nq], kinematic configs included (the kinematic part of ddQ is what dynamics() calls ddQk).  Every state is one
         least-squares solve for (u, lambda), all B x M of them in one launch.  Returns the namedtuple (U [B][M][nu], lam [B][M][nc],
@@ -505,7 +508,12 @@ class BatchMidpointVI(object):
         from consistent with the constraints.  status: TG_OK, or TG_SINGULAR where the solver rejected the state (U, lam, rho zero
         there).  ridge >= 0 weighs |(u, lambda)|^2 against |rho|^2; it is required (ValueError) when nu + nc > nd, and a
         rank-deficient system needs it too -- that is not detected.  For inputs [B][nq] the M axis is dropped.  With a parameter
-        table each trajectory uses its row; the time base has no say.  The integrator state of the batch is left alone."""
+        table each trajectory uses its row; the time base has no say.  The integrator state of the batch is left alone.
+        rcond (a float in [0, 1); None: the path above, unchanged) answers by rank-revealing least squares instead
+        (tg_batch_dynamics_inverse_lsq): (u, lambda) is numpy.linalg.lstsq's minimum-norm answer on [A; sqrt(ridge) I], so a
+        rank-deficient system needs no ridge and nu + nc > nd is accepted without one; pivot columns with a norm <= rcond times the
+        first one's count as dependent.  The namedtuple then has rank [B][M] as an additional last field: the number of independent
+        force directions of each state (with ridge > 0: of the stacked block)."""
         self.refresh()
         B, nq = self._batch, self.nq
         Q = np.ascontiguousarray(Q, dtype=np.float64)
@@ -524,26 +532,43 @@ class BatchMidpointVI(object):
         dQ, ddQ = like_q(dQ, "dQ"), like_q(ddQ, "ddQ")
         U, lam, rho = np.zeros((B, M, self.nu)), np.zeros((B, M, self.nc)), np.zeros((B, M, self.nd))
         tau, acc, status = np.zeros((B, M, self.nd)), np.zeros((B, M, self.nc)), np.zeros((B, M), dtype=np.int32)
-        rc = self._L.tg_batch_dynamics_inverse(self._h, M, Q.ctypes.data, dQ.ctypes.data, ddQ.ctypes.data, float(ridge), _lib.ptr(U),
-                                               _lib.ptr(lam), _lib.ptr(rho), _lib.ptr(tau), _lib.ptr(acc), status.ctypes.data)
+        rank = np.zeros((B, M), dtype=np.int32)
+        if rcond is None:
+            rc = self._L.tg_batch_dynamics_inverse(self._h, M, Q.ctypes.data, dQ.ctypes.data, ddQ.ctypes.data, float(ridge), _lib.ptr(U),
+                                                   _lib.ptr(lam), _lib.ptr(rho), _lib.ptr(tau), _lib.ptr(acc), status.ctypes.data)
+        else:
+            rc = self._L.tg_batch_dynamics_inverse_lsq(self._h, M, Q.ctypes.data, dQ.ctypes.data, ddQ.ctypes.data, float(ridge), float(rcond),
+                                                       _lib.ptr(U), _lib.ptr(lam), _lib.ptr(rho), _lib.ptr(tau), _lib.ptr(acc),
+                                                       rank.ctypes.data, status.ctypes.data)
         if rc == _lib.ERR_INVALID:
             raise ValueError(self._L.tg_last_error().decode())
         _lib.check(rc)
         drop = (lambda a: a[:, 0]) if flat else (lambda a: a)
-        return DynamicsInverse(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status))
+        if rcond is None:
+            return DynamicsInverse(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status))
+        return DynamicsInverseRank(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status), drop(rank))
 
     def dynamics_inverse_device(self, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride=None, dq_row_stride=None, ddq_row_stride=None,
-                                ridge=0.0, U_dev=None, lam_dev=None, rho_dev=None, tau_dev=None, acc_dev=None, status_dev=None):
+                                ridge=0.0, U_dev=None, lam_dev=None, rho_dev=None, tau_dev=None, acc_dev=None, status_dev=None,
+                                rcond=None, rank_dev=None):
         """dynamics_inverse on device pointers, asynchronous on the batch's stream (tg_batch_dynamics_inverse_device).  Row (b, m) is
         read at Q_dev + (b n_states + m) q_row_stride doubles (dQ_dev and ddQ_dev likewise with their own strides): the default nq
         for packed arrays, nX to read the configurations straight from a rollout's X [B][n_states][nX].  The outputs are laid out as
-        dynamics_inverse returns them ([B][n_states]...); any may be None."""
+        dynamics_inverse returns them ([B][n_states]...); any may be None.  rcond (None: the path above): the rank-revealing path
+        (tg_batch_dynamics_inverse_lsq_device), with rank_dev int32 [B][n_states] or None."""
         self.refresh()
         nq = self.nq
-        rc = self._L.tg_batch_dynamics_inverse_device(self._h, int(n_states), Q_dev, int(nq if q_row_stride is None else q_row_stride),
-                                                      dQ_dev, int(nq if dq_row_stride is None else dq_row_stride), ddQ_dev,
-                                                      int(nq if ddq_row_stride is None else ddq_row_stride), float(ridge), U_dev, lam_dev,
-                                                      rho_dev, tau_dev, acc_dev, status_dev)
+        strides = (int(nq if q_row_stride is None else q_row_stride), int(nq if dq_row_stride is None else dq_row_stride),
+                   int(nq if ddq_row_stride is None else ddq_row_stride))
+        if rcond is None:
+            if rank_dev is not None:
+                raise ValueError("rank_dev needs rcond")
+            rc = self._L.tg_batch_dynamics_inverse_device(self._h, int(n_states), Q_dev, strides[0], dQ_dev, strides[1], ddQ_dev, strides[2],
+                                                          float(ridge), U_dev, lam_dev, rho_dev, tau_dev, acc_dev, status_dev)
+        else:
+            rc = self._L.tg_batch_dynamics_inverse_lsq_device(self._h, int(n_states), Q_dev, strides[0], dQ_dev, strides[1], ddQ_dev, strides[2],
+                                                              float(ridge), float(rcond), U_dev, lam_dev, rho_dev, tau_dev, acc_dev, rank_dev,
+                                                              status_dev)
         if rc == _lib.ERR_INVALID:
             raise ValueError(self._L.tg_last_error().decode())
         _lib.check(rc)
@@ -614,7 +639,7 @@ class BatchMidpointVI(object):
         finally:
             self.set_step_sizes(*(saved if saved is not None else (None,)))
 
-    def inverse_dynamics(self, Q, dt, p0=None, ridge=0.0):
+    def inverse_dynamics(self, Q, dt, p0=None, ridge=0.0, rcond=None):
         """Inputs and constraint forces of given paths (include/trep_amd.h, tg_batch_inverse_dynamics): Q [B][N+1][nq], kinematic
         configs included; `dt` a scalar or one step size per step; p0 [B][nd], optional.  Every step (b, k) is one least-squares
         solve for the impulses (dt_k u_k, lambda_k), all B x N of them in one launch.  Returns the namedtuple (U [B][N][nu], lam
@@ -624,7 +649,11 @@ class BatchMidpointVI(object):
         retrace Q (inverse_dynamics_trajectory packs that).  status: TG_OK, or TG_SINGULAR where the solver rejected the step (U,
         lam, rho zero there).  ridge >= 0 weighs |(dt u, lambda)|^2 against |rho|^2; it is required (ValueError) when nu + nc > nd,
         and a rank-deficient system needs it too -- that is not detected.  With a parameter table each trajectory uses its row.
-        The integrator state of the batch is left alone."""
+        The integrator state of the batch is left alone.
+        rcond (a float in [0, 1); None: the path above, unchanged) answers by rank-revealing least squares instead
+        (tg_batch_inverse_dynamics_lsq): the impulses are numpy.linalg.lstsq's minimum-norm answer on [A~; sqrt(ridge) I], so a
+        rank-deficient system needs no ridge and nu + nc > nd is accepted without one.  The namedtuple then has rank [B][N] as an
+        additional last field (0 for a step that is not solved)."""
         self.refresh()
         B = self._batch
         Q = np.ascontiguousarray(Q, dtype=np.float64)
@@ -635,25 +664,42 @@ class BatchMidpointVI(object):
         p0 = None if p0 is None else _lib.as_f64(np.broadcast_to(np.asarray(p0, dtype=float), (B, self.nd)), (B, self.nd))
         U, lam, P = np.zeros((B, N, self.nu)), np.zeros((B, N, self.nc)), np.zeros((B, N + 1, self.nd))
         rho, h, status = np.zeros((B, N, self.nd)), np.zeros((B, N, self.nc)), np.zeros((B, N), dtype=np.int32)
+        rank = np.zeros((B, N), dtype=np.int32)
 
         def call():
-            rc = self._L.tg_batch_inverse_dynamics(self._h, N, dt, Q.ctypes.data, None if p0 is None else p0.ctypes.data, float(ridge),
-                                                   _lib.ptr(U), _lib.ptr(lam), _lib.ptr(P), _lib.ptr(rho), _lib.ptr(h), status.ctypes.data)
+            p0_ptr = None if p0 is None else p0.ctypes.data
+            if rcond is None:
+                rc = self._L.tg_batch_inverse_dynamics(self._h, N, dt, Q.ctypes.data, p0_ptr, float(ridge), _lib.ptr(U), _lib.ptr(lam),
+                                                       _lib.ptr(P), _lib.ptr(rho), _lib.ptr(h), status.ctypes.data)
+            else:
+                rc = self._L.tg_batch_inverse_dynamics_lsq(self._h, N, dt, Q.ctypes.data, p0_ptr, float(ridge), float(rcond), _lib.ptr(U),
+                                                           _lib.ptr(lam), _lib.ptr(P), _lib.ptr(rho), _lib.ptr(h), rank.ctypes.data,
+                                                           status.ctypes.data)
             if rc == _lib.ERR_INVALID:
                 raise ValueError(self._L.tg_last_error().decode())
             _lib.check(rc)
         self._with_step_sizes(dts, call)
-        return InverseDynamics(U, lam, P, rho, h, status)
+        if rcond is None:
+            return InverseDynamics(U, lam, P, rho, h, status)
+        return InverseDynamicsRank(U, lam, P, rho, h, status, rank)
 
     def inverse_dynamics_device(self, n_steps, dt, Q_dev, q_row_stride=None, p0_dev=None, ridge=0.0, U_dev=None, lam_dev=None,
-                                P_dev=None, rho_dev=None, h_dev=None, status_dev=None):
+                                P_dev=None, rho_dev=None, h_dev=None, status_dev=None, rcond=None, rank_dev=None):
         """inverse_dynamics on device pointers, asynchronous on the batch's stream (tg_batch_inverse_dynamics_device).  Row (b, k) of
         the path is read at Q_dev + (b (n_steps + 1) + k) q_row_stride doubles: the default nq for a packed Q, nX to read the
         configurations straight from a rollout's X [B][N+1][nX].  Any output may be None.  The step sizes are the scalar dt or the
-        by-step list the batch has (set_step_sizes)."""
+        by-step list the batch has (set_step_sizes).  rcond (None: the path above): the rank-revealing path
+        (tg_batch_inverse_dynamics_lsq_device), with rank_dev int32 [B][n_steps] or None."""
         self.refresh()
-        rc = self._L.tg_batch_inverse_dynamics_device(self._h, int(n_steps), float(dt), Q_dev, int(self.nq if q_row_stride is None else q_row_stride),
-                                                      p0_dev, float(ridge), U_dev, lam_dev, P_dev, rho_dev, h_dev, status_dev)
+        stride = int(self.nq if q_row_stride is None else q_row_stride)
+        if rcond is None:
+            if rank_dev is not None:
+                raise ValueError("rank_dev needs rcond")
+            rc = self._L.tg_batch_inverse_dynamics_device(self._h, int(n_steps), float(dt), Q_dev, stride, p0_dev, float(ridge), U_dev, lam_dev,
+                                                          P_dev, rho_dev, h_dev, status_dev)
+        else:
+            rc = self._L.tg_batch_inverse_dynamics_lsq_device(self._h, int(n_steps), float(dt), Q_dev, stride, p0_dev, float(ridge), float(rcond),
+                                                              U_dev, lam_dev, P_dev, rho_dev, h_dev, rank_dev, status_dev)
         if rc == _lib.ERR_INVALID:
             raise ValueError(self._L.tg_last_error().decode())
         _lib.check(rc)
