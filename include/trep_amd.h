@@ -672,6 +672,63 @@ int tg_batch_dynamics_inverse_lsq_device(tg_batch *b, int32_t n_states, const do
 int tg_batch_debug_lsq_solve(tg_batch *b, int32_t team, int32_t count, int32_t rows, int32_t cols, const double *A_host,
                              const double *c_host, double rcond, double *z_host, int32_t *rank_host, int32_t *status_host);
 
+/* ---- bounded inverse dynamics: strings that only pull, inputs within limits ------------------------------------------------
+ * The box-constrained versions of tg_batch_dynamics_inverse_lsq and tg_batch_inverse_dynamics_lsq.  Per state or step
+ *   minimise |r0 + A z|^2 + ridge |z|^2   subject to   lo <= z <= hi,   z = (u, lambda),
+ * with r0, A, TAU, ACC, P, H evaluated exactly as by the _lsq siblings, solved exactly by an active-set method (Stark-Parker BVLS, the
+ * method of scipy.optimize.lsq_linear(method="bvls")): a short sequence of rank-revealing least-squares solves on the free columns of
+ * W = [A; sqrt(ridge) I], c = (-r0; 0) (csrc/bvls_solve.hpp; tests/bounded_reference.py is the specification).  The first solve has
+ * every variable free: with all bounds infinite the results are the _lsq siblings' bit for bit, and a state whose unconstrained answer
+ * lies in the box costs one solve.
+ * Arguments: those of the _lsq sibling, and behind rcond
+ *   lo, hi [bound_rows][nu + nc] in (u | lambda) order: host arrays in the host variants, device arrays in the _device variants;
+ *   bound_rows is 1 (one box for the launch) or B (trajectory b uses row b); -INFINITY / +INFINITY mean no bound.  In
+ *   tg_batch_inverse_dynamics_bounded the bounds on u are FORCES (the kernel scales them by the step's own dt_k, uniform or from
+ *   tg_batch_set_step_sizes, to bounds on the impulses it solves for) and the bounds on lambda apply to lambda as returned;
+ * and, ahead of rank,
+ *   active [..][nu + nc] (int32, nullable): -1 at the lower bound, +1 at the upper, 0 free (scipy's active_mask); lo == hi reports -1;
+ *   solves [..] (int32, nullable): the least-squares solves the state took (0 where nothing is solved).
+ * rank is the FIRST solve's.  status: TG_OK (the KKT conditions hold); TG_SINGULAR when the first solve finds rank < n at rcond -- the
+ * problem is then not strictly convex and its minimiser not unique: USE A RIDGE; U, LAM, RHO and active are zero, rank is reported --
+ * and for anything not finite (rank 0 too, as the siblings); TG_NOT_CONVERGED when 3 n + 3 solves did not reach the KKT conditions (not
+ * observed): U, LAM, RHO, active are then the last feasible iterate's.  n == 0: nothing is solved, rho = r0.
+ * WHICH SIGN PULLS.  A Distance constraint is h = |p1 - p2| - d (reference Distance.h).  In the continuous equations the multipliers
+ * enter as +Ad' lambda on the side of the applied forces: lambda > 0 pushes the two points apart, so a string (which can only pull
+ * them together) has lambda <= 0 in tg_batch_dynamics_inverse*: lo = -inf, hi = 0.  In the discrete equations they enter as
+ * -Dh' lambda: a string has lambda >= 0 in tg_batch_inverse_dynamics* (and in the integrator's lambda1): lo = 0, hi = +inf.
+ * TG_ERR_INVALID, before a device is touched: everything the _lsq sibling refuses; n > nd at ridge == 0 (never strictly convex);
+ * bound_rows other than 1 or B; a null lo or hi with n > 0; and, in the host variants, which can read the box, a bound that is not a
+ * number, lo_j > hi_j, lo_j == +inf or hi_j == -inf.  The _device variants take the box's contents on trust (a box that breaks these
+ * rules cannot hang the kernel -- its loop has a fixed cap -- but the answer is then not specified).
+ * LDS per team: the _lsq sibling's, plus a second block (nd + n)(n + 1) and 5 n doubles (tg_system_*_bounded_lds: the 160 KiB refusal
+ * without a device).  Generic kernels only, with parameter twins, counted under modes 14 and 11 of tg_batch_info like their siblings.
+ * tg_batch_debug_bvls_solve (test hook) runs the solver alone as tg_batch_debug_lsq_solve does, with lo, hi [count][cols] and a cap
+ * max_solves in 0 .. 3 cols + 3 (0: 3 cols + 3) on the solves of a problem. */
+int tg_system_dynamics_inverse_bounded_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_dynamics_inverse_bounded(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host,
+                                      double ridge, double rcond, const double *lo_host, const double *hi_host, int32_t bound_rows,
+                                      double *U, double *LAM, double *RHO, double *TAU, double *ACC,
+                                      int32_t *active, int32_t *solves, int32_t *rank, int32_t *status);
+int tg_batch_dynamics_inverse_bounded_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                             const double *dQ_dev, uint64_t dq_row_stride_doubles,
+                                             const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge, double rcond,
+                                             const double *lo_dev, const double *hi_dev, int32_t bound_rows,
+                                             double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev,
+                                             int32_t *active_dev, int32_t *solves_dev, int32_t *rank_dev, int32_t *status_dev);
+int tg_system_inverse_dynamics_bounded_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_inverse_dynamics_bounded(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge,
+                                      double rcond, const double *lo_host, const double *hi_host, int32_t bound_rows,
+                                      double *U, double *LAM, double *P, double *RHO, double *H,
+                                      int32_t *active, int32_t *solves, int32_t *rank, int32_t *status);
+int tg_batch_inverse_dynamics_bounded_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                             const double *p0_dev, double ridge, double rcond,
+                                             const double *lo_dev, const double *hi_dev, int32_t bound_rows,
+                                             double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev, double *H_dev,
+                                             int32_t *active_dev, int32_t *solves_dev, int32_t *rank_dev, int32_t *status_dev);
+int tg_batch_debug_bvls_solve(tg_batch *b, int32_t team, int32_t count, int32_t rows, int32_t cols, const double *A_host,
+                              const double *c_host, const double *lo_host, const double *hi_host, double rcond, int32_t max_solves,
+                              double *z_host, int32_t *active_host, int32_t *solves_host, int32_t *rank_host, int32_t *status_host);
+
 /* DSystem.set(X[s][k], U[s][k], k, xk_hint = X[s][k+1]) for every (s, k) at once (reference
  * trep/discopt/dsystem.py:229-251 as used by linearize_trajectory, :406-423, and calc_newton_model,
  * doptimizer.py:333-335): the batch must hold seeds*horizon trajectories, trajectory t = s*horizon + k;

@@ -197,6 +197,17 @@ _LSQ_SIGNATURES = {
     "tg_batch_debug_lsq_solve": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _f64, _vp, _vp, _vp]),
 }
 
+# The box-constrained twins of those (lo, hi, bound_rows after rcond; active, solves before rank) and the bounded solver's test hook.
+_BOUNDED_SIGNATURES = {
+    "tg_system_inverse_dynamics_bounded_lds": (ctypes.c_int, [_vp, _c_ip]),
+    "tg_batch_inverse_dynamics_bounded": (ctypes.c_int, [_vp, _i32, _f64, _vp, _vp, _f64, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_inverse_dynamics_bounded_device": (ctypes.c_int, [_vp, _i32, _f64, _vp, ctypes.c_uint64, _vp, _f64, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tg_system_dynamics_inverse_bounded_lds": (ctypes.c_int, [_vp, _c_ip]),
+    "tg_batch_dynamics_inverse_bounded": (ctypes.c_int, [_vp, _i32, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_dynamics_inverse_bounded_device": (ctypes.c_int, [_vp, _i32, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _vp, ctypes.c_uint64, _f64, _f64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_debug_bvls_solve": (ctypes.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class LibraryError(RuntimeError):
     pass
@@ -216,7 +227,7 @@ def lib():
         # and it must be in the environment before the HIP runtime initialises, i.e. before the library that links it is loaded.
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()) + list(_INVERSE_SIGNATURES.items()) + list(_FRAMES_SIGNATURES.items()) + list(_TAPE_SIGNATURES.items()) + list(_DYN_INVERSE_SIGNATURES.items()) + list(_LSQ_SIGNATURES.items()):
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()) + list(_INVERSE_SIGNATURES.items()) + list(_FRAMES_SIGNATURES.items()) + list(_TAPE_SIGNATURES.items()) + list(_DYN_INVERSE_SIGNATURES.items()) + list(_LSQ_SIGNATURES.items()) + list(_BOUNDED_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -225,7 +236,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES) + list(_INVERSE_SIGNATURES) + list(_FRAMES_SIGNATURES) + list(_TAPE_SIGNATURES) + list(_DYN_INVERSE_SIGNATURES) + list(_LSQ_SIGNATURES))
+    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES) + list(_INVERSE_SIGNATURES) + list(_FRAMES_SIGNATURES) + list(_TAPE_SIGNATURES) + list(_DYN_INVERSE_SIGNATURES) + list(_LSQ_SIGNATURES) + list(_BOUNDED_SIGNATURES))
 
 
 def check(rc):

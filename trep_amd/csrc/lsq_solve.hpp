@@ -112,14 +112,18 @@ TG_HD int lsq_factor(bool on, double *X, int rs, int cs, int rows, int cols, int
 
 // The solve described at the head of the file.  on: this team has a problem (an idle team still takes part in every TG_SYNC).
 // Returns the rank; z [n] holds the answer, ok whether it is finite.  W, perm, nrm and tau2 are left as the factorisation left them.
+// n is THIS TEAM's column count (0 is allowed: rank 0, nothing written), n_trips >= n the launch's, which alone sets the trip count of
+// every loop with a fence in it (bvls_solve.hpp: the free set's size is a team's own); -1: n, the _lsq kernels' case.
 template <int TEAM>
-TG_HD int lsq_solve(bool on, double *W, int R, int n, int ld, double rcond, int *perm, double *nrm, double *z, double *tau2, int lane, bool &ok) {
-    const int trips = R < n ? R : n;
+TG_HD int lsq_solve(bool on, double *W, int R, int n, int ld, double rcond, int *perm, double *nrm, double *z, double *tau2, int lane, bool &ok,
+                    int n_trips = -1) {
+    if (n_trips < 0) n_trips = n;
+    const int trips = R < n_trips ? R : n_trips, own = R < n ? R : n;
     if (on) for (int j = lane; j < n; j += TEAM) perm[j] = j;
     bool bad = false;
     if (on) for (int i = 0; i < R; i++) if (!(fabs(W[i * ld + n]) <= DBL_MAX)) bad = true;      // (every lane scans the same words: team-uniform)
     TG_SYNC();
-    const int r = lsq_factor<TEAM, true>(on, W, ld, 1, R, n, 1, trips, trips, rcond, perm, nrm, nullptr, lane, bad);
+    const int r = lsq_factor<TEAM, true>(on, W, ld, 1, R, n, 1, own, trips, rcond, perm, nrm, nullptr, lane, bad);
     TG_SYNC();
     const bool deficient = on && r < n;
     const int r2 = lsq_factor<TEAM, false>(deficient, W, 1, ld, n, r, 0, r, trips, 0.0, nullptr, nullptr, tau2, lane, bad);

@@ -52,6 +52,11 @@ struct DynInverseArgs {
     int lds_per_team;            // doubles per team: what the kernel strides its teams by
     double rcond;                // the LSQ kernels alone: pivot norms <= rcond * the first one end the factorisation
     int *rank;                   // the LSQ kernels alone: [batch][n_states] or null
+    // the BND kernels alone (which use rcond and rank too):
+    const double *lo, *hi;       // the box [bound_rows][nu + nc] in (u | lambda) order, -inf / +inf: no bound
+    int bound_rows;              // 1: one box for the launch; batch: one per trajectory
+    int max_solves;              // the cap on the least-squares solves of a state (bvls_max_solves)
+    int *active, *solves;        // [batch][n_states][nu + nc] (-1 at lo, +1 at hi, 0 free), [batch][n_states]; each may be null
 };
 
 // the scratch layout of one team (host; the same numbers for the device launch and the emulation)
@@ -75,9 +80,22 @@ inline void dyn_inverse_lsq_layout(int rollout_lds_per_team, int nq, int nd, int
     J.lds_per_team = (off + 1) & ~1;
 }
 
+// ... and of the BND kernels: o_kkt the PRISTINE stacked block [nd + n][n + 1], o_scal the solver's scratch (bvls_solve.hpp: the
+// working block of the same size, lo, hi, z, the gradient, the bound-state words, and lsq_solve's 4 n)
+inline void dyn_inverse_bounded_layout(int rollout_lds_per_team, int nq, int nd, int nu, int nc, DynInverseArgs &J) {
+    const int n = nu + nc;
+    int off = (rollout_lds_per_team + 1) & ~1;
+    J.o_kkt = off; off += (nd + n) * (n + 1);
+    J.o_ddq = off; off += nq;
+    J.o_scal = off; off += bvls_scratch_doubles(nd + n, n);
+    J.lds_per_team = (off + 1) & ~1;
+}
+
 // team index i = b * n_states + s; i >= batch * n_states: an idle team, which still takes part in every TG_SYNC
 // LSQ: the solve is lsq_solve.hpp's on [A; sqrt(ridge) I] (inverse_lsq_stage) in place of the augmented image, and J.rank is written
-template <int TEAM, bool SPRINGS, bool PAR, bool LSQ = false, class PROG, class ARGS>
+// BND: the solve is bvls_solve.hpp's on the same block with the box J.lo, J.hi (inverse_bounded_stage); J.rank, J.active and J.solves
+// are written, and the status may be TG_NOT_CONVERGED (U, LAM, RHO then belong to the last feasible iterate)
+template <int TEAM, bool SPRINGS, bool PAR, bool LSQ = false, bool BND = false, class PROG, class ARGS>
 TG_HD void run_dyn_inverse(PROG &P, ARGS &A, const DynInverseArgs &J, const ParTable T, double *S, int lane, long long team_index) {
     const int nq = P.nq, nd = P.nd, nu = P.nu, nc = P.nc, nf = P.nf, M = J.n_states;
     const int n = nu + nc, m = nd + n, ld = m + 1;
@@ -162,6 +180,25 @@ TG_HD void run_dyn_inverse(PROG &P, ARGS &A, const DynInverseArgs &J, const ParT
 
     const bool solve = live && n > 0;
     if (live && !solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = rhs[i];      // n == 0: rho = r0
+    if constexpr (BND) {
+        // ---- the pristine stacked block, the active-set loop around the rank-revealing solve, rho from r0 and the block's rows ------
+        int r = 0, solves = 0, st = TG_OK;
+        const size_t box = (J.bound_rows > 1 ? b : 0) * (size_t)n;
+        if (n > 0) r = inverse_bounded_stage<TEAM>(core, P, S, lane, solve, rhs, S + P.o_Dh2, false, J.ridge, J.rcond, J.lo + box, J.hi + box, 1.0,
+                                                   J.max_solves, K, scal, solves, st);
+        const bool answer = solve && st != TG_SINGULAR;
+        const BvlsScratch X = bvls_scratch(scal, nd + (J.ridge > 0.0 ? n : 0), n);
+        if (live) {
+            if (J.U) TG_FOR(i, nu) J.U[bs * nu + i] = answer ? X.z[i] : 0.0;
+            if (J.LAM) TG_FOR(c, nc) J.LAM[bs * nc + c] = answer ? X.z[nu + c] : 0.0;
+            if (solve && J.RHO) TG_FOR(i, nd) J.RHO[bs * nd + i] = answer ? K[i * (n + 1) + n] : 0.0;
+            if (J.active) TG_FOR(j, n) J.active[bs * n + j] = answer ? X.bnd[j] : 0;
+            if (lane == 0 && J.solves) J.solves[bs] = solves;
+            if (lane == 0 && J.rank) J.rank[bs] = solve ? r : 0;
+            if (lane == 0 && J.status) J.status[bs] = st;
+        }
+        return;
+    }
     if constexpr (LSQ) {
         // ---- the stacked block [A; sqrt(ridge) I] with (-r0; 0), its rank-revealing solve, rho from r0 and A ----------------------------
         bool ok = true;

@@ -56,6 +56,11 @@ struct InverseArgs {
     int lds_per_team;            // doubles per team: what the kernel strides its teams by
     double rcond;                // the LSQ kernels alone: pivot norms <= rcond * the first one end the factorisation
     int *rank;                   // the LSQ kernels alone: [batch][n_steps] or null
+    // the BND kernels alone (which use rcond and rank too):
+    const double *lo, *hi;       // the box [bound_rows][nu + nc] in (u | lambda) order, u as FORCES; -inf / +inf: no bound
+    int bound_rows;              // 1: one box for the launch; batch: one per trajectory
+    int max_solves;              // the cap on the least-squares solves of a step (bvls_max_solves)
+    int *active, *solves;        // [batch][n_steps][nu + nc] (-1 at lo, +1 at hi, 0 free), [batch][n_steps]; each may be null
 };
 
 // the scratch layout of one team (host; the same numbers for the device launch and the emulation)
@@ -79,10 +84,24 @@ inline void inverse_lsq_layout(int rollout_lds_per_team, int nd, int nu, int nc,
     J.lds_per_team = (off + 1) & ~1;
 }
 
+// ... and of the BND kernels: o_kkt the PRISTINE stacked block [nd + n][n + 1], o_scal the solver's scratch (bvls_solve.hpp: the
+// working block of the same size, lo, hi, z, the gradient, the bound-state words, and lsq_solve's 4 n)
+inline void inverse_bounded_layout(int rollout_lds_per_team, int nd, int nu, int nc, InverseArgs &J) {
+    const int n = nu + nc;
+    int off = (rollout_lds_per_team + 1) & ~1;
+    J.o_kkt = off; off += (nd + n) * (n + 1);
+    J.o_pk = off; off += nd;
+    J.o_scal = off; off += bvls_scratch_doubles(nd + n, n);
+    J.lds_per_team = (off + 1) & ~1;
+}
+
 // team index i = b * n_steps + k; i >= batch * n_steps: an idle team, which still takes part in every TG_SYNC
 // LSQ: the solve is lsq_solve.hpp's on [A~; sqrt(ridge) I] (inverse_lsq_stage) in place of the augmented image, run BEFORE the
 // constraints of Q_{k+1} are evaluated (r0, o_wD and Dh(Q_k) are then still in place for rho), and J.rank is written
-template <int TEAM, bool SPRINGS, bool PAR, bool LSQ = false, class PROG, class ARGS>
+// BND: as LSQ, the solve being bvls_solve.hpp's with the box J.lo, J.hi (inverse_bounded_stage): the bounds on u are forces and are
+// scaled by this step's dt_k to bounds on the impulses dt_k u; those on lambda apply to lambda as returned.  J.active and J.solves
+// are written, and the status may be TG_NOT_CONVERGED (U, LAM, RHO then belong to the last feasible iterate)
+template <int TEAM, bool SPRINGS, bool PAR, bool LSQ = false, bool BND = false, class PROG, class ARGS>
 TG_HD void run_inverse(PROG &P, ARGS &A, const InverseArgs &J, const ParTable T, double *S, int lane, long long team_index) {
     const int nq = P.nq, nd = P.nd, nu = P.nu, nc = P.nc, N = J.n_steps;
     const int n = nu + nc, m = nd + n, ld = m + 1;
@@ -139,6 +158,26 @@ TG_HD void run_inverse(PROG &P, ARGS &A, const InverseArgs &J, const ParTable T,
         core.eval_constraints(live, 2, true, S + P.o_Dh2);
         if (live && J.H) TG_FOR(c, nc) J.H[bk * nc + c] = S[P.o_f + nd + c];
     };
+    if constexpr (BND) {
+        // the pristine stacked block, the active-set loop around the rank-revealing solve, rho from r0 and the block's rows
+        int r = 0, solves = 0, st = TG_OK;
+        const size_t box = (J.bound_rows > 1 ? b : 0) * (size_t)n;
+        if (n > 0) r = inverse_bounded_stage<TEAM>(core, P, S, lane, solve, S + P.o_f, S + P.o_Dh1, true, J.ridge, J.rcond, J.lo + box, J.hi + box,
+                                                   dt_k, J.max_solves, K, scal, solves, st);
+        const bool answer = solve && st != TG_SINGULAR;
+        const BvlsScratch X = bvls_scratch(scal, nd + (J.ridge > 0.0 ? n : 0), n);
+        if (live) {
+            if (J.U) TG_FOR(i, nu) J.U[bk * nu + i] = answer ? X.z[i] / dt_k : 0.0;
+            if (J.LAM) TG_FOR(c, nc) J.LAM[bk * nc + c] = answer ? X.z[nu + c] : 0.0;
+            if (solve && J.RHO) TG_FOR(i, nd) J.RHO[bk * nd + i] = answer ? K[i * (n + 1) + n] : 0.0;
+            if (J.active) TG_FOR(j, n) J.active[bk * n + j] = answer ? X.bnd[j] : 0;
+            if (lane == 0 && J.solves) J.solves[bk] = solves;
+            if (lane == 0 && J.rank) J.rank[bk] = solve ? r : 0;
+            if (lane == 0 && J.status) J.status[bk] = st;
+        }
+        momenta_and_h();
+        return;
+    }
     if constexpr (LSQ) {
         // the stacked block [A~; sqrt(ridge) I] with (-r0; 0), its rank-revealing solve, rho from r0 and A~
         bool ok = true;

@@ -34,13 +34,16 @@ int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::
 // the equilibrium-search kernel and its parameter-table twin (trepamd_equilibrium.hip, likewise)
 int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the inverse-dynamics kernel and its parameter-table twin (trepamd_inverse.hip, likewise)
-int launch_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+int launch_inverse(int team, bool springs, bool par, int solve, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the frame-kinematics kernel (trepamd_frames.hip, likewise)
 int launch_frames(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::FrameArgs &J, int grid, size_t lds, hipStream_t stream);
 // the tape-measure kernel (trepamd_tape.hip, likewise)
 int launch_tape(int team, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::TapeArgs &J, int grid, size_t lds, hipStream_t stream);
 // the computed-torque kernel and its parameter-table twin (trepamd_dyn_inverse.hip, likewise)
-int launch_dyn_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+int launch_dyn_inverse(int team, bool springs, bool par, int solve, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::DynInverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+int launch_bvls_debug(int team, int per_block, int count, int rows, int cols, int per_team, const double *A, const double *c, const double *lo,
+                      const double *hi, double rcond, int max_solves, double *z, int *active, int *solves, int *rank, int *status, size_t lds,
+                      hipStream_t stream);
 int launch_lsq_debug(int team, int per_block, int count, int rows, int cols, int per_team, const double *A, const double *c, double rcond, double *z,
                      int *rank, int *status, size_t lds, hipStream_t stream);
 }
@@ -1242,6 +1245,42 @@ int tg_system_inverse_dynamics_lsq_lds(const tg_system *sys, int32_t out[4]) {
     return rc;
 }
 
+/* ... and for the kernel whose solve is the bounded least squares (tg_batch_inverse_dynamics_bounded): the pristine stacked block, and
+ * in place of the 4 n doubles the solver's scratch, (nd + n)(n + 1) + 9 n doubles (inverse_bounded_layout). */
+int tg_system_inverse_dynamics_bounded_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::InverseArgs J{};
+    tg::inverse_bounded_layout(sys->H.p.lds_per_team, sys->H.p.nd, sys->H.p.nu, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident inverse-dynamics kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no inverse-dynamics kernel");
+#endif
+    return rc;
+}
+
+// the box of the _bounded entry points and their two additional outputs; lo, hi: host arrays in the host variants (checked entry by
+// entry), device arrays in the _device variants (their contents are the caller's word)
+struct BoundedArgs {
+    const double *lo, *hi;
+    int32_t bound_rows;
+    int32_t *active, *solves;
+};
+
+// what the _bounded entry points refuse on top of the _lsq siblings' refusals (after those: b is not null); host: lo, hi can be read
+static int bounded_check(const tg_batch *b, double ridge, const BoundedArgs &box, bool host) {
+    const int n = b->P.nu + b->P.nc;
+    if (n > b->P.nd && ridge == 0.0)
+        return fail(TG_ERR_INVALID, "more unknowns (nu + nc) than dynamic configs: the bounded problem is not strictly convex without a ridge");
+    if (box.bound_rows != 1 && box.bound_rows != b->batch) return fail(TG_ERR_INVALID, "bound_rows must be 1 or the batch size");
+    if (n > 0 && (!box.lo || !box.hi)) return fail(TG_ERR_INVALID, "null lo or hi");
+    if (host) for (size_t i = 0; i < (size_t)box.bound_rows * n; i++) {
+        if (std::isnan(box.lo[i]) || std::isnan(box.hi[i])) return fail(TG_ERR_INVALID, "a bound is not a number");
+        if (box.lo[i] > box.hi[i]) return fail(TG_ERR_INVALID, "a lower bound above its upper bound");
+        if (box.lo[i] == INFINITY || box.hi[i] == -INFINITY) return fail(TG_ERR_INVALID, "a bound that no finite value meets");
+    }
+    return TG_SUCCESS;
+}
+
 // what the least-squares entry points refuse on top of their siblings' refusals
 static int rcond_check(double rcond) {
     if (!(rcond >= 0.0) || !(rcond < 1.0)) return fail(TG_ERR_INVALID, "rcond must be finite, not negative and below 1");
@@ -1264,12 +1303,14 @@ static int inverse_check(const tg_batch *b, int32_t n_steps, double dt, const do
 // both device entry points: lsq selects the least-squares kernel, its layout, rcond and the rank words
 static int inverse_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles, const double *p0_dev,
                           double ridge, bool lsq, double rcond, double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev, double *H_dev,
-                          int32_t *rank_dev, int32_t *status_dev) {
+                          int32_t *rank_dev, int32_t *status_dev, const BoundedArgs *box = nullptr, bool box_checked = false) {
     if (lsq) if (int rc = rcond_check(rcond)) return rc;
     if (int rc = inverse_check(b, n_steps, dt, Q_dev, ridge, lsq)) return rc;
     if (q_row_stride_doubles < (uint64_t)b->P.nq) return fail(TG_ERR_INVALID, "row stride of Q shorter than a configuration");
+    if (box && !box_checked) if (int rc = bounded_check(b, ridge, *box, false)) return rc;
     int32_t geo[4];
-    if (int rc = lsq ? tg_system_inverse_dynamics_lsq_lds(b->sys, geo) : tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
+    if (int rc = box ? tg_system_inverse_dynamics_bounded_lds(b->sys, geo)
+                     : (lsq ? tg_system_inverse_dynamics_lsq_lds(b->sys, geo) : tg_system_inverse_dynamics_lds(b->sys, geo))) return rc;
     const long long teams = (long long)b->batch * n_steps, per_block = 64 / b->sys->team;
     if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many steps for one launch");
     HIP_TRY(hipSetDevice(b->device));
@@ -1280,14 +1321,19 @@ static int inverse_device(tg_batch *b, int32_t n_steps, double dt, const double 
     A.iters = A.status = nullptr;
     A.n_steps = n_steps; A.dt = dt;
     tg::InverseArgs J{};
-    if (lsq) tg::inverse_lsq_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    if (box) tg::inverse_bounded_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    else if (lsq) tg::inverse_lsq_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
     else tg::inverse_layout(b->P.lds_per_team, b->P.nd, b->P.nu, b->P.nc, J);
+    if (box) {
+        J.lo = box->lo; J.hi = box->hi; J.bound_rows = box->bound_rows; J.active = box->active; J.solves = box->solves;
+        J.max_solves = tg::bvls_max_solves(b->P.nu + b->P.nc);
+    }
     J.rcond = rcond; J.rank = rank_dev;
     J.Q = Q_dev; J.p0 = p0_dev; J.dt_steps = b->dt_host.empty() ? nullptr : b->dt_dev.get();
     J.U = U_dev; J.LAM = LAM_dev; J.P = P_dev; J.RHO = RHO_dev; J.H = H_dev; J.status = status_dev;
     J.dt = dt; J.ridge = ridge; J.q_stride = (size_t)q_row_stride_doubles; J.n_steps = n_steps;
     const bool par = b->par_rows > 0;
-    int rc = tg_detail::launch_inverse(b->sys->team, launch_springs(b), par, lsq, b->d_prog.get(), A, J,
+    int rc = tg_detail::launch_inverse(b->sys->team, launch_springs(b), par, box ? 2 : (lsq ? 1 : 0), b->d_prog.get(), A, J,
                                        tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0},
                                        (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
@@ -1309,23 +1355,34 @@ int tg_batch_inverse_dynamics_lsq_device(tg_batch *b, int32_t n_steps, double dt
 
 // both host entry points
 static int inverse_host(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge, bool lsq, double rcond,
-                        double *U, double *LAM, double *P, double *RHO, double *H, int32_t *rank, int32_t *status) {
+                        double *U, double *LAM, double *P, double *RHO, double *H, int32_t *rank, int32_t *status, const BoundedArgs *box = nullptr) {
     if (lsq) if (int rc = rcond_check(rcond)) return rc;
     if (int rc = inverse_check(b, n_steps, dt, Q_host, ridge, lsq)) return rc;
+    if (box) if (int rc = bounded_check(b, ridge, *box, true)) return rc;
     int32_t geo[4];
-    if (int rc = lsq ? tg_system_inverse_dynamics_lsq_lds(b->sys, geo) : tg_system_inverse_dynamics_lds(b->sys, geo)) return rc;
+    if (int rc = box ? tg_system_inverse_dynamics_bounded_lds(b->sys, geo)
+                     : (lsq ? tg_system_inverse_dynamics_lsq_lds(b->sys, geo) : tg_system_inverse_dynamics_lds(b->sys, geo))) return rc;
     HIP_TRY(hipSetDevice(b->device));
     // staging of this call alone (its size follows n_steps): Q, p0 in; U, LAM, P, RHO, H and the status words out
     const size_t B = (size_t)b->batch, N = (size_t)n_steps, nq = b->P.nq, nd = b->P.nd, nu = b->P.nu, nc = b->P.nc;
     const size_t n_q = B * (N + 1) * nq, n_p0 = B * nd, n_u = B * N * nu, n_l = B * N * nc, n_p = B * (N + 1) * nd, n_r = B * N * nd;
     tg::DeviceBuffer<double> stage;
     tg::DeviceBuffer<int> words;
-    HIP_TRY(stage.ensure(n_q + n_p0 + n_u + n_l + n_p + n_r + n_l));
-    HIP_TRY(words.ensure(2 * B * N));      // (status, then rank)
-    double *q = stage.get(), *p0 = q + n_q, *u = p0 + n_p0, *lam = u + n_u, *p = lam + n_l, *rho = p + n_p, *h = rho + n_r;
+    // (the box and its outputs behind them: lo and hi [bound_rows][n]; solves, then active [B][N][n])
+    const size_t n_box = box ? (size_t)box->bound_rows * (nu + nc) : 0, n_act = box ? B * N * (nu + nc) : 0;
+    HIP_TRY(stage.ensure(n_q + n_p0 + n_u + n_l + n_p + n_r + n_l + 2 * n_box));
+    HIP_TRY(words.ensure(2 * B * N + (box ? B * N + n_act : 0)));      // (status, then rank)
+    double *q = stage.get(), *p0 = q + n_q, *u = p0 + n_p0, *lam = u + n_u, *p = lam + n_l, *rho = p + n_p, *h = rho + n_r, *lo = h + n_l, *hi = lo + n_box;
     HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     if (p0_host && n_p0) HIP_TRY(hipMemcpyAsync(p0, p0_host, n_p0 * sizeof(double), hipMemcpyHostToDevice, b->stream));
-    int rc = inverse_device(b, n_steps, dt, q, nq, p0_host ? p0 : nullptr, ridge, lsq, rcond, u, lam, p, rho, h, lsq ? words.get() + B * N : nullptr, words.get());
+    BoundedArgs dev{};
+    if (box) {
+        dev = BoundedArgs{lo, hi, box->bound_rows, box->active ? words.get() + 3 * B * N : nullptr, box->solves ? words.get() + 2 * B * N : nullptr};
+        if (n_box) HIP_TRY(hipMemcpyAsync(lo, box->lo, n_box * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (n_box) HIP_TRY(hipMemcpyAsync(hi, box->hi, n_box * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    }
+    int rc = inverse_device(b, n_steps, dt, q, nq, p0_host ? p0 : nullptr, ridge, lsq, rcond, u, lam, p, rho, h, lsq ? words.get() + B * N : nullptr, words.get(),
+                            box ? &dev : nullptr, true);
     auto back = [&](void *dst, const void *src, size_t bytes) {
         if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
             rc = fail(TG_ERR_HIP, "copy of the results failed");
@@ -1333,6 +1390,7 @@ static int inverse_host(tg_batch *b, int32_t n_steps, double dt, const double *Q
     back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(P, p, n_p * sizeof(double));
     back(RHO, rho, n_r * sizeof(double)); back(H, h, n_l * sizeof(double)); back(status, words.get(), B * N * sizeof(int));
     if (lsq) back(rank, words.get() + B * N, B * N * sizeof(int));
+    if (box) { back(box->solves, words.get() + 2 * B * N, B * N * sizeof(int)); back(box->active, words.get() + 3 * B * N, n_act * sizeof(int)); }
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
 }
@@ -1345,6 +1403,22 @@ int tg_batch_inverse_dynamics(tg_batch *b, int32_t n_steps, double dt, const dou
 int tg_batch_inverse_dynamics_lsq(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge, double rcond,
                                   double *U, double *LAM, double *P, double *RHO, double *H, int32_t *rank, int32_t *status) {
     return inverse_host(b, n_steps, dt, Q_host, p0_host, ridge, true, rcond, U, LAM, P, RHO, H, rank, status);
+}
+
+int tg_batch_inverse_dynamics_bounded(tg_batch *b, int32_t n_steps, double dt, const double *Q_host, const double *p0_host, double ridge, double rcond,
+                                      const double *lo_host, const double *hi_host, int32_t bound_rows, double *U, double *LAM, double *P, double *RHO,
+                                      double *H, int32_t *active, int32_t *solves, int32_t *rank, int32_t *status) {
+    const BoundedArgs box{lo_host, hi_host, bound_rows, active, solves};
+    return inverse_host(b, n_steps, dt, Q_host, p0_host, ridge, true, rcond, U, LAM, P, RHO, H, rank, status, &box);
+}
+
+int tg_batch_inverse_dynamics_bounded_device(tg_batch *b, int32_t n_steps, double dt, const double *Q_dev, uint64_t q_row_stride_doubles,
+                                             const double *p0_dev, double ridge, double rcond, const double *lo_dev, const double *hi_dev,
+                                             int32_t bound_rows, double *U_dev, double *LAM_dev, double *P_dev, double *RHO_dev, double *H_dev,
+                                             int32_t *active_dev, int32_t *solves_dev, int32_t *rank_dev, int32_t *status_dev) {
+    const BoundedArgs box{lo_dev, hi_dev, bound_rows, active_dev, solves_dev};
+    return inverse_device(b, n_steps, dt, Q_dev, q_row_stride_doubles, p0_dev, ridge, true, rcond, U_dev, LAM_dev, P_dev, RHO_dev, H_dev, rank_dev,
+                          status_dev, &box);
 }
 
 // ---- batched frame kinematics (mvi_frames.hpp): one team per state, one launch
@@ -1607,6 +1681,19 @@ int tg_system_dynamics_inverse_lsq_lds(const tg_system *sys, int32_t out[4]) {
     return rc;
 }
 
+/* ... and for the kernel whose solve is the bounded least squares (tg_batch_dynamics_inverse_bounded): the pristine stacked block, and
+ * in place of the 4 n doubles the solver's scratch, (nd + n)(n + 1) + 9 n doubles (dyn_inverse_bounded_layout). */
+int tg_system_dynamics_inverse_bounded_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::DynInverseArgs J{};
+    tg::dyn_inverse_bounded_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nd, sys->H.p.nu, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident computed-torque kernel", out);
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no computed-torque kernel");
+#endif
+    return rc;
+}
+
 // what both entry points refuse, decided on the host before a device is touched: first what the arguments alone show, then what
 // needs the system (the strides are nq for the host variant; lsq: n > nd needs no ridge)
 static int dyn_inverse_check(const tg_batch *b, int32_t n_states, const double *Q, const double *dQ, const double *ddQ, uint64_t q_stride,
@@ -1630,11 +1717,13 @@ static int dyn_inverse_check(const tg_batch *b, int32_t n_states, const double *
 static int dyn_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
                               uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge, bool lsq,
                               double rcond, double *U_dev, double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev, int32_t *rank_dev,
-                              int32_t *status_dev) {
+                              int32_t *status_dev, const BoundedArgs *box = nullptr, bool box_checked = false) {
     if (lsq) if (int rc = rcond_check(rcond)) return rc;
     if (int rc = dyn_inverse_check(b, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride_doubles, dq_row_stride_doubles, ddq_row_stride_doubles, ridge, lsq)) return rc;
+    if (box && !box_checked) if (int rc = bounded_check(b, ridge, *box, false)) return rc;
     int32_t geo[4];
-    if (int rc = lsq ? tg_system_dynamics_inverse_lsq_lds(b->sys, geo) : tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
+    if (int rc = box ? tg_system_dynamics_inverse_bounded_lds(b->sys, geo)
+                     : (lsq ? tg_system_dynamics_inverse_lsq_lds(b->sys, geo) : tg_system_dynamics_inverse_lds(b->sys, geo))) return rc;
     const long long teams = (long long)b->batch * n_states, per_block = 64 / b->sys->team;
     if ((teams + per_block - 1) / per_block > 0x7fffffffLL) return fail(TG_ERR_INVALID, "too many states for one launch");
     HIP_TRY(hipSetDevice(b->device));
@@ -1645,8 +1734,13 @@ static int dyn_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev
     A.iters = A.status = nullptr;
     A.n_steps = n_states;
     tg::DynInverseArgs J{};
-    if (lsq) tg::dyn_inverse_lsq_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    if (box) tg::dyn_inverse_bounded_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    else if (lsq) tg::dyn_inverse_lsq_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
     else tg::dyn_inverse_layout(b->P.lds_per_team, b->P.nq, b->P.nd, b->P.nu, b->P.nc, J);
+    if (box) {
+        J.lo = box->lo; J.hi = box->hi; J.bound_rows = box->bound_rows; J.active = box->active; J.solves = box->solves;
+        J.max_solves = tg::bvls_max_solves(b->P.nu + b->P.nc);
+    }
     J.rcond = rcond; J.rank = rank_dev;
     J.Q = Q_dev; J.dQ = dQ_dev; J.ddQ = ddQ_dev;
     J.U = U_dev; J.LAM = LAM_dev; J.RHO = RHO_dev; J.TAU = TAU_dev; J.ACC = ACC_dev; J.status = status_dev;
@@ -1655,7 +1749,7 @@ static int dyn_inverse_device(tg_batch *b, int32_t n_states, const double *Q_dev
     const bool par = b->par_rows > 0;
     LaunchTiming timed;
     if (int rc = timing_begin(b, timed)) return rc;
-    int rc = tg_detail::launch_dyn_inverse(b->sys->team, launch_springs(b), par, lsq, b->d_prog.get(), A, J,
+    int rc = tg_detail::launch_dyn_inverse(b->sys->team, launch_springs(b), par, box ? 2 : (lsq ? 1 : 0), b->d_prog.get(), A, J,
                                            tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0},
                                            (int)((teams + per_block - 1) / per_block), (size_t)geo[2], b->stream);
     if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
@@ -1680,12 +1774,15 @@ int tg_batch_dynamics_inverse_lsq_device(tg_batch *b, int32_t n_states, const do
 
 // both host entry points
 static int dyn_inverse_host(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
-                            bool lsq, double rcond, double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *rank, int32_t *status) {
+                            bool lsq, double rcond, double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *rank, int32_t *status,
+                            const BoundedArgs *box = nullptr) {
     if (lsq) if (int rc = rcond_check(rcond)) return rc;
     const uint64_t nq_ = b && b->sys ? (uint64_t)b->sys->H.p.nq : 0;
     if (int rc = dyn_inverse_check(b, n_states, Q_host, dQ_host, ddQ_host, nq_, nq_, nq_, ridge, lsq)) return rc;
+    if (box) if (int rc = bounded_check(b, ridge, *box, true)) return rc;
     int32_t geo[4];
-    if (int rc = lsq ? tg_system_dynamics_inverse_lsq_lds(b->sys, geo) : tg_system_dynamics_inverse_lds(b->sys, geo)) return rc;
+    if (int rc = box ? tg_system_dynamics_inverse_bounded_lds(b->sys, geo)
+                     : (lsq ? tg_system_dynamics_inverse_lsq_lds(b->sys, geo) : tg_system_dynamics_inverse_lds(b->sys, geo))) return rc;
     HIP_TRY(hipSetDevice(b->device));
     // staging of this call alone (its size follows n_states): Q, dQ, ddQ in; the outputs asked for and the status words out
     const size_t rows = (size_t)b->batch * n_states, nq = b->P.nq, nd = b->P.nd, nu = b->P.nu, nc = b->P.nc;
@@ -1693,14 +1790,24 @@ static int dyn_inverse_host(tg_batch *b, int32_t n_states, const double *Q_host,
     const size_t n_a = ACC ? rows * nc : 0;
     tg::DeviceBuffer<double> stage;
     tg::DeviceBuffer<int> words;
-    HIP_TRY(stage.ensure(3 * n_q + n_u + n_l + n_r + n_t + n_a));
-    if (status || rank) HIP_TRY(words.ensure(2 * rows));      // (status, then rank)
+    // (the box and its outputs behind them: lo and hi [bound_rows][n]; solves, then active [rows][n])
+    const size_t n_box = box ? (size_t)box->bound_rows * (nu + nc) : 0, n_act = box ? rows * (nu + nc) : 0;
+    HIP_TRY(stage.ensure(3 * n_q + n_u + n_l + n_r + n_t + n_a + 2 * n_box));
+    if (status || rank || box) HIP_TRY(words.ensure(2 * rows + (box ? rows + n_act : 0)));      // (status, then rank)
     double *q = stage.get(), *dq = q + n_q, *ddq = dq + n_q, *u = ddq + n_q, *lam = u + n_u, *rho = lam + n_l, *tau = rho + n_r, *acc = tau + n_t;
+    double *lo = acc + n_a, *hi = lo + n_box;
+    BoundedArgs dev{};
+    if (box) {
+        dev = BoundedArgs{lo, hi, box->bound_rows, box->active ? words.get() + 3 * rows : nullptr, box->solves ? words.get() + 2 * rows : nullptr};
+        if (n_box) HIP_TRY(hipMemcpyAsync(lo, box->lo, n_box * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (n_box) HIP_TRY(hipMemcpyAsync(hi, box->hi, n_box * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(q, Q_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(dq, dQ_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemcpyAsync(ddq, ddQ_host, n_q * sizeof(double), hipMemcpyHostToDevice, b->stream));
     int rc = dyn_inverse_device(b, n_states, q, nq, dq, nq, ddq, nq, ridge, lsq, rcond, n_u ? u : nullptr, n_l ? lam : nullptr, n_r ? rho : nullptr,
-                                n_t ? tau : nullptr, n_a ? acc : nullptr, rank ? words.get() + rows : nullptr, status ? words.get() : nullptr);
+                                n_t ? tau : nullptr, n_a ? acc : nullptr, rank ? words.get() + rows : nullptr, status ? words.get() : nullptr,
+                                box ? &dev : nullptr, true);
     auto back = [&](void *dst, const void *src, size_t bytes) {
         if (rc == TG_SUCCESS && dst && bytes && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess)
             rc = fail(TG_ERR_HIP, "copy of the results failed");
@@ -1708,6 +1815,7 @@ static int dyn_inverse_host(tg_batch *b, int32_t n_states, const double *Q_host,
     back(U, u, n_u * sizeof(double)); back(LAM, lam, n_l * sizeof(double)); back(RHO, rho, n_r * sizeof(double));
     back(TAU, tau, n_t * sizeof(double)); back(ACC, acc, n_a * sizeof(double)); back(status, words.get(), rows * sizeof(int));
     if (rank) back(rank, words.get() + rows, rows * sizeof(int));
+    if (box) { back(box->solves, words.get() + 2 * rows, rows * sizeof(int)); back(box->active, words.get() + 3 * rows, n_act * sizeof(int)); }
     if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
     return rc;
 }
@@ -1720,6 +1828,71 @@ int tg_batch_dynamics_inverse(tg_batch *b, int32_t n_states, const double *Q_hos
 int tg_batch_dynamics_inverse_lsq(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
                                   double rcond, double *U, double *LAM, double *RHO, double *TAU, double *ACC, int32_t *rank, int32_t *status) {
     return dyn_inverse_host(b, n_states, Q_host, dQ_host, ddQ_host, ridge, true, rcond, U, LAM, RHO, TAU, ACC, rank, status);
+}
+
+int tg_batch_dynamics_inverse_bounded(tg_batch *b, int32_t n_states, const double *Q_host, const double *dQ_host, const double *ddQ_host, double ridge,
+                                      double rcond, const double *lo_host, const double *hi_host, int32_t bound_rows, double *U, double *LAM,
+                                      double *RHO, double *TAU, double *ACC, int32_t *active, int32_t *solves, int32_t *rank, int32_t *status) {
+    const BoundedArgs box{lo_host, hi_host, bound_rows, active, solves};
+    return dyn_inverse_host(b, n_states, Q_host, dQ_host, ddQ_host, ridge, true, rcond, U, LAM, RHO, TAU, ACC, rank, status, &box);
+}
+
+int tg_batch_dynamics_inverse_bounded_device(tg_batch *b, int32_t n_states, const double *Q_dev, uint64_t q_row_stride_doubles, const double *dQ_dev,
+                                             uint64_t dq_row_stride_doubles, const double *ddQ_dev, uint64_t ddq_row_stride_doubles, double ridge,
+                                             double rcond, const double *lo_dev, const double *hi_dev, int32_t bound_rows, double *U_dev,
+                                             double *LAM_dev, double *RHO_dev, double *TAU_dev, double *ACC_dev, int32_t *active_dev,
+                                             int32_t *solves_dev, int32_t *rank_dev, int32_t *status_dev) {
+    const BoundedArgs box{lo_dev, hi_dev, bound_rows, active_dev, solves_dev};
+    return dyn_inverse_device(b, n_states, Q_dev, q_row_stride_doubles, dQ_dev, dq_row_stride_doubles, ddQ_dev, ddq_row_stride_doubles, ridge, true,
+                              rcond, U_dev, LAM_dev, RHO_dev, TAU_dev, ACC_dev, rank_dev, status_dev, &box);
+}
+
+/* Test hook (tests/test_gpu_bounded.py): the bounded least-squares solver of the _bounded kernels (bvls_solve.hpp) alone, as
+ * tg_batch_debug_lsq_solve runs lsq_solve.hpp: `count` problems of one shape with a box each, lo and hi [count][cols] (host), one team of
+ * `team` lanes on each, in one launch.  max_solves: the cap on the solves of a problem (0: the kernels' 3 cols + 3); a problem that
+ * needs more reports TG_NOT_CONVERGED with its last feasible iterate.  z and active [count][cols]; solves, rank (the first solve's),
+ * status [count]; TG_SINGULAR (first solve of rank < cols, or something not finite -- rank 0 then) comes with z = 0, active = 0.  Only
+ * here do teams that need different numbers of solves share a wavefront. */
+int tg_batch_debug_bvls_solve(tg_batch *b, int32_t team, int32_t count, int32_t rows, int32_t cols, const double *A_host, const double *c_host,
+                              const double *lo_host, const double *hi_host, double rcond, int32_t max_solves, double *z_host, int32_t *active_host,
+                              int32_t *solves_host, int32_t *rank_host, int32_t *status_host) {
+    if (!b || !A_host || !c_host || !lo_host || !hi_host || !z_host || !active_host || !solves_host || !rank_host || !status_host)
+        return fail(TG_ERR_INVALID, "null argument");
+    if (team != 1 && team != 4 && team != 16 && team != 64) return fail(TG_ERR_INVALID, "team must be 1, 4, 16 or 64");
+    if (count < 1 || rows < 1 || cols < 1 || rows > 1024 || cols > 1024) return fail(TG_ERR_INVALID, "count, rows and cols must be positive (rows, cols at most 1024)");
+    if (max_solves < 0 || max_solves > 3 * cols + 3) return fail(TG_ERR_INVALID, "max_solves must lie in 0 .. 3 cols + 3");
+    if (int rc = rcond_check(rcond)) return rc;
+    for (size_t i = 0; i < (size_t)count * cols; i++) {
+        if (std::isnan(lo_host[i]) || std::isnan(hi_host[i])) return fail(TG_ERR_INVALID, "a bound is not a number");
+        if (lo_host[i] > hi_host[i]) return fail(TG_ERR_INVALID, "a lower bound above its upper bound");
+        if (lo_host[i] == INFINITY || hi_host[i] == -INFINITY) return fail(TG_ERR_INVALID, "a bound that no finite value meets");
+    }
+    const int per_team = (rows * (cols + 1) + tg::bvls_scratch_doubles(rows, cols) + 1) & ~1;
+    const int per_block = (int)std::min<size_t>(64 / team, (160 * 1024) / (per_team * sizeof(double)));
+    if (per_block < 1) return fail(TG_ERR_UNSUPPORTED, "problem too large for the LDS of a workgroup");
+    const size_t lds = (size_t)per_block * per_team * sizeof(double);
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t cA = (size_t)count * rows * cols, cc = (size_t)count * rows, cz = (size_t)count * cols;
+    tg::DeviceBuffer<double> buf;
+    tg::DeviceBuffer<int> words;
+    HIP_TRY(buf.ensure(cA + cc + 3 * cz));
+    HIP_TRY(words.ensure(3 * (size_t)count + cz));
+    double *dA = buf.get(), *dc = dA + cA, *dlo = dc + cc, *dhi = dlo + cz, *dz = dhi + cz;
+    int *dsolves = words.get(), *drank = dsolves + count, *dstatus = drank + count, *dactive = dstatus + count;
+    HIP_TRY(hipMemcpyAsync(dA, A_host, cA * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dc, c_host, cc * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dlo, lo_host, cz * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(dhi, hi_host, cz * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    int rc = tg_detail::launch_bvls_debug(team, per_block, count, rows, cols, per_team, dA, dc, dlo, dhi, rcond, max_solves ? max_solves : tg::bvls_max_solves(cols),
+                                          dz, dactive, dsolves, drank, dstatus, lds, b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    auto back = [&](void *dst, const void *src, size_t bytes) {
+        if (rc == TG_SUCCESS && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, b->stream) != hipSuccess) rc = fail(TG_ERR_HIP, "copy of the results failed");
+    };
+    back(z_host, dz, cz * sizeof(double)); back(active_host, dactive, cz * sizeof(int)); back(solves_host, dsolves, count * sizeof(int));
+    back(rank_host, drank, count * sizeof(int)); back(status_host, dstatus, count * sizeof(int));
+    if (hipStreamSynchronize(b->stream) != hipSuccess && rc == TG_SUCCESS) rc = fail(TG_ERR_HIP, "hipStreamSynchronize failed");      // (before the staging is freed)
+    return rc;
 }
 
 /* Test hook (tests/test_gpu_min_norm.py): the rank-revealing least-squares solver of the _lsq kernels (lsq_solve.hpp) alone, on `count`

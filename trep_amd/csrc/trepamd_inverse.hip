@@ -12,31 +12,32 @@
 
 namespace {
 
-template <int TEAM, bool SPRINGS, bool PAR, bool LSQ>
+// SOLVE: 0 the augmented image, 1 lsq_solve.hpp's least squares (LSQ), 2 bvls_solve.hpp's bounded least squares (BND)
+template <int TEAM, bool SPRINGS, bool PAR, int SOLVE>
 __global__ __launch_bounds__(64, 1) void k_inverse(const tg::DevProg *__restrict__ Pg, const tg::RunArgs A, const tg::InverseArgs J, const tg::ParTable T) {
     double *lds = tg_lds_base();
     tg::CProg &P = *(tg::CProg *)Pg;
     const int team = threadIdx.x / TEAM, lane = threadIdx.x % TEAM;
     const long long index = (long long)blockIdx.x * (64 / TEAM) + team;
-    tg::run_inverse<TEAM, SPRINGS, PAR, LSQ>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, index);
+    tg::run_inverse<TEAM, SPRINGS, PAR, SOLVE == 1, SOLVE == 2>(P, A, J, T, lds + (size_t)team * J.lds_per_team, lane, index);
 }
 
 }  // namespace
 
 namespace tg_detail {
-int launch_inverse(int team, bool springs, bool par, bool lsq, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
+int launch_inverse(int team, bool springs, bool par, int solve, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream) {
 #if defined(TG_PROFILE)   // the diagnostic build instruments the default kernels only
-    (void)team; (void)springs; (void)par; (void)lsq; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
+    (void)team; (void)springs; (void)par; (void)solve; (void)d_prog; (void)A; (void)J; (void)T; (void)grid; (void)lds; (void)stream;
     return fail(TG_ERR_UNSUPPORTED, "the profiling build has no inverse-dynamics kernel");
 #else
     return dispatch_team(team, [&](auto team_tag) {
         constexpr int TEAM = decltype(team_tag)::value;
-        auto pick = [&](auto lsq_tag) {      // LSQ: the solve is lsq_solve.hpp's (tg_batch_inverse_dynamics_lsq)
-            constexpr bool LSQ = decltype(lsq_tag)::value != 0;
-            return par ? (springs ? &k_inverse<TEAM, true, true, LSQ> : &k_inverse<TEAM, false, true, LSQ>)
-                       : (springs ? &k_inverse<TEAM, true, false, LSQ> : &k_inverse<TEAM, false, false, LSQ>);
+        auto pick = [&](auto solve_tag) {      // 1: tg_batch_inverse_dynamics_lsq, 2: tg_batch_inverse_dynamics_bounded
+            constexpr int SOLVE = decltype(solve_tag)::value;
+            return par ? (springs ? &k_inverse<TEAM, true, true, SOLVE> : &k_inverse<TEAM, false, true, SOLVE>)
+                       : (springs ? &k_inverse<TEAM, true, false, SOLVE> : &k_inverse<TEAM, false, false, SOLVE>);
         };
-        return launch_kernel(lsq ? pick(tg::IntTag<1>()) : pick(tg::IntTag<0>()), grid, lds, stream, d_prog, A, J, T);
+        return launch_kernel(solve == 2 ? pick(tg::IntTag<2>()) : (solve == 1 ? pick(tg::IntTag<1>()) : pick(tg::IntTag<0>())), grid, lds, stream, d_prog, A, J, T);
     });
 #endif
 }

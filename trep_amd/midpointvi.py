@@ -29,6 +29,9 @@ DynamicsInverse = collections.namedtuple("DynamicsInverse", "U lam rho tau acc s
 # ... and what the two inverse questions return with rcond=: the rank of every state or step as one more field
 InverseDynamicsRank = collections.namedtuple("InverseDynamicsRank", "U lam P rho h status rank")
 DynamicsInverseRank = collections.namedtuple("DynamicsInverseRank", "U lam rho tau acc status rank")
+# ... and with bounds=: active (-1 at the lower bound, +1 at the upper, 0 free) and solves (least-squares solves taken) behind rank
+InverseDynamicsBounded = collections.namedtuple("InverseDynamicsBounded", "U lam P rho h status rank active solves")
+DynamicsInverseBounded = collections.namedtuple("DynamicsInverseBounded", "U lam rho tau acc status rank active solves")
 
 
 class BatchMidpointVI(object):
@@ -499,7 +502,43 @@ class BatchMidpointVI(object):
                                              _lib.ptr(ddq), _lib.ptr(lam), status.ctypes.data))
         return ddq, lam, status
 
-    def dynamics_inverse(self, Q, dQ, ddQ, ridge=0.0, rcond=None):
+    def _box(self, bounds):
+        """bounds = (lo, hi) -> contiguous lo, hi [rows][nu + nc] and rows (1 or B): each side None (no bound), a scalar, [n] or [B][n]
+        in (u | lambda) order."""
+        B, n = self._batch, self.nu + self.nc
+        try:
+            lo, hi = bounds
+        except (TypeError, ValueError):
+            raise ValueError("bounds must be a pair (lo, hi)")
+        lo = np.asarray(-np.inf if lo is None else lo, dtype=np.float64)
+        hi = np.asarray(np.inf if hi is None else hi, dtype=np.float64)
+        for a in (lo, hi):
+            if a.ndim > 2 or (a.ndim >= 1 and a.shape[-1] != n) or (a.ndim == 2 and a.shape[0] != B):
+                raise ValueError("expected bounds of shape (), (%d,) or (%d, %d), got %r" % (n, B, n, a.shape))
+        rows = B if (lo.ndim == 2 or hi.ndim == 2) else 1
+        lo = np.ascontiguousarray(np.broadcast_to(lo, (rows, n)), dtype=np.float64)
+        hi = np.ascontiguousarray(np.broadcast_to(hi, (rows, n)), dtype=np.float64)
+        return lo, hi, rows
+
+    def tension_bounds(self, call="inverse_dynamics"):
+        """(lo, hi) [nu + nc] for bounds=: the inputs unbounded and the multiplier of every Distance constraint -- a string --
+        confined to the side on which it PULLS its two points together.  The side depends on the call, because the multipliers enter
+        the two sets of equations with opposite signs (h = |p1 - p2| - d in both): call="dynamics_inverse" (continuous, +Ad' lambda
+        beside the applied forces): lambda <= 0 pulls; call="inverse_dynamics" (discrete, -Dh' lambda; the sign of the integrator's
+        lambda1): lambda >= 0 pulls.  Other constraints stay unbounded."""
+        if call not in ("dynamics_inverse", "inverse_dynamics"):
+            raise ValueError("call must be 'dynamics_inverse' or 'inverse_dynamics', got %r" % (call,))
+        n = self.nu + self.nc
+        lo, hi = np.full(n, -np.inf), np.full(n, np.inf)
+        for c, con in enumerate(self._system.constraints):
+            if type(con).__name__ == "Distance":
+                if call == "dynamics_inverse":
+                    hi[self.nu + c] = 0.0
+                else:
+                    lo[self.nu + c] = 0.0
+        return lo, hi
+
+    def dynamics_inverse(self, Q, dQ, ddQ, ridge=0.0, rcond=None, bounds=None):
         """Computed torque, the inverse of dynamics() (include/trep_amd.h, tg_batch_dynamics_inverse): Q, dQ, ddQ [B][nq] or
         [B][M][nq], kinematic configs included (the kinematic part of ddQ is what dynamics() calls ddQk).  Every state is one
         least-squares solve for (u, lambda), all B x M of them in one launch.  Returns the namedtuple (U [B][M][nu], lam [B][M][nc],
@@ -513,7 +552,16 @@ class BatchMidpointVI(object):
         (tg_batch_dynamics_inverse_lsq): (u, lambda) is numpy.linalg.lstsq's minimum-norm answer on [A; sqrt(ridge) I], so a
         rank-deficient system needs no ridge and nu + nc > nd is accepted without one; pivot columns with a norm <= rcond times the
         first one's count as dependent.  The namedtuple then has rank [B][M] as an additional last field: the number of independent
-        force directions of each state (with ridge > 0: of the stacked block)."""
+        force directions of each state (with ridge > 0: of the stacked block).
+        bounds = (lo, hi) (None: the paths above, unchanged) confines (u | lambda) to a box and answers with the exact minimiser
+        of |rho|^2 + ridge |z|^2 inside it (tg_batch_dynamics_inverse_bounded; an active-set loop around the rank-revealing solve,
+        scipy.optimize.lsq_linear(method="bvls")'s method).  lo and hi are [nu + nc] or [B][nu + nc] in (u | lambda) order, a scalar
+        broadcasts, None on one side or +-inf per variable mean no bound; rcond then defaults to 1e-9.  A state whose unbounded answer
+        lies in the box returns that answer's bits.  rho now holds what inputs and constraints cannot supply WITHIN the box.  The
+        namedtuple has active [B][M][nu + nc] (-1 at the lower bound, +1 at the upper, 0 free; lo == hi reports -1) and solves [B][M]
+        behind rank (the first solve's).  A state whose first solve loses rank has no unique minimiser: TG_SINGULAR -- use a ridge;
+        nu + nc > nd without one is refused (ValueError).  A string (Distance constraint) pulls where lambda <= 0 HERE:
+        tension_bounds("dynamics_inverse")."""
         self.refresh()
         B, nq = self._batch, self.nq
         Q = np.ascontiguousarray(Q, dtype=np.float64)
@@ -533,7 +581,14 @@ class BatchMidpointVI(object):
         U, lam, rho = np.zeros((B, M, self.nu)), np.zeros((B, M, self.nc)), np.zeros((B, M, self.nd))
         tau, acc, status = np.zeros((B, M, self.nd)), np.zeros((B, M, self.nc)), np.zeros((B, M), dtype=np.int32)
         rank = np.zeros((B, M), dtype=np.int32)
-        if rcond is None:
+        if bounds is not None:
+            lo, hi, rows = self._box(bounds)
+            active, solves = np.zeros((B, M, self.nu + self.nc), dtype=np.int32), np.zeros((B, M), dtype=np.int32)
+            rc = self._L.tg_batch_dynamics_inverse_bounded(self._h, M, Q.ctypes.data, dQ.ctypes.data, ddQ.ctypes.data, float(ridge),
+                                                           float(1e-9 if rcond is None else rcond), _lib.ptr(lo), _lib.ptr(hi), rows,
+                                                           _lib.ptr(U), _lib.ptr(lam), _lib.ptr(rho), _lib.ptr(tau), _lib.ptr(acc),
+                                                           _lib.ptr(active), solves.ctypes.data, rank.ctypes.data, status.ctypes.data)
+        elif rcond is None:
             rc = self._L.tg_batch_dynamics_inverse(self._h, M, Q.ctypes.data, dQ.ctypes.data, ddQ.ctypes.data, float(ridge), _lib.ptr(U),
                                                    _lib.ptr(lam), _lib.ptr(rho), _lib.ptr(tau), _lib.ptr(acc), status.ctypes.data)
         else:
@@ -544,23 +599,36 @@ class BatchMidpointVI(object):
             raise ValueError(self._L.tg_last_error().decode())
         _lib.check(rc)
         drop = (lambda a: a[:, 0]) if flat else (lambda a: a)
+        if bounds is not None:
+            return DynamicsInverseBounded(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status), drop(rank), drop(active), drop(solves))
         if rcond is None:
             return DynamicsInverse(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status))
         return DynamicsInverseRank(drop(U), drop(lam), drop(rho), drop(tau), drop(acc), drop(status), drop(rank))
 
     def dynamics_inverse_device(self, n_states, Q_dev, dQ_dev, ddQ_dev, q_row_stride=None, dq_row_stride=None, ddq_row_stride=None,
                                 ridge=0.0, U_dev=None, lam_dev=None, rho_dev=None, tau_dev=None, acc_dev=None, status_dev=None,
-                                rcond=None, rank_dev=None):
+                                rcond=None, rank_dev=None, bounds_dev=None, active_dev=None, solves_dev=None):
         """dynamics_inverse on device pointers, asynchronous on the batch's stream (tg_batch_dynamics_inverse_device).  Row (b, m) is
         read at Q_dev + (b n_states + m) q_row_stride doubles (dQ_dev and ddQ_dev likewise with their own strides): the default nq
         for packed arrays, nX to read the configurations straight from a rollout's X [B][n_states][nX].  The outputs are laid out as
         dynamics_inverse returns them ([B][n_states]...); any may be None.  rcond (None: the path above): the rank-revealing path
-        (tg_batch_dynamics_inverse_lsq_device), with rank_dev int32 [B][n_states] or None."""
+        (tg_batch_dynamics_inverse_lsq_device), with rank_dev int32 [B][n_states] or None.  bounds_dev = (lo_dev, hi_dev, rows): the
+        bounded path (tg_batch_dynamics_inverse_bounded_device) with device arrays [rows][nu + nc], rows 1 or B, whose contents are
+        taken on trust (numbers, lo <= hi); rcond defaults to 1e-9; active_dev int32 [B][n_states][nu + nc], solves_dev int32
+        [B][n_states], each or None."""
         self.refresh()
         nq = self.nq
         strides = (int(nq if q_row_stride is None else q_row_stride), int(nq if dq_row_stride is None else dq_row_stride),
                    int(nq if ddq_row_stride is None else ddq_row_stride))
-        if rcond is None:
+        if bounds_dev is None and (active_dev is not None or solves_dev is not None):
+            raise ValueError("active_dev and solves_dev need bounds_dev")
+        if bounds_dev is not None:
+            lo_dev, hi_dev, rows = bounds_dev
+            rc = self._L.tg_batch_dynamics_inverse_bounded_device(self._h, int(n_states), Q_dev, strides[0], dQ_dev, strides[1], ddQ_dev,
+                                                                  strides[2], float(ridge), float(1e-9 if rcond is None else rcond), lo_dev,
+                                                                  hi_dev, int(rows), U_dev, lam_dev, rho_dev, tau_dev, acc_dev, active_dev,
+                                                                  solves_dev, rank_dev, status_dev)
+        elif rcond is None:
             if rank_dev is not None:
                 raise ValueError("rank_dev needs rcond")
             rc = self._L.tg_batch_dynamics_inverse_device(self._h, int(n_states), Q_dev, strides[0], dQ_dev, strides[1], ddQ_dev, strides[2],
@@ -639,7 +707,7 @@ class BatchMidpointVI(object):
         finally:
             self.set_step_sizes(*(saved if saved is not None else (None,)))
 
-    def inverse_dynamics(self, Q, dt, p0=None, ridge=0.0, rcond=None):
+    def inverse_dynamics(self, Q, dt, p0=None, ridge=0.0, rcond=None, bounds=None):
         """Inputs and constraint forces of given paths (include/trep_amd.h, tg_batch_inverse_dynamics): Q [B][N+1][nq], kinematic
         configs included; `dt` a scalar or one step size per step; p0 [B][nd], optional.  Every step (b, k) is one least-squares
         solve for the impulses (dt_k u_k, lambda_k), all B x N of them in one launch.  Returns the namedtuple (U [B][N][nu], lam
@@ -653,7 +721,14 @@ class BatchMidpointVI(object):
         rcond (a float in [0, 1); None: the path above, unchanged) answers by rank-revealing least squares instead
         (tg_batch_inverse_dynamics_lsq): the impulses are numpy.linalg.lstsq's minimum-norm answer on [A~; sqrt(ridge) I], so a
         rank-deficient system needs no ridge and nu + nc > nd is accepted without one.  The namedtuple then has rank [B][N] as an
-        additional last field (0 for a step that is not solved)."""
+        additional last field (0 for a step that is not solved).
+        bounds = (lo, hi) (None: the paths above, unchanged) confines (u | lambda) to a box, as in dynamics_inverse
+        (tg_batch_inverse_dynamics_bounded): lo and hi are [nu + nc] or [B][nu + nc], a scalar broadcasts, None or +-inf mean no
+        bound; rcond then defaults to 1e-9.  The bounds on u are FORCES, like the U returned (each step scales them by its own dt_k
+        for the impulses it solves for); the bounds on lambda apply to lam as returned.  rho is then the impulse that inputs and
+        constraints cannot supply WITHIN the box: a path that needs a string to push shows it there instead of in a negative
+        tension.  The namedtuple has active [B][N][nu + nc] and solves [B][N] behind rank.  A string (Distance constraint) pulls where
+        lambda >= 0 HERE (the integrator's sign): tension_bounds("inverse_dynamics")."""
         self.refresh()
         B = self._batch
         Q = np.ascontiguousarray(Q, dtype=np.float64)
@@ -665,10 +740,18 @@ class BatchMidpointVI(object):
         U, lam, P = np.zeros((B, N, self.nu)), np.zeros((B, N, self.nc)), np.zeros((B, N + 1, self.nd))
         rho, h, status = np.zeros((B, N, self.nd)), np.zeros((B, N, self.nc)), np.zeros((B, N), dtype=np.int32)
         rank = np.zeros((B, N), dtype=np.int32)
+        if bounds is not None:
+            lo, hi, rows = self._box(bounds)
+            active, solves = np.zeros((B, N, self.nu + self.nc), dtype=np.int32), np.zeros((B, N), dtype=np.int32)
 
         def call():
             p0_ptr = None if p0 is None else p0.ctypes.data
-            if rcond is None:
+            if bounds is not None:
+                rc = self._L.tg_batch_inverse_dynamics_bounded(self._h, N, dt, Q.ctypes.data, p0_ptr, float(ridge),
+                                                               float(1e-9 if rcond is None else rcond), _lib.ptr(lo), _lib.ptr(hi), rows,
+                                                               _lib.ptr(U), _lib.ptr(lam), _lib.ptr(P), _lib.ptr(rho), _lib.ptr(h),
+                                                               _lib.ptr(active), solves.ctypes.data, rank.ctypes.data, status.ctypes.data)
+            elif rcond is None:
                 rc = self._L.tg_batch_inverse_dynamics(self._h, N, dt, Q.ctypes.data, p0_ptr, float(ridge), _lib.ptr(U), _lib.ptr(lam),
                                                        _lib.ptr(P), _lib.ptr(rho), _lib.ptr(h), status.ctypes.data)
             else:
@@ -679,20 +762,31 @@ class BatchMidpointVI(object):
                 raise ValueError(self._L.tg_last_error().decode())
             _lib.check(rc)
         self._with_step_sizes(dts, call)
+        if bounds is not None:
+            return InverseDynamicsBounded(U, lam, P, rho, h, status, rank, active, solves)
         if rcond is None:
             return InverseDynamics(U, lam, P, rho, h, status)
         return InverseDynamicsRank(U, lam, P, rho, h, status, rank)
 
     def inverse_dynamics_device(self, n_steps, dt, Q_dev, q_row_stride=None, p0_dev=None, ridge=0.0, U_dev=None, lam_dev=None,
-                                P_dev=None, rho_dev=None, h_dev=None, status_dev=None, rcond=None, rank_dev=None):
+                                P_dev=None, rho_dev=None, h_dev=None, status_dev=None, rcond=None, rank_dev=None, bounds_dev=None,
+                                active_dev=None, solves_dev=None):
         """inverse_dynamics on device pointers, asynchronous on the batch's stream (tg_batch_inverse_dynamics_device).  Row (b, k) of
         the path is read at Q_dev + (b (n_steps + 1) + k) q_row_stride doubles: the default nq for a packed Q, nX to read the
         configurations straight from a rollout's X [B][N+1][nX].  Any output may be None.  The step sizes are the scalar dt or the
         by-step list the batch has (set_step_sizes).  rcond (None: the path above): the rank-revealing path
-        (tg_batch_inverse_dynamics_lsq_device), with rank_dev int32 [B][n_steps] or None."""
+        (tg_batch_inverse_dynamics_lsq_device), with rank_dev int32 [B][n_steps] or None.  bounds_dev = (lo_dev, hi_dev, rows): the
+        bounded path (tg_batch_inverse_dynamics_bounded_device), as in dynamics_inverse_device; the u bounds are forces."""
         self.refresh()
         stride = int(self.nq if q_row_stride is None else q_row_stride)
-        if rcond is None:
+        if bounds_dev is None and (active_dev is not None or solves_dev is not None):
+            raise ValueError("active_dev and solves_dev need bounds_dev")
+        if bounds_dev is not None:
+            lo_dev, hi_dev, rows = bounds_dev
+            rc = self._L.tg_batch_inverse_dynamics_bounded_device(self._h, int(n_steps), float(dt), Q_dev, stride, p0_dev, float(ridge),
+                                                                  float(1e-9 if rcond is None else rcond), lo_dev, hi_dev, int(rows), U_dev,
+                                                                  lam_dev, P_dev, rho_dev, h_dev, active_dev, solves_dev, rank_dev, status_dev)
+        elif rcond is None:
             if rank_dev is not None:
                 raise ValueError("rank_dev needs rcond")
             rc = self._L.tg_batch_inverse_dynamics_device(self._h, int(n_steps), float(dt), Q_dev, stride, p0_dev, float(ridge), U_dev, lam_dev,
