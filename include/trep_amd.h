@@ -312,7 +312,9 @@ int tg_batch_debug_newton_solve(tg_batch *b, int32_t n_mats, int32_t skip_struct
  * with helper waves), bits 8-15 fb_n: the joints of the floating base's translational prefix whose terms the loaded rollout kernel
  * takes in closed form, as that library reports it (0: none, compiled out, or no specialised library), bits 16-23
  * tr_n: the joints of translation runs whose world poses the loaded rollout kernel stores directly instead of sweeping them, as that
- * library reports it (0 likewise).  (Modes: 0 rollout/step, 1 calc_p2, 2 calc_f, 3 deriv1, 4 deriv2z, 5.. dynamics.) */
+ * library reports it (0 likewise), bit 24: the loaded rollout kernel takes the poses of a step's first evaluation behind
+ * the step edge from the q2 poses of the converged evaluation before it, bits 25-28 the joints without a q2 twin whose q2 pose it keeps
+ * for that (carried poses; 0 likewise).  (Modes: 0 rollout/step, 1 calc_p2, 2 calc_f, 3 deriv1, 4 deriv2z, 5.. dynamics.) */
 int64_t tg_system_spec_header(const tg_system *sys, char *buf, uint64_t capacity);
 uint64_t tg_system_spec_key(const tg_system *sys);
 int tg_batch_load_specialized(tg_batch *b, const char *library_path);

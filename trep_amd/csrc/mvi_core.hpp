@@ -150,6 +150,10 @@ template <class P> struct tg_static_fb<P, typename std::enable_if<(P::fb_on >= 0
 template <class P, class = void> struct tg_static_tr { static constexpr bool value = false; };
 template <class P> struct tg_static_tr<P, typename std::enable_if<(P::tr_on >= 0)>::type> { static constexpr bool value = P::tr_on != 0 && tg_static_sweep<P>::value && P::tab_ok != 0; };
 
+// ... and the carried poses of a step's first evaluation behind the step edge (program.hpp, PoseCarry: cells only a header with them has)
+template <class P, class = void> struct tg_static_carry { static constexpr bool value = false; static constexpr int n = 0; };
+template <class P> struct tg_static_carry<P, typename std::enable_if<(P::pc_on >= 0)>::type> { static constexpr bool value = P::pc_on != 0 && tg_static_tr<P>::value && tg_static_wev<P>::value; static constexpr int n = value ? P::pc_n : 0; };
+
 enum { MODE_ROLLOUT = 0, MODE_CALC_P2 = 1, MODE_CALC_F = 2, MODE_DERIV1 = 3, MODE_DERIV2Z = 4, MODE_DYNAMICS = 5, MODE_DYN_DERIV1 = 6, MODE_ENERGY = 7, MODE_LAGRANGIAN = 8 };
 
 struct RunArgs {
@@ -641,7 +645,9 @@ struct Core {
     // through the same phases: the second pose set lives in the W area and its sin/cos in the J area (both dead until
     // the Jacobians / prefix velocities are formed), every chain lane carries the two row recurrences side by side
     // (two independent FMA chains per lane), and the local-transform pass covers 2 x 12 x n_joints entries.
-    TG_HD void pose_sweep_dual(bool on, bool rollout_lists) {
+    // CARRYL (eval_world of a system with carried poses alone; program.hpp, PoseCarry): the (set 1, joint) items of the joints without a q2 twin
+    // run on the idle lanes behind the rollout's list -- every other instantiation is the text it was
+    template <bool CARRYL = false> TG_HD void pose_sweep_dual(bool on, bool rollout_lists) {
         const int sjn = rollout_lists ? P.n_sj : 2 * P.n_joints;     // (what init_sweep_schedule filled jck from)
         double *sc = S + P.o_sc, *sc2 = S + P.o_J, *G = S + P.o_G, *G2 = S + P.o_W;
         const int nj = P.n_joints;
@@ -676,18 +682,21 @@ struct Core {
 #pragma unroll
                 for (int e = 0; e < 12; e++) pr[u][e] = src[e];
                 if constexpr (TR) { if (rollout_lists) trw[u] = P.tr_sj[lane + u * TEAM < sjn ? lane + u * TEAM : 0]; }
+                if constexpr (CARRYL) { if (lane + u * TEAM >= sjn) trw[u] = 0; }      // (the items behind the list copy no row)
             }
             if (on) {
 #pragma unroll
                 for (int u = 0; u < 2; u++) {
                     const int idx = lane + u * TEAM;
-                    if (u * TEAM < sjn && idx < sjn) {
+                    if (u * TEAM < sjn && idx < (CARRYL ? sjn + tg_static_carry<typename std::remove_cv<PROG>::type>::n : sjn)) {
                         const bool second = (jck[u] >> 28) != 0;
                         const int j = (jck[u] >> 16) & 0xFFF, kind = (jck[u] >> 12) & 0xF;
                         const double x = qval(second ? dsB : dsA, jck[u] & 0xFFF);
                         const bool rotary = kind >= TG_RX;
                         const int a = rotary ? kind - TG_RX : kind - TG_TX, b = a == 2 ? 0 : a + 1, c = a == 0 ? 2 : a - 1;
                         double *g = (second ? G2 : G) + 12 * j;
+                        // (pose_carry_pass holds a second copy of row_t and of the prismatic form below for the run joints a kinematic config moves:
+                        // change one, change the other)
                         // translation column of row l: v, or for a run joint's copied row the config itself (one instruction stream: selects)
                         // (tr_rows: the rows some item of the plan copies at all; a row outside it costs neither the config's read nor the select)
                         auto row_t = [&](int l, double v) {
@@ -1312,7 +1321,62 @@ struct Core {
             }      // (pairwise sums -- a shorter dependent chain -- measured: no difference)
         }
     }
-    TG_HD void eval_world(bool on) {
+    // ---- carried poses (program.hpp, PoseCarry): the pose pass of the first evaluation behind a step edge ----
+    // Every dynamic config has
+    // q1 = q2 = the converged q2 of the step before, the midpoint 0.5 * (b + b) is b, so both poses of a joint no kinematic config moves
+    // are, bit for bit, the q2 world pose that evaluation's sweep left in G2 -- nothing has written a listed joint's record there since:
+    // E3 .. E6 write the end points, the twist / composite records of the J area and the body entries BEHIND the poses (o_W + 12
+    // n_joints), the step edge writes q1, q2, p1, dq, u, Dh1, and no Newton matrix or solve follows a converged evaluation.  The lane of
+    // a (midpoint, joint) item copies the record, the lane of a (q2, joint) item has nothing to do, the lanes of the run joints a
+    // kinematic config moves store their closed forms as ever (the pass's own expressions), and no chain round runs.
+    // THE CLOSED FORM BELOW IS A SECOND COPY of pose_sweep_dual's prismatic branch and its row_t (kept apart so that every other
+    // instantiation of that pass stays the text it was: docs/LOG.md, "carried into the next step"): change one, change the other.
+    TG_HD void pose_carry_pass(bool on) {
+        typedef typename std::remove_cv<PROG>::type SP;
+        static_assert((SP::o_G & 1) == 0 && (SP::o_W & 1) == 0, "carried poses: the 16-byte copy G2 -> G needs both pose areas on an even double");
+        double *G = S + P.o_G, *G2 = S + P.o_W;
+        const int l = tg_opaque(lane);
+        if (on && l < SP::n_sj) {
+            const int w = jck[0];
+            const bool second = (w >> 28) != 0;
+            const int j = (w >> 16) & 0xFFF;
+            if (((l < 32 ? SP::pc_kin_0 : SP::pc_kin_1) >> (l & 31)) & 1) {
+                const int a = ((w >> 12) & 0xF) - TG_TX, b = a == 2 ? 0 : a + 1, c = a == 0 ? 2 : a - 1;
+                const double x = qval(second ? dsB : dsA, w & 0xFFF);
+                const double *src = P.tr_prm + 12 * (size_t)j;
+                const int tw = P.tr_sj[l];
+                double *g = (second ? G2 : G) + 12 * j;
+#pragma unroll
+                for (int r = 0; r < 3; r++) {
+                    const double A_ = src[4 * r], B_ = src[4 * r + 1], C_ = src[4 * r + 2], D_ = src[4 * r + 3];
+                    double t = fma(A_, x, D_);
+                    if ((SP::tr_rows >> r) & 1) { const double e = qval(second ? dsB : dsA, (tw >> (8 * r)) & 0xFF); t = (tw >> (24 + r)) & 1 ? e : t; }
+                    g[4 * r + a] = A_; g[4 * r + b] = B_; g[4 * r + c] = C_; g[4 * r + 3] = t;
+                }
+            } else if (!second) {
+                typedef double tg_d2 __attribute__((ext_vector_type(2)));
+                const tg_d2 *from = reinterpret_cast<const tg_d2 *>(G2 + 12 * j);
+                tg_d2 *to = reinterpret_cast<tg_d2 *>(G + 12 * j);
+                tg_d2 v[6];
+#pragma unroll
+                for (int e = 0; e < 6; e++) v[e] = from[e];
+#pragma unroll
+                for (int e = 0; e < 6; e++) to[e] = v[e];
+            }
+        }
+        TG_RSYNC();
+        TG_STAMP(5);
+        TG_STAMP(15);
+    }
+    // the joints without a q2 twin: their (set 1, joint) items on the idle lanes behind the rollout's list, first trip (run_trajectory,
+    // behind init_sweep_schedule)
+    TG_HD void init_carry_lanes() {
+        typedef typename std::remove_cv<PROG>::type SP;
+        static_assert(TEAM == 64 && SP::n_sj + SP::pc_n <= TEAM && SP::pc_n <= kPoseCarryMax, "carried poses: the items without a q2 twin fit the first trip");
+        const int l = tg_opaque(lane);
+        if (l >= SP::n_sj && l < SP::n_sj + SP::pc_n) jck[0] = SP::pc_item[l - SP::n_sj];
+    }
+    TG_HD void eval_world(bool on, bool carry = false) {
         typedef typename std::remove_cv<PROG>::type SP;
         constexpr bool FB = tg_static_fb<SP>::value;      // translational prefix: shared list record, closed-form matrix entries
         constexpr int nd = SP::nd, NB = SP::n_bodies, NG = SP::n_cgroups, MAXD = FB ? SP::fb_depth : SP::wev_depth;
@@ -1343,7 +1407,8 @@ struct Core {
             TG_RSYNC();
         }
         TG_STAMP(0);
-        pose_sweep_dual(on, true);
+        if constexpr (tg_static_carry<SP>::value) { if (carry) pose_carry_pass(on); else pose_sweep_dual<true>(on, true); }
+        else pose_sweep_dual(on, true);
         TG_STAMP(1);
         const double *G = S + P.o_G, *G2 = S + P.o_W;
         // per-body world entries: behind the q2 poses in the W area (with the dead body-velocity / gravity vectors that follow it) -- the body
@@ -4476,6 +4541,9 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
     core.wave = wave; core.nw = nw;
     core.d1_compact = MODE == MODE_DERIV1 && P.a_ok != 0;
     if (wave == 0) core.init_sweep_schedule(MODE == MODE_ROLLOUT);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (MODE == MODE_ROLLOUT && TEAM == 64 && !SPRINGS && tg_static_carry<typename std::remove_cv<PROG>::type>::value) core.init_carry_lanes();
+#endif
 #if defined(TG_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
     core.prof_last = (long long)__builtin_amdgcn_s_memtime();
     const long long prof_rt0 = (long long)__builtin_amdgcn_s_memrealtime();     // 100 MHz wall clock: total cycles / these ticks = the shader clock
@@ -4699,7 +4767,13 @@ TG_HD void run_trajectory(PROG &P0, ARGS &A0, double *S, int lane, int traj, int
             PROG &P = tg_rebind(P0);
             const int nd = P.nd, nc = P.nc;
 #if defined(__HIP_DEVICE_COMPILE__)
-            if constexpr (TEAM == 64 && !SPRINGS && tg_static_wev<typename std::remove_cv<PROG>::type>::value) { core.wev_on = true; core.pk_image = PIVOT == 0; core.eval_world(!done); }
+            if constexpr (TEAM == 64 && !SPRINGS && tg_static_wev<typename std::remove_cv<PROG>::type>::value) {
+                core.wev_on = true; core.pk_image = PIVOT == 0;
+                // (carried poses: the first evaluation of a step the edge has set up -- a live, converged, full-wave team on the open-loop
+                // reference path, so !done holds here -- takes its poses from the converged evaluation before it)
+                if constexpr (tg_static_carry<typename std::remove_cv<PROG>::type>::value) core.eval_world(!done, edged && iterations == 0);
+                else core.eval_world(!done);
+            }
             else if (core.dual_ok()) { if (P.tab_ok) core.eval_both_tab(!done); else core.eval_both(!done); }
             else
 #endif

@@ -31,6 +31,21 @@ template <class SP> constexpr int cmp_stride() {
     return stride;
 }
 
+// Carried poses (schedule.hpp, pose_carry): whether the rollout kernel of a system may take the midpoint and q2 poses of
+// a step's first evaluation behind the step edge from the q2 poses the converged evaluation before it left in LDS, and what it needs for
+// it.  NOT a member of DevProg: the generic kernels never read it, and a specialisation header gains its cells (pc_on, pc_n, pc_kin_0 /
+// pc_kin_1, pc_item) only where it is on -- the header of every other system stays the text it was, and with it its kernels.
+//   item[i]: the (set 1, joint) item, in sj_list's layout, of a joint whose midpoint pose is read but whose q2 pose is not (no q2 twin in
+//            sj_list): the local-transform pass gives it to lane n_sj + i, so that the chain step which already runs over it in pose set 1
+//            leaves its q2 world pose in G2
+//   kin:     bit l set when item l of sj_list is a joint that a kinematic config moves (a translation-run joint, by the conditions)
+constexpr int kPoseCarryMax = 8;
+struct PoseCarry {
+    int on = 0, n = 0;
+    int item[kPoseCarryMax] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned kin[2] = {0u, 0u};
+};
+
 }  // namespace tg
 
 // A plain host compiler (the emulation of the kernels under tests/) also gets the compiler, whose HostProgram drives the emulated

@@ -41,6 +41,7 @@ struct HostProgram {
     // ancestor-or-self; -1: fixed to the world) and the constant 3 x 4 transform from it
     std::vector<int> frame_anchor;
     std::vector<double> frame_offset;   // [n_frames][12]
+    PoseCarry carry;      // carried poses of the rollout kernel (program.hpp), host side and specialisation header only
     // all tables packed into two pools, in the order of the field list; bind() points a DevProg's table pointers into (copies of) them
     std::vector<int> ipool;
     std::vector<double> dpool;
@@ -120,7 +121,7 @@ struct ScheduleBuilder {
     void counts_and_step_layout(), sweep_lists_and_plan(), layout_pose_union_and_deriv1();
     void body_chunks(), helper_wave_lists(), layout_derivatives();
     void composite_form(), floating_base_tables(const std::vector<std::vector<int>> &lists), world_eval();
-    void structured_solve(), translation_runs();
+    void structured_solve(), translation_runs(), pose_carry();
 };
 
 // constraint end points (unique frames)
@@ -1035,6 +1036,47 @@ inline void ScheduleBuilder::translation_runs() {
     }
     if (H.tr_joint.empty()) { H.tr_joint.push_back(0); H.tr_src.assign(3, -1); H.tr_const.assign(3, 0.0); }
 }
+// carried poses (HostProgram::carry, program.hpp): at the first evaluation behind a step edge every dynamic config has q1 = q2 = the converged
+// q2 of the step before, so the midpoint pose and the q2 pose of a joint no kinematic config moves ARE the q2 world pose that evaluation left
+// in G2.  On when the rollout's second sweep plan is (tr_on), every listed joint a kinematic config moves is a translation-run joint (their
+// world poses are closed forms of the local-transform pass: no chain reads a moved pose), the listed joints without a q2 twin -- a body
+// below, no constraint end point -- fit the idle lanes of the pass's first trip, and the chain of each is one the second plan already
+// sweeps in pose set 1 over that joint (the schedule words hold one length per chain, for both sets): no pass, round or LDS is added.
+inline void ScheduleBuilder::pose_carry() {
+    PoseCarry &C = H.carry;
+    C = PoseCarry();
+    if (!P.tr_on || P.n_sj > 64) return;
+    std::vector<int> run(nj, 0), moved(nj, 0);
+    for (int i = 0; i < P.tr_n; i++) run[H.tr_joint[i]] = 1;
+    for (int j = 0; j < nj; j++) moved[j] = (H.j_cfg[j] >= nd ? 1 : 0) | (H.j_parent[j] >= 0 ? moved[H.j_parent[j]] : 0);      // (parents come first)
+    for (int n = 0; n < P.n_sj; n++) {
+        const int j = (H.sj_list[n] >> 16) & 0xFFF;
+        if (!moved[j]) continue;
+        if (!run[j]) { C = PoseCarry(); return; }      // a chain would read a pose that moves across the step boundary
+        C.kin[n >> 5] |= 1u << (n & 31);
+    }
+    int n = 0, item[kPoseCarryMax];
+    for (int k = 0; k < nj; k++) {
+        if ((pose_need[k] & 3) != 1) continue;
+        if (n == kPoseCarryMax || moved[k] || run[k]) { C = PoseCarry(); return; }
+        // the chain of joint k, its round and slot; the trimmed chain of the second plan and its instance in pose set 1
+        bool swept = false;
+        for (int r = 0; r < P.n_rounds && !swept; r++)
+            for (int c = H.round_off[r]; c < H.round_off[r + 1] && !swept; c++) {
+                if (k < H.ch_first[c] || k >= H.ch_first[c] + H.ch_len[c]) continue;
+                const int slot = c - H.round_off[r];
+                if (slot >= 16) break;
+                const int w = H.tr_sched[2 * (size_t)(16 * r + slot)], first = (w & 0xFFFF) / 12, len = w >> 16;
+                if (k < first || k >= first + len) break;
+                for (int i = 0; i < 20; i++) if (P.tr_inst[20 * r + i] == (slot | (1 << 8) | (1 << 9))) swept = true;
+            }
+        if (!swept) { C = PoseCarry(); return; }
+        item[n++] = H.j_cfg[k] | (H.j_kind[k] << 12) | (k << 16) | (1 << 28);
+    }
+    if (P.n_sj + n > 64) { C = PoseCarry(); return; }
+    C.on = 1; C.n = n;
+    for (int i = 0; i < n; i++) C.item[i] = item[i];
+}
 }  // namespace detail
 
 // A list of passes over one ScheduleBuilder: each is one plan of the schedule and reads what the passes before it left in the builder.
@@ -1046,7 +1088,7 @@ inline HostProgram build_program(const tg_system_desc *d) {
     b.body_chunks(); b.helper_wave_lists(); b.layout_derivatives();      // derivative kernels
     // the specialised rollout kernels' plans: the world-frame evaluation needs the composite form and holds the floating-base prefix, the
     // solve plan appends to lds_per_team, the translation runs read sw_ok, wev_ok, pose_need and lds_per_team
-    b.composite_form(); b.world_eval(); b.structured_solve(); b.translation_runs();
+    b.composite_form(); b.world_eval(); b.structured_solve(); b.translation_runs(); b.pose_carry();
     b.H.pack();
     return std::move(b.H);
 }
@@ -1141,6 +1183,15 @@ inline void emit_spec_header(const HostProgram &H, std::string &out) {
 #undef TG_F_INT
 #undef TG_F_ARRAY
 #undef TG_F_TABLE
+    // NOTE for whoever adds the next field: the cells below are NOT in devprog_fields.def, so a header's set of cells depends on the
+    // system -- a carrying system has pc_*, every other header has not -- and the kernels find them by SFINAE (mvi_core.hpp,
+    // tg_static_carry, as tg_static_tr finds tr_on), never by name alone.  A field every kernel reads belongs in the list, above.
+    if (H.carry.on) {      // (program.hpp, PoseCarry: only where it is on -- every other header is the text it was)
+        const PoseCarry &C = H.carry;
+        out += "    static constexpr int pc_on = 1;\n    static constexpr int pc_n = " + std::to_string(C.n) + ";\n";
+        out += "    static constexpr int pc_kin_0 = " + std::to_string((int)C.kin[0]) + ";\n    static constexpr int pc_kin_1 = " + std::to_string((int)C.kin[1]) + ";\n";
+        detail::emit_spec_array(out, "int", "pc_item", C.item, kPoseCarryMax);
+    }
     out += "};\n";
 }
 

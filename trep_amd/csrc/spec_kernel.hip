@@ -173,6 +173,11 @@ int tg_spec_fb_n(void) { return tg::tg_static_fb<SpecProg>::value ? SpecProg::fb
 // joints of translation runs whose world poses THIS library's rollout kernel stores directly instead of sweeping them (mvi_core.hpp,
 // tg_static_tr: the plan's run joints, 0 when the kernel follows the first sweep plan)
 int tg_spec_tr_n(void) { return tg::tg_static_tr<SpecProg>::value ? SpecProg::tr_n : 0; }
+// carried poses of THIS library's rollout kernels (mvi_core.hpp, tg_static_carry): bit 0 = a step's first evaluation behind the step edge
+// copies the q2 poses instead of sweeping, bits 1.. = the joints without a q2 twin the local-transform pass has on its spare lanes
+// (This is what the library was COMPILED with -- the plan's cells, tg_static_carry -- not a record of what ran: a carried evaluation also
+// needs a full-wave team without springs on the step-edge path, i.e. the open-loop reference predictor, at a step that is not a launch's first.)
+int tg_spec_pose_carry(void) { return tg::tg_static_carry<SpecProg>::value ? 1 | (tg::tg_static_carry<SpecProg>::n << 1) : 0; }
 // bit m set: kernel mode m (tg::MODE_*) has a specialised instantiation in this library
 int tg_spec_modes(void) {
     int m = 1 << tg::MODE_ROLLOUT;

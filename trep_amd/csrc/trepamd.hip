@@ -128,7 +128,7 @@ struct tg_batch {
     double *io_dev = nullptr;          // the same block as the device sees it
     size_t io_in = 0, io_out = 0;      // doubles in the input / output part
     bool mirror_valid = false;
-    int spec_modes = 0, spec_waves = 1, spec_fb_n = 0, spec_tr_n = 0;
+    int spec_modes = 0, spec_waves = 1, spec_fb_n = 0, spec_tr_n = 0, spec_pose_carry = 0;
     std::string spec_path;
     tg::DeviceBuffer<int> d_ints;
     tg::DeviceBuffer<double> d_dbls;
@@ -2127,6 +2127,8 @@ int tg_batch_load_specialized(tg_batch *b, const char *library_path) {
     b->spec_fb_n = fb_fn ? fb_fn() : 0;
     auto tr_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_tr_n"));
     b->spec_tr_n = tr_fn ? tr_fn() : 0;
+    auto pc_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_pose_carry"));
+    b->spec_pose_carry = pc_fn ? pc_fn() : 0;
     auto par_fn = reinterpret_cast<int (*)(int, const tg::RunArgs *, tg::RunArgs *, int, size_t, void *, const double *, int, int)>(dlsym(h, "tg_spec_launch_par"));
     auto par_modes_fn = reinterpret_cast<int (*)(void)>(dlsym(h, "tg_spec_par_modes"));
     b->spec_launch_par = par_modes_fn ? par_fn : nullptr;
@@ -2178,13 +2180,14 @@ int tg_batch_debug_newton_solve(tg_batch *b, int32_t n_mats, int32_t skip_struct
  * such launches; out[5] pivot rule; out[6] team size; out[7] bits 0-7 wavefronts per trajectory of the loaded library's derivative kernels,
  * bits 8-15 the joints of the translational prefix its rollout kernel has closed forms for, as the library itself reports them
  * (tg_spec_fb_n; 0: none, compiled out, or no library), bits 16-23 the joints of translation runs whose world poses its rollout
- * kernel stores directly (tg_spec_tr_n; likewise). */
+ * kernel stores directly (tg_spec_tr_n; likewise), bit 24 its rollout kernel carries the q2 poses into a step's first evaluation behind the
+ * step edge, bits 25-28 the joints without a q2 twin that needs (tg_spec_pose_carry; likewise). */
 int tg_batch_info(const tg_batch *b, int32_t out[8]) {
     if (!b || !out) return fail(TG_ERR_INVALID, "null argument");
     out[0] = b->spec_launch ? b->spec_modes : 0;
     for (int spec = 0; spec < 2; spec++) { out[2 - spec] = (int32_t)b->launched[0][spec].modes; out[4 - spec] = (int32_t)std::min<long long>(b->launched[0][spec].n, 0x7fffffff); }
     out[5] = b->exact_pivot; out[6] = b->sys->team; out[7] = b->spec_launch ? b->spec_waves : 1;
-    if (b->spec_launch) out[7] |= (b->spec_fb_n << 8) | ((b->spec_tr_n & 0xFF) << 16);
+    if (b->spec_launch) out[7] |= (b->spec_fb_n << 8) | ((b->spec_tr_n & 0xFF) << 16) | ((b->spec_pose_carry & 0x1F) << 24);
     return TG_SUCCESS;
 }
 

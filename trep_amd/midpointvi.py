@@ -200,6 +200,9 @@ class BatchMidpointVI(object):
         d["fb_n"] = (int(kout[7]) >> 8) & 0xFF
         # joints of translation runs whose world poses the loaded rollout kernel stores directly (likewise)
         d["tr_n"] = (int(kout[7]) >> 16) & 0xFF
+        # the loaded rollout kernel carries the q2 poses into a step's first evaluation behind the step edge; the joints without a q2 twin (likewise)
+        d["pose_carry"] = bool((int(kout[7]) >> 24) & 1)
+        d["n_carry"] = (int(kout[7]) >> 25) & 0xF
         return d
 
     MODES = {"rollout": 0, "calc_p2": 1, "calc_f": 2, "deriv1": 3, "deriv2z": 4}
@@ -250,6 +253,8 @@ class BatchMidpointVI(object):
         loaded, `spec_launched` / `generic_launched` = mode names that have actually gone through a specialised / generic
         kernel, and the launch counts; `helper_waves` = wavefronts per trajectory in the loaded library's derivative kernels; `fb_n` = joints of the
         translational prefix the loaded rollout kernel has closed forms for; `tr_n` = joints of translation runs whose world poses it stores directly;
+        `pose_carry` / `n_carry` = it was compiled to carry the q2 poses into a step's first evaluation behind the step edge / the joints without a q2 twin that needs
+        (what the library holds, not a record that a carried evaluation ran: that takes the step-edge path);
         `spec_library` the loaded file.  The par_* keys: the same for the per-trajectory parameter kernels (set_parameters),
         over all kernel modes (ALL_MODES), with `par_spec_launch_mask` / `par_generic_launch_mask` the raw mode bits as
         `spec_launch_mask` / `generic_launch_mask` are for the default kernels (bit 9: the projection, bit 10: the equilibrium search,
@@ -263,7 +268,8 @@ class BatchMidpointVI(object):
         return {"spec_modes": names(out[0]), "spec_launched": names(out[1]), "generic_launched": names(out[2]),
                 "spec_launch_mask": int(out[1]), "generic_launch_mask": int(out[2]),
                 "spec_launches": int(out[3]), "generic_launches": int(out[4]), "exact_pivot": bool(out[5]), "team": int(out[6]),
-                "helper_waves": int(out[7]) & 0xFF, "fb_n": (int(out[7]) >> 8) & 0xFF, "tr_n": (int(out[7]) >> 16) & 0xFF, "spec_library": self._specialized,
+                "helper_waves": int(out[7]) & 0xFF, "fb_n": (int(out[7]) >> 8) & 0xFF, "tr_n": (int(out[7]) >> 16) & 0xFF,
+                "pose_carry": bool((int(out[7]) >> 24) & 1), "n_carry": (int(out[7]) >> 25) & 0xF, "spec_library": self._specialized,
                 # per-trajectory parameter kernels (set_parameters); the keys above count the default kernels only
                 "par_spec_modes": every(par[0]), "par_spec_launched": every(par[1]), "par_generic_launched": every(par[2]),
                 "par_spec_launch_mask": int(par[1]), "par_generic_launch_mask": int(par[2]), "par_spec_launches": int(par[3]), "par_generic_launches": int(par[4]), "parameter_rows": int(par[5]),
