@@ -481,6 +481,42 @@ int tg_batch_minimize_potential_device(tg_batch *b, const double *q_dev, const i
                                        int32_t max_iterations, double *q_out_dev, double *mu_out_dev, double *v_out_dev,
                                        int32_t *iterations_out_dev, int32_t *status_out_dev);
 
+/* ---- batched normal modes ------------------------------------------------------------------------------------------
+ * The small-oscillation eigenproblem K phi = omega^2 M phi on the tangent space of the constraints, for every pose of the batch in
+ * one launch (tests/normal_modes_reference.py is the specification).  free [nq] (HOST memory in both variants: it is the launch's,
+ * nq words, and is checked before a device is touched), NULL: every dynamic config; a kinematic config is never free.  n_free = the
+ * number of free configs.  Per pose, over the free configs F:
+ *   1. at rest (dq = 0): V_q, V_qq[F, F], h, D = Dh[:, F], M = L_ddqddq[F, F]; a parameter table is honoured as in the equilibrium
+ *      search (its twin is mode 15 in tg_batch_par_info, the default kernel mode 15 in tg_batch_info);
+ *   2. mu [B][nc] as supplied (mu_in, for example what tg_batch_minimize_potential returned), or (NULL) the minimum-norm minimiser
+ *      of |V_q[F] + D' mu| by column-pivoted QR under rcond; residual = |V_q[F] + D' mu|inf says how far the pose is from rest;
+ *   3. K = V_qq[F, F] + sum_c mu_c h_c,qq[F, F];
+ *   4. column-pivoted Householder QR of D' with the identity carried along; r = the rank under rcond, Z = the last nm = n_free - r
+ *      columns of Q (the identity without constraints);
+ *   5. M_r = Z'MZ and K_r = Z'KZ, symmetrised; unpivoted Cholesky M_r = LL', a pivot that is not > 0 ends the pose with TG_SINGULAR;
+ *      C = L^-1 K_r L^-T, symmetrised;
+ *   6. cyclic Jacobi on C in the round-robin ordering (csrc/sym_eig.hpp), sweeps until max |off-diagonal| <= eps max |entry| (tested
+ *      at the start of a sweep), max_sweeps at the most: a pose that uses them all is TG_NOT_CONVERGED, its current answer written;
+ *   7. omega2 [B][n_free] ascending (equal values in column order), modes [B][n_free][nq] = (Z L^-T Y)' with zeros at the held
+ *      configs, M-orthonormal and tangent to the constraints, the component of largest magnitude of every shape positive (of equal
+ *      magnitudes the lowest config index decides); rows beyond count = nm are zero.
+ * count, rank, sweeps, status [B]; mu_out [B][nc]; residual [B].  A pose that is TG_SINGULAR (also: a q, multipliers or C that are
+ * not finite) has every numeric output zero.  mu_in, mu_out, residual_out, count_out, rank_out, sweeps_out, status_out may be NULL.
+ * The integrator state of the batch is not touched.  TG_ERR_INVALID for a null q, omega2 or modes, rcond < 0 (or not a number),
+ * max_sweeps < 1, a mask that frees a kinematic config; TG_ERR_UNSUPPORTED for a system with a NonlinearConfigSpring (a force without
+ * a potential, as in the equilibrium search), for the profiling build, and if the workgroup's LDS exceeds 160 KiB
+ * (tg_system_normal_modes_lds: out = team size, doubles per team, bytes per workgroup, 0; computed without a device).  All of these
+ * are refused before a device is touched.
+ * The _device variant takes device pointers (except free), launches on the batch's stream and does not synchronise. */
+int tg_system_normal_modes_lds(const tg_system *sys, int32_t out[4]);
+int tg_batch_normal_modes(tg_batch *b, const double *q_host, const double *mu_host, const int32_t *free_host, double rcond,
+                          int32_t max_sweeps, double *omega2_out, double *modes_out, int32_t *count_out, int32_t *rank_out,
+                          double *mu_out, double *residual_out, int32_t *sweeps_out, int32_t *status_out);
+int tg_batch_normal_modes_device(tg_batch *b, const double *q_dev, const double *mu_dev, const int32_t *free_host, double rcond,
+                                 int32_t max_sweeps, double *omega2_out_dev, double *modes_out_dev, int32_t *count_out_dev,
+                                 int32_t *rank_out_dev, double *mu_out_dev, double *residual_out_dev, int32_t *sweeps_out_dev,
+                                 int32_t *status_out_dev);
+
 /* ---- batched inverse dynamics --------------------------------------------------------------------------------------
  * Given configuration paths Q [B][N + 1][nq] (kinematic configs included; B = the batch size, N = n_steps >= 1), the inputs u_k and
  * constraint forces lambda_k that make the discrete Euler-Lagrange equations hold on every step, and the impulse rho_k that no

@@ -4177,6 +4177,23 @@ struct Core {
         TG_SYNC();
     }
 
+    // The mass matrix over the free configs, summed into LDS (MODE_MODES): M = L_ddqddq as dynamics() sums it over the dynamic pair
+    // list, entry (idx[ca], idx[cb]) of an [ld][ld] image, a config with idx < 0 left out (a kinematic config is in no pair).  Reads the
+    // Jacobians of the pose in q2: potential_lds leaves them.  The inertias are the parameter row's in a PAR core (init_sweep_schedule).
+    TG_HD void mass_lds(bool on, Real *M, int ld, const int *idx) {
+        if (on) TG_FOR(i, ld * ld) M[i] = 0.0;
+        TG_SYNC();
+        if (on) TG_FOR(pp, P.n_npairs) {
+            const int *pw = P.pair4 + 4 * (size_t)pp;
+            const int ia = pw[0], ib = pw[1], ca = idx[pw[2] & 0xFFFF], cb = idx[pw[2] >> 16], b = pw[3];
+            if (ca < 0 || cb < 0) continue;
+            const Real mab = inner6(S + P.o_I + 4 * b, S + P.o_J + 6 * ia, S + P.o_J + 6 * ib);
+            lds_add(&M[ca * ld + cb], mab);
+            if (ia != ib) lds_add(&M[cb * ld + ca], mab);
+        }
+        TG_SYNC();
+    }
+
     // =====================================================================================================
     // First derivatives of the continuous dynamics (reference calc_dynamics_deriv1, system.c:912-1299): d(ddq_d, lambda)
     // / d(q, dq, ddq_k, u).  With r = D - M ddq_d + Ad^T lambda = 0 and g = A ddq + dq^T H dq = 0 solved by `dynamics`,

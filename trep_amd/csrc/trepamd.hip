@@ -19,6 +19,7 @@
 #include "launch_generic.hpp"
 #include "mvi_project.hpp"
 #include "mvi_equilibrium.hpp"
+#include "mvi_modes.hpp"
 #include "mvi_inverse.hpp"
 #include "mvi_frames.hpp"
 #include "mvi_tape.hpp"
@@ -33,6 +34,8 @@ int launch_par(int team, bool springs, const tg::DevProg *d_prog, const tg::RunA
 int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ProjectArgs &J, int grid, size_t lds, hipStream_t stream);
 // the equilibrium-search kernel and its parameter-table twin (trepamd_equilibrium.hip, likewise)
 int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+// the normal-modes kernel and its parameter-table twin (trepamd_modes.hip, likewise)
+int launch_modes(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ModesArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the inverse-dynamics kernel and its parameter-table twin (trepamd_inverse.hip, likewise)
 int launch_inverse(int team, bool springs, bool par, int solve, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the frame-kinematics kernel (trepamd_frames.hip, likewise)
@@ -144,6 +147,9 @@ struct tg_batch {
     tg::DeviceBuffer<double> pose;    // staging of the host-facing pose solvers (stream-ordered, one call at a time): q0 in, q, mu out, and
                                       // the projection's dq0 in, dq out or the equilibrium search's V out
     tg::DeviceBuffer<int> pose_ints;  // their free mask [nq], iteration [batch] and status [batch] words
+    tg::DeviceBuffer<double> modes_stage;   // staging of the host-facing normal-modes call: q, mu in; omega2, modes, mu, residual out
+    tg::DeviceBuffer<int> modes_ints;       // its free mask [nq] (both entry points), then count, rank, sweeps, status [batch] each
+    std::vector<int32_t> modes_mask;        // the mask as the host built it (kinematic configs cleared)
     // frame table of tg_batch_frame_kinematics (mvi_frames.hpp, FrameArgs::tab / ::off) for the selection frames_sel: rebuilt only
     // when a call's selection differs from it, reallocated only when it grows
     std::vector<int32_t> frames_sel;
@@ -1214,6 +1220,97 @@ int tg_batch_minimize_potential(tg_batch *b, const double *q_host, const int32_t
     if (int rc = tg_batch_minimize_potential_device(b, s.q0, free_host ? s.mask : nullptr, tolerance, max_iterations, s.q, s.mu, s.extra, s.iters, s.status)) return rc;
     if (v_out) HIP_TRY(hipMemcpyAsync(v_out, s.extra, (size_t)b->batch * 2 * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     return pose_stage_out(b, s, q_out, mu_out, iterations_out, status_out);
+}
+
+// ---- batched normal modes (mvi_modes.hpp): one team per pose, one launch
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the normal-modes kernel for this system (out[0..2]; out[3] 0):
+ * the rollout slice plus the image, K, M, four [nq][nq | 1] images, q0, V_q, g, V, the least-squares and Jacobi scratch, the
+ * eigenvalues and their places, the row scales and the free configs' places (mvi_modes.hpp: modes_layout).  TG_ERR_UNSUPPORTED, with out
+ * filled, above the 160 KiB a workgroup can have, for a system with a NonlinearConfigSpring and in the profiling build. */
+int tg_system_normal_modes_lds(const tg_system *sys, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    tg::ModesArgs J{};
+    tg::modes_layout(sys->H.p.lds_per_team, sys->H.p.nq, sys->H.p.nc, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident normal-modes kernel", out);
+    if (sys->H.p.n_ncs > 0) return fail(TG_ERR_UNSUPPORTED, "a NonlinearConfigSpring has a force but no potential energy (as in the reference): no stiffness to take modes of");
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no normal-modes kernel");
+#endif
+    return rc;
+}
+
+// what both entry points check before a device is touched; the mask the kernel gets (kinematic configs cleared) and n_free
+static int modes_check(tg_batch *b, const double *q, const int32_t *free_host, double rcond, int32_t max_sweeps, const double *omega2, const double *modes,
+                       int32_t geo[4], int &n_free) {
+    if (!b || !q || !omega2 || !modes) return fail(TG_ERR_INVALID, "null argument");
+    if (!(rcond >= 0.0)) return fail(TG_ERR_INVALID, "rcond must not be negative");
+    if (max_sweeps < 1) return fail(TG_ERR_INVALID, "max_sweeps must be at least 1");
+    const int nq = b->sys->H.p.nq, nd = b->sys->H.p.nd;
+    if (free_host) for (int k = nd; k < nq; k++) if (free_host[k]) return fail(TG_ERR_INVALID, "a kinematic config cannot be free: its motion is prescribed");
+    if (int rc = tg_system_normal_modes_lds(b->sys, geo)) return rc;
+    b->modes_mask.assign((size_t)nq, 0);
+    n_free = 0;
+    for (int k = 0; k < nd; k++) if (!free_host || free_host[k]) { b->modes_mask[k] = 1; n_free++; }
+    return TG_SUCCESS;
+}
+
+static int modes_launch(tg_batch *b, const int32_t geo[4], int n_free, const double *q_dev, const double *mu_dev, double rcond, int32_t max_sweeps,
+                        double *omega2, double *modes, int32_t *count, int32_t *rank, double *mu_out, double *residual, int32_t *sweeps, int32_t *status) {
+    tg::RunArgs A;
+    int grid;
+    if (int rc = pose_prepare(b, tg::MODE_MODES, 1.0, max_sweeps, sweeps, status, A, grid)) return rc;
+    const size_t nq = b->P.nq;
+    HIP_TRY(b->modes_ints.ensure(nq + 4 * (size_t)b->batch));
+    if (nq) HIP_TRY(hipMemcpyAsync(b->modes_ints.get(), b->modes_mask.data(), nq * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    tg::ModesArgs J{};
+    tg::modes_layout(b->P.lds_per_team, b->P.nq, b->P.nc, J);
+    J.free_mask = b->modes_ints.get(); J.q0 = q_dev; J.mu_in = mu_dev; J.q = nullptr; J.mu = mu_out; J.omega2 = omega2; J.modes = modes;
+    J.residual = residual; J.count = count; J.rank = rank; J.rcond = rcond; J.n_free = n_free; J.max_sweeps = max_sweeps;
+    const bool par = b->par_rows > 0;
+    int rc = tg_detail::launch_modes(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+                                     tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0}, grid,
+                                     (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[par][0].add(tg::MODE_MODES);
+    return rc;
+}
+
+int tg_batch_normal_modes_device(tg_batch *b, const double *q_dev, const double *mu_dev, const int32_t *free_host, double rcond, int32_t max_sweeps,
+                                 double *omega2_out_dev, double *modes_out_dev, int32_t *count_out_dev, int32_t *rank_out_dev, double *mu_out_dev,
+                                 double *residual_out_dev, int32_t *sweeps_out_dev, int32_t *status_out_dev) {
+    int32_t geo[4];
+    int n_free;
+    if (int rc = modes_check(b, q_dev, free_host, rcond, max_sweeps, omega2_out_dev, modes_out_dev, geo, n_free)) return rc;
+    return modes_launch(b, geo, n_free, q_dev, mu_dev, rcond, max_sweeps, omega2_out_dev, modes_out_dev, count_out_dev, rank_out_dev, mu_out_dev,
+                        residual_out_dev, sweeps_out_dev, status_out_dev);
+}
+
+int tg_batch_normal_modes(tg_batch *b, const double *q_host, const double *mu_host, const int32_t *free_host, double rcond, int32_t max_sweeps,
+                          double *omega2_out, double *modes_out, int32_t *count_out, int32_t *rank_out, double *mu_out, double *residual_out,
+                          int32_t *sweeps_out, int32_t *status_out) {
+    int32_t geo[4];
+    int n_free;
+    if (int rc = modes_check(b, q_host, free_host, rcond, max_sweeps, omega2_out, modes_out, geo, n_free)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc, nF = (size_t)n_free;
+    HIP_TRY(b->modes_stage.ensure(B * (nq + 2 * nc + nF + nF * nq + 1)));
+    HIP_TRY(b->modes_ints.ensure(nq + 4 * B));
+    double *q = b->modes_stage.get(), *mu_in = q + B * nq, *o2 = mu_in + B * nc, *md = o2 + B * nF, *mu = md + B * nF * nq, *res = mu + B * nc;
+    int *count = b->modes_ints.get() + nq, *rank = count + B, *sweeps = rank + B, *status = sweeps + B;
+    HIP_TRY(hipMemcpyAsync(q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (mu_host && nc) HIP_TRY(hipMemcpyAsync(mu_in, mu_host, B * nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (int rc = modes_launch(b, geo, n_free, q, mu_host && nc ? mu_in : nullptr, rcond, max_sweeps, o2, md, count, rank, mu, res, sweeps, status)) return rc;
+    if (nF) HIP_TRY(hipMemcpyAsync(omega2_out, o2, B * nF * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (nF && nq) HIP_TRY(hipMemcpyAsync(modes_out, md, B * nF * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (residual_out) HIP_TRY(hipMemcpyAsync(residual_out, res, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (count_out) HIP_TRY(hipMemcpyAsync(count_out, count, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (rank_out) HIP_TRY(hipMemcpyAsync(rank_out, rank, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (sweeps_out) HIP_TRY(hipMemcpyAsync(sweeps_out, sweeps, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return TG_SUCCESS;
 }
 
 // ---- batched inverse dynamics (mvi_inverse.hpp): one team per (trajectory, step), one launch

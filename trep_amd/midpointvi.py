@@ -22,6 +22,23 @@ from .errors import ConvergenceError
 
 Projection = collections.namedtuple("Projection", "Q dQ mu iterations status")      # BatchMidpointVI.satisfy_constraints
 Equilibrium = collections.namedtuple("Equilibrium", "Q mu V iterations status")     # BatchMidpointVI.minimize_potential_energy
+
+
+class NormalModes(collections.namedtuple("NormalModes", "omega2 modes count rank mu residual sweeps status")):      # BatchMidpointVI.normal_modes
+    """omega2 [B][nF] ascending, modes [B][nF][nq], count, rank [B], mu [B][nc], residual [B], sweeps, status [B]; rows beyond
+    count are zero."""
+    __slots__ = ()
+
+    @property
+    def frequencies(self):
+        """Natural frequencies in Hz, [B][nF] (formed on the host): NaN where omega2 < 0 (an unstable direction has none)."""
+        w2 = np.asarray(self.omega2, dtype=float)
+        return np.sqrt(np.where(w2 >= 0.0, w2, np.nan)) / (2.0 * np.pi)
+
+    @property
+    def unstable(self):
+        """[B]: the number of negative omega2 of every pose (formed on the host); 0 for a minimum of the potential."""
+        return (np.asarray(self.omega2) < 0.0).sum(axis=1).astype(np.int32)
 InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h status")     # BatchMidpointVI.inverse_dynamics
 FrameKinematics = collections.namedtuple("FrameKinematics", "g vb p_dq vb_ddq")         # BatchMidpointVI.frame_kinematics
 TapeMeasures = collections.namedtuple("TapeMeasures", "length velocity length_dq velocity_dq length_dqdq")      # BatchMidpointVI.tape_measures
@@ -701,6 +718,41 @@ class BatchMidpointVI(object):
                                                        int(max_iterations), _lib.ptr(q), _lib.ptr(mu), _lib.ptr(v), iters.ctypes.data,
                                                        status.ctypes.data))
         return Equilibrium(q, mu, v, iters, status)
+
+    def normal_modes(self, Q, mu=None, constant_q_list=None, rcond=1e-9, max_sweeps=30):
+        """Natural frequencies and mode shapes of B poses in one launch (include/trep_amd.h, tg_batch_normal_modes): per pose the
+        eigenproblem K phi = omega^2 M phi on the tangent space of the constraints, over the free configs -- every dynamic config
+        outside constant_q_list (names or Config objects); a kinematic config is never free.  K = V_qq + sum_c mu_c h_c,qq and M = L_ddqddq at rest; with a
+        parameter table (set_parameters) each pose under its own row's masses, inertias and gravity.  Q [B][nq].  mu [B][nc]: the
+        constraints' multipliers at the pose, for example those minimize_potential_energy returned; None: the least-squares
+        multipliers under rcond.  Returns the namedtuple NormalModes(omega2 [B][nF] ascending, modes [B][nF][nq] -- M-orthonormal,
+        tangent to the constraints, zero at the held configs, the component of largest magnitude positive --, count [B] = nF - rank,
+        rank [B] of Dh over the free configs, mu [B][nc], residual [B] = |V_q + Dh' mu|inf over the free configs, sweeps [B], status
+        [B]); rows beyond count are zero.  .frequencies (Hz, NaN where omega2 < 0) and .unstable (negative omega2 per pose) are
+        formed on the host.  A pose with residual > 0 is not at rest: its modes are those of the motion linearised with the
+        unbalanced force frozen, i.e. of the quadratic model of V + mu.h at that pose -- meaningful only as far as the residual is
+        small.  status: TG_OK; TG_NOT_CONVERGED the Jacobi sweeps ran out (the current answer is returned); TG_SINGULAR the reduced
+        mass matrix is not positive definite (a massless free config) or the pose is not finite: every output of that pose is
+        zero.  Nothing is raised for a pose that fails.  The integrator state of the batch is left alone."""
+        self.refresh()
+        B = self._batch
+        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
+        free = np.array([0 if c.kinematic else 1 for c in self._system.configs], dtype=np.int32)
+        if constant_q_list:
+            free &= self.free_mask(False, constant_q_list)
+        nF = int(free.sum())
+        mu_in = None if mu is None else _lib.as_f64(np.broadcast_to(np.asarray(mu, dtype=float), (B, self.nc)), (B, self.nc))
+        omega2, modes = np.zeros((B, nF)), np.zeros((B, nF, self.nq))
+        count, rank = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        mu_out, residual = np.zeros((B, self.nc)), np.zeros(B)
+        sweeps, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        rc = self._L.tg_batch_normal_modes(self._h, _lib.ptr(Q), _lib.ptr(mu_in), free.ctypes.data, float(rcond), int(max_sweeps),
+                                           omega2.ctypes.data, modes.ctypes.data, count.ctypes.data, rank.ctypes.data, _lib.ptr(mu_out),
+                                           residual.ctypes.data, sweeps.ctypes.data, status.ctypes.data)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        return NormalModes(omega2, modes, count, rank, mu_out, residual, sweeps, status)
 
     def _with_step_sizes(self, dts, call):
         """call() under the by-step list dts (None: as the batch stands); the list set before is put back."""
