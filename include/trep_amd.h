@@ -517,6 +517,47 @@ int tg_batch_normal_modes_device(tg_batch *b, const double *q_dev, const double 
                                  int32_t *rank_out_dev, double *mu_out_dev, double *residual_out_dev, int32_t *sweeps_out_dev,
                                  int32_t *status_out_dev);
 
+/* ---- batched static response ----------------------------------------------------------------------------------------
+ * How a rest pose and its constraint forces answer a moved held config and a load, for every pose of the batch in one launch
+ * (tests/static_response_reference.py is the specification).  free [nq] (HOST memory in both variants, as the drive list is: they
+ * are the launch's and are checked before a device is touched), NULL: every config; F the free configs, n_free of them, H the held
+ * ones.  drive [n_drive]: the driven configs, distinct and all held; E selects them.  Per pose, at rest (dq = 0) at the input pose,
+ * under the pose's parameter row if a table is set (its twin is mode 16 in tg_batch_par_info, the default kernel mode 16 in
+ * tg_batch_info):
+ *   1. V_q, V_qq over all configs, h, Dh, D_F = Dh[:, F], D_H = Dh[:, H];
+ *   2. mu [B][nc] as supplied (mu_in, for example what tg_batch_minimize_potential returned), or (NULL) the minimum-norm minimiser
+ *      of |V_q[F] + D_F' mu| by column-pivoted QR under rcond; residual = |V_q[F] + D_F' mu|inf says how far the pose is from rest;
+ *   3. W = V_qq + sum_c mu_c h_c,qq over all config pairs; the blocks W_FF and W_FH are used;
+ *   4. column-pivoted Householder QR of D_F' with the identity carried along; r = the rank under rcond, Z = the last n_free - r
+ *      columns of Q (the identity without constraints); the pseudo-inverses below are those of the rank-r part, through the same
+ *      factorisation (a second, unpivoted stage where r < nc), minimum norm;
+ *   5. K_r = Z' W_FF Z, symmetrised; unpivoted Cholesky, a pivot that is not > 0 ends the pose with TG_SINGULAR (the pose is not a
+ *      strict minimum on the tangent space of the constraints);
+ *   6. the drive response: X_p = -D_F^+ D_H E, X = X_p + Z K_r^-1 Z' (-W_FH E - W_FF X_p), dmu = -(D_F')^+ (W_FF X + W_FH E);
+ *      defect = |D_F X + D_H E|inf, non-zero only where the constraints cannot follow the drive;
+ *   7. with_compliance: C = Z K_r^-1 Z' and R = (D_F')^+ (I - W_FF C): a generalized force f on the free configs' equations
+ *      V_q[F] + D_F' mu = f moves the pose by C f and the multipliers by R f.
+ * dq [B][n_drive][nq]: row j = the pose's derivative along driven config j (X[:, j] at F, 1 at its own place, 0 at the other held
+ * configs); dmu [B][n_drive][nc]; compliance [B][nq][nq] = C with zero rows and columns at H; reaction [B][nq][nc] = R' with zero
+ * rows at H; rank, status [B]; mu_out [B][nc]; residual, defect [B].  A pose that is TG_SINGULAR (also: a q, multipliers or result
+ * that are not finite) has every numeric output zero; nothing else is reported per pose.  mu_in, rank_out, mu_out, residual_out,
+ * defect_out, status_out may be NULL; dq and dmu only with n_drive == 0, compliance and reaction only without with_compliance.
+ * The integrator state of the batch is not touched.  TG_ERR_INVALID for a null q, rcond < 0 (or not a number), a drive entry that
+ * is free, out of range or repeated, and for n_drive == 0 without with_compliance (nothing to compute); TG_ERR_UNSUPPORTED for a
+ * system with a NonlinearConfigSpring (a force without a potential, as in the equilibrium search), for the profiling build, and if
+ * the workgroup's LDS exceeds 160 KiB (tg_system_static_response_lds for these sizes of a launch: out = team size, doubles per
+ * team, bytes per workgroup, 0; computed without a device).  All of these are refused before a device is touched.
+ * The _device variant takes device pointers (except free and drive), launches on the batch's stream and does not synchronise. */
+int tg_system_static_response_lds(const tg_system *sys, int32_t n_free, int32_t n_drive, int32_t with_compliance, int32_t out[4]);
+int tg_batch_static_response(tg_batch *b, const double *q_host, const double *mu_host, const int32_t *free_host, int32_t n_drive,
+                             const int32_t *drive_host, int32_t with_compliance, double rcond, double *dq_out, double *dmu_out,
+                             double *compliance_out, double *reaction_out, int32_t *rank_out, double *mu_out, double *residual_out,
+                             double *defect_out, int32_t *status_out);
+int tg_batch_static_response_device(tg_batch *b, const double *q_dev, const double *mu_dev, const int32_t *free_host, int32_t n_drive,
+                                    const int32_t *drive_host, int32_t with_compliance, double rcond, double *dq_out_dev,
+                                    double *dmu_out_dev, double *compliance_out_dev, double *reaction_out_dev, int32_t *rank_out_dev,
+                                    double *mu_out_dev, double *residual_out_dev, double *defect_out_dev, int32_t *status_out_dev);
+
 /* ---- batched inverse dynamics --------------------------------------------------------------------------------------
  * Given configuration paths Q [B][N + 1][nq] (kinematic configs included; B = the batch size, N = n_steps >= 1), the inputs u_k and
  * constraint forces lambda_k that make the discrete Euler-Lagrange equations hold on every step, and the impulse rho_k that no

@@ -165,6 +165,14 @@ _MODES_SIGNATURES = {
     "tg_batch_normal_modes_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# Batched static response: likewise (q, mu, free, n_drive, drive, with_compliance, rcond; dq, dmu, compliance, reaction, rank, mu,
+# residual, defect, status).
+_RESPONSE_SIGNATURES = {
+    "tg_system_static_response_lds": (ctypes.c_int, [_vp, _i32, _i32, _i32, _c_ip]),
+    "tg_batch_static_response": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tg_batch_static_response_device": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 # Batched inverse dynamics: likewise.
 _INVERSE_SIGNATURES = {
     "tg_system_inverse_dynamics_lds": (ctypes.c_int, [_vp, _c_ip]),
@@ -234,7 +242,7 @@ def lib():
         # and it must be in the environment before the HIP runtime initialises, i.e. before the library that links it is loaded.
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()) + list(_MODES_SIGNATURES.items()) + list(_INVERSE_SIGNATURES.items()) + list(_FRAMES_SIGNATURES.items()) + list(_TAPE_SIGNATURES.items()) + list(_DYN_INVERSE_SIGNATURES.items()) + list(_LSQ_SIGNATURES.items()) + list(_BOUNDED_SIGNATURES.items()):
+        for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_PROJECTION_SIGNATURES.items()) + list(_EQUILIBRIUM_SIGNATURES.items()) + list(_MODES_SIGNATURES.items()) + list(_RESPONSE_SIGNATURES.items()) + list(_INVERSE_SIGNATURES.items()) + list(_FRAMES_SIGNATURES.items()) + list(_TAPE_SIGNATURES.items()) + list(_DYN_INVERSE_SIGNATURES.items()) + list(_LSQ_SIGNATURES.items()) + list(_BOUNDED_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -243,7 +251,7 @@ def lib():
 
 
 def exported_symbols():
-    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES) + list(_MODES_SIGNATURES) + list(_INVERSE_SIGNATURES) + list(_FRAMES_SIGNATURES) + list(_TAPE_SIGNATURES) + list(_DYN_INVERSE_SIGNATURES) + list(_LSQ_SIGNATURES) + list(_BOUNDED_SIGNATURES))
+    return sorted(list(_SIGNATURES) + list(_PROJECTION_SIGNATURES) + list(_EQUILIBRIUM_SIGNATURES) + list(_MODES_SIGNATURES) + list(_RESPONSE_SIGNATURES) + list(_INVERSE_SIGNATURES) + list(_FRAMES_SIGNATURES) + list(_TAPE_SIGNATURES) + list(_DYN_INVERSE_SIGNATURES) + list(_LSQ_SIGNATURES) + list(_BOUNDED_SIGNATURES))
 
 
 def check(rc):

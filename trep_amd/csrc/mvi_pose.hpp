@@ -114,6 +114,19 @@ struct PoseFrame {
             if (na != nb) lds_add(&M[a * ldm + b], h);
         }
     }
+    // the same over the places `at` [nq] gives the configs (-1: left out) instead of the frame's own: the identity for every config pair,
+    // kinematic configs included (mvi_response.hpp)
+    template <class CORE>
+    TG_HD void add_curvature(CORE &core, double *M, int ldm, const int *at) {
+        for (int pp = tg_opaque(lane); pp < P.n_cpair; pp += TEAM) {
+            const int *pw = P.cpair4 + 4 * (size_t)pp;
+            const int c = pw[0], na = pw[1], nb = pw[2], a = at[pw[3] & 0xFFFF], b = at[pw[3] >> 16];
+            if (a < 0 || b < 0) continue;
+            const double h = S[P.o_lam + c] * core.con_d2(c, na, nb);
+            lds_add(&M[b * ldm + a], h);
+            if (na != nb) lds_add(&M[a * ldm + b], h);
+        }
+    }
     // the answer of a live team: the pose, the multipliers, the iteration and status words
     template <class ARGS>
     TG_HD void store(ARGS &A, int iterations, int status) {

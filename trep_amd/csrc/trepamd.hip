@@ -20,6 +20,7 @@
 #include "mvi_project.hpp"
 #include "mvi_equilibrium.hpp"
 #include "mvi_modes.hpp"
+#include "mvi_response.hpp"
 #include "mvi_inverse.hpp"
 #include "mvi_frames.hpp"
 #include "mvi_tape.hpp"
@@ -36,6 +37,8 @@ int launch_project(int team, bool springs, const tg::DevProg *d_prog, const tg::
 int launch_equilibrium(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::EquilibriumArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the normal-modes kernel and its parameter-table twin (trepamd_modes.hip, likewise)
 int launch_modes(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ModesArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
+// the static-response kernel and its parameter-table twin (trepamd_response.hip, likewise)
+int launch_response(int team, bool springs, bool par, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::ResponseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the inverse-dynamics kernel and its parameter-table twin (trepamd_inverse.hip, likewise)
 int launch_inverse(int team, bool springs, bool par, int solve, const tg::DevProg *d_prog, const tg::RunArgs &A, const tg::InverseArgs &J, const tg::ParTable &T, int grid, size_t lds, hipStream_t stream);
 // the frame-kinematics kernel (trepamd_frames.hip, likewise)
@@ -150,6 +153,9 @@ struct tg_batch {
     tg::DeviceBuffer<double> modes_stage;   // staging of the host-facing normal-modes call: q, mu in; omega2, modes, mu, residual out
     tg::DeviceBuffer<int> modes_ints;       // its free mask [nq] (both entry points), then count, rank, sweeps, status [batch] each
     std::vector<int32_t> modes_mask;        // the mask as the host built it (kinematic configs cleared)
+    tg::DeviceBuffer<double> response_stage;   // staging of the host-facing static-response call: q, mu in; dq, dmu, C, R, mu, residual, defect out
+    tg::DeviceBuffer<int> response_ints;       // its free mask [nq] and drive list [n_drive] (both entry points), then rank, status [batch] each
+    std::vector<int32_t> response_mask;        // mask [nq] and drive list as the host checked them
     // frame table of tg_batch_frame_kinematics (mvi_frames.hpp, FrameArgs::tab / ::off) for the selection frames_sel: rebuilt only
     // when a call's selection differs from it, reallocated only when it grows
     std::vector<int32_t> frames_sel;
@@ -1308,6 +1314,117 @@ int tg_batch_normal_modes(tg_batch *b, const double *q_host, const double *mu_ho
     if (count_out) HIP_TRY(hipMemcpyAsync(count_out, count, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     if (rank_out) HIP_TRY(hipMemcpyAsync(rank_out, rank, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     if (sweeps_out) HIP_TRY(hipMemcpyAsync(sweeps_out, sweeps, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return TG_SUCCESS;
+}
+
+// ---- batched static response (mvi_response.hpp): one team per pose, one launch
+
+/* Team size, doubles of LDS per team and bytes of LDS per workgroup of the static-response kernel for this system and these sizes
+ * of a launch (out[0..2]; out[3] 0): the rollout slice plus the image, W, the pseudo-inverse, K_r, a work area and the two column
+ * blocks X and G [n_free][n_drive (+ n_free with the compliance)], q0, V_q, V, the least-squares scratch, the free configs' list, the
+ * identity index, the row scales and the free configs' places (mvi_response.hpp: response_layout).  TG_ERR_UNSUPPORTED, with out filled,
+ * above the 160 KiB a workgroup can have, for a system with a NonlinearConfigSpring and in the profiling build. */
+int tg_system_static_response_lds(const tg_system *sys, int32_t n_free, int32_t n_drive, int32_t with_compliance, int32_t out[4]) {
+    if (!sys || !out) return fail(TG_ERR_INVALID, "null argument");
+    const int nq = sys->H.p.nq;
+    if (n_free < 0 || n_drive < 0 || n_free > nq || n_drive > nq - n_free) return fail(TG_ERR_INVALID, "n_free configs free and n_drive of the others driven: more than the system has");
+    tg::ResponseArgs J{};
+    tg::response_layout(sys->H.p.lds_per_team, nq, sys->H.p.nc, n_free, n_drive, with_compliance != 0, J);
+    const int rc = pose_lds(sys, J.lds_per_team, "system too large for the LDS-resident static-response kernel", out);
+    if (sys->H.p.n_ncs > 0) return fail(TG_ERR_UNSUPPORTED, "a NonlinearConfigSpring has a force but no potential energy (as in the reference): no stiffness to respond with");
+#if defined(TG_PROFILE)
+    if (rc == TG_SUCCESS) return fail(TG_ERR_UNSUPPORTED, "the profiling build has no static-response kernel");
+#endif
+    return rc;
+}
+
+// what both entry points check before a device is touched; the mask and the drive list the kernel gets, and n_free
+static int response_check(tg_batch *b, const double *q, const int32_t *free_host, int32_t n_drive, const int32_t *drive_host, int32_t with_compliance,
+                          double rcond, const double *dq, const double *dmu, const double *compliance, const double *reaction, int32_t geo[4], int &n_free) {
+    if (!b || !q) return fail(TG_ERR_INVALID, "null argument");
+    if (!(rcond >= 0.0)) return fail(TG_ERR_INVALID, "rcond must not be negative");
+    if (n_drive < 0 || (n_drive > 0 && (!drive_host || !dq || !dmu))) return fail(TG_ERR_INVALID, "n_drive configs driven: drive, dq and dmu are needed");
+    if (with_compliance && (!compliance || !reaction)) return fail(TG_ERR_INVALID, "null argument");
+    if (n_drive == 0 && !with_compliance) return fail(TG_ERR_INVALID, "nothing to compute: no config driven and no compliance asked");
+    const int nq = b->sys->H.p.nq;
+    b->response_mask.assign((size_t)nq, 0);
+    n_free = 0;
+    for (int k = 0; k < nq; k++) if (!free_host || free_host[k]) { b->response_mask[k] = 1; n_free++; }
+    for (int j = 0; j < n_drive; j++) {
+        const int k = drive_host[j];
+        if (k < 0 || k >= nq) return fail(TG_ERR_INVALID, "a driven config is out of range");
+        if (b->response_mask[k]) return fail(TG_ERR_INVALID, "a driven config is free: only a held config can be driven");
+        for (int i = 0; i < j; i++) if (drive_host[i] == k) return fail(TG_ERR_INVALID, "a config is driven twice");
+    }
+    if (int rc = tg_system_static_response_lds(b->sys, n_free, n_drive, with_compliance, geo)) return rc;
+    b->response_mask.insert(b->response_mask.end(), drive_host, drive_host + n_drive);
+    return TG_SUCCESS;
+}
+
+static int response_launch(tg_batch *b, const int32_t geo[4], int n_free, int n_drive, bool loads, const double *q_dev, const double *mu_dev, double rcond,
+                           double *dq, double *dmu, double *compliance, double *reaction, int32_t *rank, double *mu_out, double *residual, double *defect,
+                           int32_t *status) {
+    tg::RunArgs A;
+    int grid;
+    if (int rc = pose_prepare(b, tg::MODE_RESPONSE, 1.0, 0, nullptr, status, A, grid)) return rc;
+    const size_t nq = b->P.nq, words = nq + (size_t)n_drive;
+    HIP_TRY(b->response_ints.ensure(words + 2 * (size_t)b->batch));
+    if (words) HIP_TRY(hipMemcpyAsync(b->response_ints.get(), b->response_mask.data(), words * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    tg::ResponseArgs J{};
+    tg::response_layout(b->P.lds_per_team, b->P.nq, b->P.nc, n_free, n_drive, loads, J);
+    J.free_mask = b->response_ints.get(); J.drive = b->response_ints.get() + nq; J.q0 = q_dev; J.mu_in = mu_dev; J.q = nullptr; J.mu = mu_out;
+    J.dq = dq; J.dmu = dmu; J.compliance = compliance; J.reaction = reaction; J.residual = residual; J.defect = defect; J.rank = rank;
+    J.rcond = rcond; J.n_free = n_free; J.n_drive = n_drive; J.loads = loads ? 1 : 0;
+    const bool par = b->par_rows > 0;
+    int rc = tg_detail::launch_response(b->sys->team, launch_springs(b), par, b->d_prog.get(), A, J,
+                                        tg::ParTable{par ? b->par_dev.get() : nullptr, par ? b->par_group : 1, par ? b->par_stride : 0}, grid,
+                                        (size_t)geo[2], b->stream);
+    if (rc == TG_SUCCESS && hipGetLastError() != hipSuccess) rc = fail(TG_ERR_HIP, "kernel launch failed");
+    if (rc == TG_SUCCESS) b->launched[par][0].add(tg::MODE_RESPONSE);
+    return rc;
+}
+
+int tg_batch_static_response_device(tg_batch *b, const double *q_dev, const double *mu_dev, const int32_t *free_host, int32_t n_drive,
+                                    const int32_t *drive_host, int32_t with_compliance, double rcond, double *dq_out_dev, double *dmu_out_dev,
+                                    double *compliance_out_dev, double *reaction_out_dev, int32_t *rank_out_dev, double *mu_out_dev,
+                                    double *residual_out_dev, double *defect_out_dev, int32_t *status_out_dev) {
+    int32_t geo[4];
+    int n_free;
+    if (int rc = response_check(b, q_dev, free_host, n_drive, drive_host, with_compliance, rcond, dq_out_dev, dmu_out_dev, compliance_out_dev,
+                                reaction_out_dev, geo, n_free)) return rc;
+    return response_launch(b, geo, n_free, n_drive, with_compliance != 0, q_dev, mu_dev, rcond, dq_out_dev, dmu_out_dev, compliance_out_dev,
+                           reaction_out_dev, rank_out_dev, mu_out_dev, residual_out_dev, defect_out_dev, status_out_dev);
+}
+
+int tg_batch_static_response(tg_batch *b, const double *q_host, const double *mu_host, const int32_t *free_host, int32_t n_drive,
+                             const int32_t *drive_host, int32_t with_compliance, double rcond, double *dq_out, double *dmu_out, double *compliance_out,
+                             double *reaction_out, int32_t *rank_out, double *mu_out, double *residual_out, double *defect_out, int32_t *status_out) {
+    int32_t geo[4];
+    int n_free;
+    if (int rc = response_check(b, q_host, free_host, n_drive, drive_host, with_compliance, rcond, dq_out, dmu_out, compliance_out, reaction_out, geo,
+                                n_free)) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const size_t B = (size_t)b->batch, nq = b->P.nq, nc = b->P.nc, nD = (size_t)n_drive, words = nq + nD;
+    const size_t load = with_compliance ? nq * (nq + nc) : 0;
+    HIP_TRY(b->response_stage.ensure(B * (nq + 2 * nc + nD * (nq + nc) + load + 2)));
+    HIP_TRY(b->response_ints.ensure(words + 2 * B));
+    double *q = b->response_stage.get(), *mu_in = q + B * nq, *dq = mu_in + B * nc, *dmu = dq + B * nD * nq, *cm = dmu + B * nD * nc;
+    double *re = cm + (with_compliance ? B * nq * nq : 0), *mu = cm + B * load, *res = mu + B * nc, *def = res + B;
+    int *rank = b->response_ints.get() + words, *status = rank + B;
+    HIP_TRY(hipMemcpyAsync(q, q_host, B * nq * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (mu_host && nc) HIP_TRY(hipMemcpyAsync(mu_in, mu_host, B * nc * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    if (int rc = response_launch(b, geo, n_free, n_drive, with_compliance != 0, q, mu_host && nc ? mu_in : nullptr, rcond, dq, dmu, cm, re, rank, mu, res,
+                                 def, status)) return rc;
+    if (nD && nq) HIP_TRY(hipMemcpyAsync(dq_out, dq, B * nD * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (nD && nc) HIP_TRY(hipMemcpyAsync(dmu_out, dmu, B * nD * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (with_compliance && nq) HIP_TRY(hipMemcpyAsync(compliance_out, cm, B * nq * nq * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (with_compliance && nq && nc) HIP_TRY(hipMemcpyAsync(reaction_out, re, B * nq * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (mu_out && nc) HIP_TRY(hipMemcpyAsync(mu_out, mu, B * nc * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (residual_out) HIP_TRY(hipMemcpyAsync(residual_out, res, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (defect_out) HIP_TRY(hipMemcpyAsync(defect_out, def, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (rank_out) HIP_TRY(hipMemcpyAsync(rank_out, rank, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     if (status_out) HIP_TRY(hipMemcpyAsync(status_out, status, B * sizeof(int), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return TG_SUCCESS;

@@ -39,6 +39,7 @@ class NormalModes(collections.namedtuple("NormalModes", "omega2 modes count rank
     def unstable(self):
         """[B]: the number of negative omega2 of every pose (formed on the host); 0 for a minimum of the potential."""
         return (np.asarray(self.omega2) < 0.0).sum(axis=1).astype(np.int32)
+StaticResponse = collections.namedtuple("StaticResponse", "dq dmu compliance reaction rank mu residual defect status")      # BatchMidpointVI.static_response
 InverseDynamics = collections.namedtuple("InverseDynamics", "U lam P rho h status")     # BatchMidpointVI.inverse_dynamics
 FrameKinematics = collections.namedtuple("FrameKinematics", "g vb p_dq vb_ddq")         # BatchMidpointVI.frame_kinematics
 TapeMeasures = collections.namedtuple("TapeMeasures", "length velocity length_dq velocity_dq length_dqdq")      # BatchMidpointVI.tape_measures
@@ -753,6 +754,68 @@ class BatchMidpointVI(object):
             raise ValueError(self._L.tg_last_error().decode())
         _lib.check(rc)
         return NormalModes(omega2, modes, count, rank, mu_out, residual, sweeps, status)
+
+    def _response_sets(self, keep_kinematic, constant_q_list, drive):
+        """(free [nq] int32, drive [nD] int32) of a static_response call: the mask as minimize_potential_energy builds it, the
+        driven configs (names or Config objects; None: every held config, in config order) as places in system.configs."""
+        free = np.ascontiguousarray(self.free_mask(keep_kinematic, constant_q_list), dtype=np.int32)
+        if drive is None:
+            places = np.flatnonzero(free == 0)
+        else:
+            names = [c.name for c in self._system.configs]
+            places = [names.index(self._system.get_config(c).name) for c in drive]
+        return free, np.ascontiguousarray(places, dtype=np.int32)
+
+    def static_response(self, Q, mu=None, keep_kinematic=False, constant_q_list=None, drive=None, compliance=True, rcond=1e-9):
+        """How B rest poses and their constraint forces answer a moved held config and a load, in one launch (include/trep_amd.h,
+        tg_batch_static_response).  keep_kinematic and constant_q_list mean what they mean for minimize_potential_energy -- pass the
+        same ones: they pick the free configs F, every other config is held.  drive: names or Config objects among the held
+        configs; None: all of them, in config order.  Q [B][nq]: the poses, for example those minimize_potential_energy returned;
+        mu [B][nc]: their multipliers, None: the least-squares multipliers under rcond.  With a parameter table (set_parameters)
+        each pose under its own row's masses and gravity.  Returns the namedtuple StaticResponse(dq [B][nD][nq]: row j the
+        derivative of the rest pose along driven config j -- 1 at its own place, 0 at the other held configs --, dmu [B][nD][nc]
+        the multipliers' derivative, compliance [B][nq][nq]: a generalized force f on the free configs moves the pose by C f,
+        reaction [B][nq][nc]: and the multipliers by R'f (both zero at the held configs; None without compliance=True), rank [B]
+        of Dh over the free configs, mu [B][nc], residual [B] = |V_q + Dh' mu|inf over the free configs, defect [B] =
+        |Dh dq|inf, non-zero only where the constraints cannot follow the drive, status [B]).  status: TG_OK; TG_SINGULAR the
+        pose is not a strict minimum on the tangent space of the constraints (or is not finite): every output of that pose is
+        zero.  Nothing is raised for a pose that fails.  The integrator state of the batch is left alone."""
+        self.refresh()
+        B = self._batch
+        Q = _lib.as_f64(np.broadcast_to(np.asarray(Q, dtype=float), (B, self.nq)), (B, self.nq))
+        free, places = self._response_sets(keep_kinematic, constant_q_list, drive)
+        nD = len(places)
+        mu_in = None if mu is None else _lib.as_f64(np.broadcast_to(np.asarray(mu, dtype=float), (B, self.nc)), (B, self.nc))
+        dq, dmu = np.zeros((B, nD, self.nq)), np.zeros((B, nD, self.nc))
+        C = np.zeros((B, self.nq, self.nq)) if compliance else None
+        R = np.zeros((B, self.nq, self.nc)) if compliance else None
+        rank, status = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        mu_out, residual, defect = np.zeros((B, self.nc)), np.zeros(B), np.zeros(B)
+        rc = self._L.tg_batch_static_response(self._h, _lib.ptr(Q), _lib.ptr(mu_in), free.ctypes.data, nD, places.ctypes.data, 1 if compliance else 0,
+                                              float(rcond), dq.ctypes.data, dmu.ctypes.data, None if C is None else C.ctypes.data,
+                                              None if R is None else R.ctypes.data, rank.ctypes.data, _lib.ptr(mu_out), residual.ctypes.data,
+                                              defect.ctypes.data, status.ctypes.data)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        return StaticResponse(dq, dmu, C, R, rank, mu_out, residual, defect, status)
+
+    def static_response_device(self, Q_dev, mu_dev=None, keep_kinematic=False, constant_q_list=None, drive=None, compliance=True, rcond=1e-9,
+                               dq_dev=None, dmu_dev=None, compliance_dev=None, reaction_dev=None, rank_dev=None, mu_out_dev=None,
+                               residual_dev=None, defect_dev=None, status_dev=None):
+        """static_response on device pointers, asynchronous on the batch's stream (tg_batch_static_response_device).  Q_dev
+        [B][nq], mu_dev [B][nc] or None; the outputs are laid out as static_response returns them.  dq_dev and dmu_dev are needed
+        where a config is driven, compliance_dev and reaction_dev with compliance=True; the others may be None.  The mask and the
+        drive list stay host arguments.  Returns the number of driven configs."""
+        self.refresh()
+        free, places = self._response_sets(keep_kinematic, constant_q_list, drive)
+        rc = self._L.tg_batch_static_response_device(self._h, Q_dev, mu_dev, free.ctypes.data, len(places), places.ctypes.data, 1 if compliance else 0,
+                                                     float(rcond), dq_dev, dmu_dev, compliance_dev, reaction_dev, rank_dev, mu_out_dev, residual_dev,
+                                                     defect_dev, status_dev)
+        if rc == _lib.ERR_INVALID:
+            raise ValueError(self._L.tg_last_error().decode())
+        _lib.check(rc)
+        return len(places)
 
     def _with_step_sizes(self, dts, call):
         """call() under the by-step list dts (None: as the batch stands); the list set before is put back."""
